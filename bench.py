@@ -22,6 +22,13 @@ Workloads (BASELINE.json configs; the default is the largest single-GPU config, 
 Algorithmic bytes: topk / qsgd / ident 4*N*D + 4*D; randk 4*N*K + 4*D (device-RNG
 indices cost no bytes).  value = algorithmic bytes of all ranks / max-over-ranks step time.
 
+A plain run sets up, warms up, times exactly --steps steps and prints the result line (metric,
+value, ms_per_step, config, ...); --dump-outputs DIR then also writes the [D] direction of the last
+timed step as DIR/direction.npy (float32; the rows and the device-RNG keys are seeded, so two builds
+run with the same arguments can be compared output for output).  Everything below is measured only
+with --full, after the timed steps, and adds the roofline, cpu_baseline, strong_c4 and multi_gpu
+blocks to the line.
+
 roofline: the dominant kernel's algorithmic bytes per step / its summed launch time per step, timed
 with HIP events on its launch stream (flc_profile_*) in a second pass of the same K steps right after
 the timed region (the event packets between launches would lengthen the timed steps); peak 8.0 TB/s
@@ -519,6 +526,25 @@ def dropin(args):
                               "and uploads it; the second line reuses the drawn patterns"}))
 
 
+DUMP_BYTES = 64_000_000    # --dump-outputs: everything it writes stays within this
+DUMP_SEED = 20241015
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller (device tensors), each written
+    as path/<name>.npy in float32.  The DUMP_BYTES budget is shared evenly; an array over its share
+    is written as a fixed sample of its flattened elements (sorted indices drawn with replacement
+    from numpy's default_rng(DUMP_SEED), the same for every run and build)."""
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BYTES - 4096 * len(arrays)) // (4 * len(arrays))      # elements per array (.npy headers aside)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.numel(), size=share))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.to(torch.float32).cpu().numpy())
+
+
 def dist_info(dist, dev, d, reps=5):
     """What the process group really was, so that "RCCL saw N ranks" can be
     checked from the bench line itself: the group's own world size and backend, every rank's host,
@@ -674,7 +700,13 @@ def main():
     # ambiguous abbreviation of its own options)
     ap.add_argument("--n", "--clients", dest="n", type=int, default=None, help="override clients per GPU")
     ap.add_argument("--d", "--dim", dest="d", type=int, default=None, help="override D")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the dominant "
+                         "kernel's roofline (a second pass of the steps under HIP events, the read ceiling, PMC "
+                         "traffic on file), the CPU baseline, the strong_c4 block and, with --gpus G > 1, multi_gpu")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-counts-overlap", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dist", choices=["normal", "heavy"], default="normal",
                     help="synthetic rows: N(0,1) (default) or N(0,1) * 10^U(-3,3) (SURVEY 8d)")
@@ -698,12 +730,14 @@ def main():
     ap.add_argument("--alloc", choices=["contiguous", "default"], default="contiguous",
                     help="the resident rows' HBM: one physically contiguous range (flc_rows_alloc) or torch's allocator")
     ap.add_argument("--no-strong-c4", action="store_true",
-                    help="skip the strong_c4 block (C4 at fixed N=4096, ordered combine) of the default line")
+                    help="--full: skip the strong_c4 block (C4 at fixed N=4096, ordered combine) of the default line")
     ap.add_argument("--strong-steps", type=int, default=5, help="timed steps of the strong_c4 block")
     ap.add_argument("--e2e", action="store_true",
                     help="end-to-end: client rows start in pinned host memory, the [D] result lands in host memory "
                          "(H2D + encode+reduce + D2H per step; PCIe-bound; reported in DESIGN.md, never as value)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.shift:
         return shift(args)
     if args.dropin:
@@ -892,106 +926,113 @@ def main():
     if args.step_times and rank == 0:
         print(json.dumps({"step_ms": [round(evs[i].elapsed_time(evs[i + 1]), 3) for i in range(args.steps)]}),
               file=sys.stderr)
-    # The roofline's kernel times: the same K steps again with the HIP event pair around every
-    # launch of the dominant kernel (and the tail kernels), recorded on the stream each is launched
-    # on; only kernel durations are read from this pass, never the step time.
-    _lib.profile_enable(True)
-    for kname in [wl["kernel"]] + wl["others"]:
-        _lib.profile_collect(kname)             # drop anything recorded before this pass
-    for i in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    _lib.profile_enable(False)
-    kms, klaunch = _lib.profile_collect(wl["kernel"])
-    others = {}
-    for kname in wl["others"]:
-        oms, on = _lib.profile_collect(kname)
-        if on:
-            others[kname] = round(oms / on, 4)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    ceiling = read_ceiling(rows, out)
-    mg = dist_info(dist, dev, d) if world > 1 else None
-    strong_c4 = None
-    if args.workload == "c3" and not (args.no_strong_c4 or args.compat or strong or args.d):
-        # the north_star's fixed-N scaling curve (C4, N=4096) on every default line, G = 1 included:
-        # the C3 rows are released first (51.2 GB of C4 block rows + its workspace instead)
-        del rows
-        torch.cuda.synchronize()
-        torch.cuda.empty_cache()
-        from flpytorch_amd.sharding import N_BLOCKS, product_fold, product_partial
-        c4 = WORKLOADS["c4"]
-        blk = c4["n_total"] // N_BLOCKS
-        g4 = torch.Generator(device=dev).manual_seed(4096)          # the same rows on every rank
-        rows4, alloc4 = resident_rows(blk, c4["d"], device=dev, contiguous=args.alloc == "contiguous")
-        for i in range(0, blk, 64):
-            rows4[i:i + 64].normal_(generator=g4)
-        red4 = ag.UplinkReducer(ag.initCompressor(c4["spec"], c4["d"]), device=dev, seed=20241015)
-        strong_c4 = strong_block(product_partial(red4), product_fold(), rows4, c4["n_total"], c4["d"], dev,
-                                 steps=args.strong_steps, warmup=1, group=dist.group.WORLD if world > 1 else None)
-        strong_c4["rows_alloc"] = alloc4
-        del rows4
-
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed its caller in the last timed step: the [D] direction (taken
+        # here, before anything else runs on the GPU; every rank holds the same combined result)
+        dump_outputs(args.dump_outputs, {"direction": out})
     step_ms = elapsed / args.steps * 1e3
     total_bytes = algorithmic_bytes(spec, n_total, d, k) if strong else algorithmic_bytes(spec, n, d, k, specs) * world
     total_bytes += compat_bytes
     value = total_bytes / (elapsed / args.steps) / 1e9
-    # the dominant kernel may run as several launches per step (sparse QSGD: one per row group):
-    # its achieved rate is the algorithmic bytes of a step over its summed launch time per step
-    # mixed: the dominant kernel serves the qsgd group only
-    kb = kernel_bytes(wl["kernel"], len(range(specs.index("qsgd:127"), n, len(specs))) if mixed else n, d, k)
-    kb += compat_bytes                     # the dominant kernel reads the resident compat patterns
-    kavg_ms = kms / max(klaunch, 1)
-    kstep_ms = kms / args.steps
-    achieved = kb / (kstep_ms * 1e-3) / 1e9 if klaunch else None
-    launches_per_step = klaunch / args.steps if klaunch else 0
-    kb_launch = kb / launches_per_step if launches_per_step else None
-    line_floor = None
-    if wl["kernel"] in ("k_randk_fold", "k_randk_gen"):
-        # sparse 4-B gathers fetch whole 128-B lines (profiles/archive/r02/probe_gather_fetch.txt): the
-        # gather's physical floor is the expected number of distinct lines touched, x 128 B
-        nr = len(range(specs.index("randk:1%"), n, len(specs))) if mixed else n
-        line_floor = nr * (d / 32.0) * (1.0 - (1.0 - k / d) ** 32) * 128 + (4 * d if wl["kernel"] == "k_randk_fold" else 0)
-    randk_group = None
-    if mixed and "randk:1%" in specs:
-        # C5's RandK group: counts + list-free fold; algorithmic 4 N_r K + 4 D, the 128-B line floor
-        # of its gathers, and the PMC traffic of the fold (profiles/pmc_c5_randk.json)
-        nr = len(range(specs.index("randk:1%"), n, len(specs)))
-        rk_ms = sum(others.get(kk, 0.0) for kk in ("k_randk_counts", "k_randk_fold"))
-        rk_floor = nr * (d / 32.0) * (1.0 - (1.0 - k / d) ** 32) * 128 + 4 * d
-        rk_traffic = None
-        pmc_rk = os.path.join(ROOT, "profiles", "pmc_c5_randk.json")
-        if os.path.exists(pmc_rk):
-            with open(pmc_rk) as f:
-                pr = json.load(f)
-            if pr.get("n") == n and pr.get("d") == d:            # (a pass of this line's shape only)
-                rk_traffic = pr.get("hbm_bytes_per_launch")
-        if rk_ms:
-            randk_group = {"rows": nr, "ms_per_step": round(rk_ms, 4),
-                           "algorithmic_GBps": round((4 * nr * k + 4 * d) / (rk_ms * 1e-3) / 1e9, 1),
-                           "line_floor_bytes": int(rk_floor),
-                           "line_floor_GBps": round(rk_floor / (rk_ms * 1e-3) / 1e9, 1),
-                           "fold_traffic_bytes": rk_traffic}
-    traffic, traffic_src = None, None
-    pmc = os.path.join(ROOT, "profiles", f"pmc_{args.workload}{'_compat' if args.compat else ''}.json")
-    if os.path.exists(pmc) and not strong:
-        with open(pmc) as f:
-            pj = json.load(f)
-        # only a PMC pass of this line's shape: the same dominant kernel and
-        # pattern source (a compat line's filter also reads the uniforms), rows per GPU, D and
-        # launches per step — counters of another shape would price other bytes per launch
-        if (wl["kernel"] in pj.get("kernel", "") and bool(pj.get("compat")) == bool(args.compat)
-                and pj.get("n") == n and pj.get("d") == d and pj.get("launches_per_step") is not None
-                and abs(pj["launches_per_step"] - launches_per_step) < 0.01):
-            traffic = pj.get("hbm_bytes_per_launch")
-            traffic_src = {"file": os.path.relpath(pmc, ROOT), "n": pj["n"], "d": pj["d"],
-                           "launches_per_step": pj["launches_per_step"]}
+    if args.full:
+        # The roofline's kernel times: the same K steps again with the HIP event pair around every
+        # launch of the dominant kernel (and the tail kernels), recorded on the stream each is
+        # launched on; only kernel durations are read from this pass, never the step time.
+        _lib.profile_enable(True)
+        for kname in [wl["kernel"]] + wl["others"]:
+            _lib.profile_collect(kname)             # drop anything recorded before this pass
+        for i in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        _lib.profile_enable(False)
+        kms, klaunch = _lib.profile_collect(wl["kernel"])
+        others = {}
+        for kname in wl["others"]:
+            oms, on = _lib.profile_collect(kname)
+            if on:
+                others[kname] = round(oms / on, 4)
+        ceiling = read_ceiling(rows, out)
+        mg = dist_info(dist, dev, d) if world > 1 else None
+        strong_c4 = None
+        if args.workload == "c3" and not (args.no_strong_c4 or args.compat or strong or args.d):
+            # the north_star's fixed-N scaling curve (C4, N=4096) on every default --full line, G = 1
+            # included: the C3 rows are released first (51.2 GB of C4 block rows + its workspace instead)
+            del rows
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            from flpytorch_amd.sharding import N_BLOCKS, product_fold, product_partial
+            c4 = WORKLOADS["c4"]
+            blk = c4["n_total"] // N_BLOCKS
+            g4 = torch.Generator(device=dev).manual_seed(4096)          # the same rows on every rank
+            rows4, alloc4 = resident_rows(blk, c4["d"], device=dev, contiguous=args.alloc == "contiguous")
+            for i in range(0, blk, 64):
+                rows4[i:i + 64].normal_(generator=g4)
+            red4 = ag.UplinkReducer(ag.initCompressor(c4["spec"], c4["d"]), device=dev, seed=20241015)
+            strong_c4 = strong_block(product_partial(red4), product_fold(), rows4, c4["n_total"], c4["d"], dev,
+                                     steps=args.strong_steps, warmup=1, group=dist.group.WORLD if world > 1 else None)
+            strong_c4["rows_alloc"] = alloc4
+            del rows4
+
+        # the dominant kernel may run as several launches per step (sparse QSGD: one per row group):
+        # its achieved rate is the algorithmic bytes of a step over its summed launch time per step
+        # mixed: the dominant kernel serves the qsgd group only
+        kb = kernel_bytes(wl["kernel"], len(range(specs.index("qsgd:127"), n, len(specs))) if mixed else n, d, k)
+        kb += compat_bytes                     # the dominant kernel reads the resident compat patterns
+        kavg_ms = kms / max(klaunch, 1)
+        kstep_ms = kms / args.steps
+        achieved = kb / (kstep_ms * 1e-3) / 1e9 if klaunch else None
+        launches_per_step = klaunch / args.steps if klaunch else 0
+        kb_launch = kb / launches_per_step if launches_per_step else None
+        line_floor = None
+        if wl["kernel"] in ("k_randk_fold", "k_randk_gen"):
+            # sparse 4-B gathers fetch whole 128-B lines (profiles/archive/r02/probe_gather_fetch.txt):
+            # the gather's physical floor is the expected number of distinct lines touched, x 128 B
+            nr = len(range(specs.index("randk:1%"), n, len(specs))) if mixed else n
+            line_floor = nr * (d / 32.0) * (1.0 - (1.0 - k / d) ** 32) * 128 + (4 * d if wl["kernel"] == "k_randk_fold" else 0)
+        randk_group = None
+        if mixed and "randk:1%" in specs:
+            # C5's RandK group: counts + list-free fold; algorithmic 4 N_r K + 4 D, the 128-B line
+            # floor of its gathers, and the PMC traffic of the fold (profiles/pmc_c5_randk.json)
+            nr = len(range(specs.index("randk:1%"), n, len(specs)))
+            rk_ms = sum(others.get(kk, 0.0) for kk in ("k_randk_counts", "k_randk_fold"))
+            rk_floor = nr * (d / 32.0) * (1.0 - (1.0 - k / d) ** 32) * 128 + 4 * d
+            rk_traffic = None
+            pmc_rk = os.path.join(ROOT, "profiles", "pmc_c5_randk.json")
+            if os.path.exists(pmc_rk):
+                with open(pmc_rk) as f:
+                    pr = json.load(f)
+                if pr.get("n") == n and pr.get("d") == d:            # (a pass of this line's shape only)
+                    rk_traffic = pr.get("hbm_bytes_per_launch")
+            if rk_ms:
+                randk_group = {"rows": nr, "ms_per_step": round(rk_ms, 4),
+                               "algorithmic_GBps": round((4 * nr * k + 4 * d) / (rk_ms * 1e-3) / 1e9, 1),
+                               "line_floor_bytes": int(rk_floor),
+                               "line_floor_GBps": round(rk_floor / (rk_ms * 1e-3) / 1e9, 1),
+                               "fold_traffic_bytes": rk_traffic}
+        traffic, traffic_src = None, None
+        pmc = os.path.join(ROOT, "profiles", f"pmc_{args.workload}{'_compat' if args.compat else ''}.json")
+        if os.path.exists(pmc) and not strong:
+            with open(pmc) as f:
+                pj = json.load(f)
+            # only a PMC pass of this line's shape: the same dominant kernel
+            # and pattern source (a compat line's filter also reads the uniforms), rows per GPU, D
+            # and launches per step — counters of another shape would price other bytes per launch
+            if (wl["kernel"] in pj.get("kernel", "") and bool(pj.get("compat")) == bool(args.compat)
+                    and pj.get("n") == n and pj.get("d") == d and pj.get("launches_per_step") is not None
+                    and abs(pj["launches_per_step"] - launches_per_step) < 0.01):
+                traffic = pj.get("hbm_bytes_per_launch")
+                traffic_src = {"file": os.path.relpath(pmc, ROOT), "n": pj["n"], "d": pj["d"],
+                               "launches_per_step": pj["launches_per_step"]}
 
     if rank == 0:
-        cpu = None if args.no_cpu_baseline else cpu_baseline(spec, d, n_total if strong else n * world,
-                                                             budget_s=15.0 if mixed else 10.0, specs=specs)
+        cpu = None
+        if args.full and not args.no_cpu_baseline:
+            cpu = cpu_baseline(spec, d, n_total if strong else n * world, budget_s=15.0 if mixed else 10.0,
+                               specs=specs)
         line = {
             "metric": "gradient-codec encode+reduce GB/s (device-resident), [N,D] fp32; % HBM peak",
             "value": round(value, 2),
@@ -1025,36 +1066,39 @@ def main():
             # RandK also reports the dense-equivalent rate 4 N D / t (never the roofline)
             "dense_equivalent_GBps": round((4 * n * d + 4 * d) * world / (elapsed / args.steps) / 1e9, 1)
             if (spec.startswith("randk") or mixed) else None,
-            "roofline": {"bound": "hbm", "kernel": wl["kernel"],
-                         "achieved": round(achieved, 1) if achieved else None, "peak": PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / PEAK_GBS, 4) if achieved else None,
-                         # traffic: PMC HBM bytes of ONE launch (the contract's unit, like avg_launch_ms);
-                         # beside it the algorithmic bytes of one launch and their ratio, then the step's
-                         "traffic": traffic, "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/)",
-                         "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": int(kb_launch) if kb_launch else None,
-                         "traffic_over_algorithmic": round(traffic / kb_launch, 4) if (traffic and kb_launch) else None,
-                         "traffic_per_step": int(traffic * launches_per_step) if (traffic and klaunch) else None,
-                         "bytes_per_step": kb, "kernel_ms_per_step": round(kstep_ms, 4),
-                         "kernel_timing": "HIP events around every launch on its stream, in a second pass of the "
-                                          "same K steps after the timed region (the events would lengthen the step)",
-                         "avg_launch_ms": round(kavg_ms, 4), "launches": klaunch,
-                         "other_kernels_avg_ms": others,
-                         "read_ceiling_GBps": ceiling["GBps"],
-                         "frac_of_read_ceiling": round(achieved / ceiling["GBps"], 4) if achieved else None,
-                         "read_ceiling": ceiling,
-                         **({"line_floor_bytes_per_step": int(line_floor),
-                             "line_floor_GBps": round(line_floor / (kstep_ms * 1e-3) / 1e9, 1) if klaunch else None}
-                            if line_floor else {})},
-            "cpu_baseline": cpu,
-            "build_id": build_id,
         }
-        if randk_group:
-            line["randk_group"] = randk_group
-        if strong_c4:
-            line["strong_c4"] = strong_c4
-        if mg:
-            line["multi_gpu"] = mg
+        if args.full:
+            line["roofline"] = {
+                "bound": "hbm", "kernel": wl["kernel"],
+                "achieved": round(achieved, 1) if achieved else None, "peak": PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / PEAK_GBS, 4) if achieved else None,
+                # traffic: PMC HBM bytes of ONE launch (the contract's unit, like avg_launch_ms);
+                # beside it the algorithmic bytes of one launch and their ratio, then the step's
+                "traffic": traffic, "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, profiles/)",
+                "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": int(kb_launch) if kb_launch else None,
+                "traffic_over_algorithmic": round(traffic / kb_launch, 4) if (traffic and kb_launch) else None,
+                "traffic_per_step": int(traffic * launches_per_step) if (traffic and klaunch) else None,
+                "bytes_per_step": kb, "kernel_ms_per_step": round(kstep_ms, 4),
+                "kernel_timing": "HIP events around every launch on its stream, in a second pass of the "
+                                 "same K steps after the timed region (the events would lengthen the step)",
+                "avg_launch_ms": round(kavg_ms, 4), "launches": klaunch,
+                "other_kernels_avg_ms": others,
+                "read_ceiling_GBps": ceiling["GBps"],
+                "frac_of_read_ceiling": round(achieved / ceiling["GBps"], 4) if achieved else None,
+                "read_ceiling": ceiling,
+                **({"line_floor_bytes_per_step": int(line_floor),
+                    "line_floor_GBps": round(line_floor / (kstep_ms * 1e-3) / 1e9, 1) if klaunch else None}
+                   if line_floor else {})}
+            line["cpu_baseline"] = cpu
+        line["build_id"] = build_id
+        if args.full:
+            if randk_group:
+                line["randk_group"] = randk_group
+            if strong_c4:
+                line["strong_c4"] = strong_c4
+            if mg:
+                line["multi_gpu"] = mg
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

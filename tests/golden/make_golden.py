@@ -7,7 +7,8 @@ fixtures it writes are committed and travel instead).
 
 What it captures
 ----------------
-1. ``codecs.npz``   — per compressor spec / D / input distribution: the inputs, the
+1. ``codecs.part*.npz`` (tests/golden_io.py save(): one set of arrays kept in files under the
+   size limit of a committed file) — per compressor spec / D / input distribution: the inputs, the
    patterns drawn by ``Compressor.generateCompressPattern`` from a seeded
    ``np.random.RandomState`` (fl_pytorch/utils/compressors.py:196-216), the dense
    ``compressVector`` outputs (compressors.py:218-371), the wire-size stats
@@ -352,7 +353,9 @@ def main():
     import compressors  # /root/reference/fl_pytorch/utils/compressors.py
 
     a, m = codec_fixtures(compressors, torch)
-    np.savez_compressed(os.path.join(HERE, "codecs.npz"), **a)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import golden_io
+    golden_io.save("codecs", a)
     with open(os.path.join(HERE, "codecs.json"), "w") as f:
         json.dump(m, f, indent=1)
     print("codecs:", len(m), "cases")

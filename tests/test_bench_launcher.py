@@ -107,3 +107,25 @@ def test_strong_block_digest_is_g_invariant(tmp_path, world):
     assert outs[1]["clients_per_gpu"] == 32 and outs[world]["clients_per_gpu"] == 32 // world
     for b in outs.values():
         assert b["ms_per_step"] > 0 and b["value_GBps"] > 0 and b["clients_total"] == 32
+
+
+def test_dump_outputs_writes_float32_within_its_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): an array within its share of the budget is written
+    whole, a larger one as the same seeded sample every time; float32 .npy files, all of them
+    together within DUMP_BYTES."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_BYTES", 48_000)
+    small = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    big = torch.from_numpy(np.random.default_rng(1).standard_normal(50_001).astype(np.float32))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"small": small, "big": big})
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "big")}
+    assert got["small"].dtype == np.float32 and got["big"].dtype == np.float32
+    assert np.array_equal(got["small"], small.reshape(-1).numpy().astype(np.float32))
+    share = (48_000 - 2 * 4096) // 8
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, 50_001, size=share))
+    assert np.array_equal(got["big"], big.numpy()[idx])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 48_000
+    for n in got:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))

@@ -138,7 +138,7 @@ def test_bench_self_launch_two_ranks():
     """`python3 bench.py --gpus 2` without torchrun: the parent starts both ranks (gloo, both on
     cuda:0 for this rehearsal) and exactly one JSON line comes back, from rank 0, with n_gpus 2."""
     line = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--clients", "64", "--dim", "1000000",
-                   "--no-cpu-baseline"])
+                   "--full", "--no-cpu-baseline"])
     assert line["n_gpus"] == 2 and line["config"]["clients_total"] == 128
     assert line["scaling"] == "weak" and line["value"] > 0
     # the multi_gpu block (VERDICT r04 item 4): what the process group really was

@@ -7,7 +7,7 @@ out=gpurun_out/alloc_median; mkdir -p $out
 for wl in ${WLS:-c4 c3}; do
   rm -f $out/$wl.jsonl
   for i in $(seq ${RUNS:-3}); do
-    timeout -k 10 300 python bench.py --workload $wl --steps 20 --warmup 3 --no-cpu-baseline > $out/run.log 2>&1 || { tail -20 $out/run.log; exit 1; }
+    timeout -k 10 300 python bench.py --full --workload $wl --steps 20 --warmup 3 --no-cpu-baseline > $out/run.log 2>&1 || { tail -20 $out/run.log; exit 1; }
     grep '^{' $out/run.log | tail -1 >> $out/$wl.jsonl
   done
   python - $out/$wl.jsonl <<'PY'
