@@ -928,14 +928,6 @@ constexpr int GCAP = 512;             // staged entries per group (4 chunks: 3.1
 static_assert(GCAP % 64 == 0, "copy-out runs in whole wave slots");
 
 
-// A chunk is 16 wave-loads of 1 KB.  RING float4 registers per lane hold a software pipeline RING-1
-// loads deep (the next chunk's descriptor is built up front; past the last item it has
-// num_records 0 and its loads return zeros without touching memory).
-// FGS: chunks per work item (group).
-template <int RING, int FGS, int LONE = 0>
-#ifndef FLC_TK_RING
-#define FLC_TK_RING 16               // loads in flight per wave (ring registers: 4 x RING VGPRs)
-#endif
 #ifndef FLC_TK_STPOL
 #define FLC_TK_STPOL 0               // A/B: the filter's list copy-out stores nontemporal (2) or default (0)
 #endif
@@ -943,7 +935,48 @@ template <int RING, int FGS, int LONE = 0>
 #define FLC_TK_COPY4 1               // TopK filter copy-out: 16-B stores of whole quads
 #endif
 #ifndef FLC_TK_PROBE
-#define FLC_TK_PROBE 0               // A/B cost probes (outputs NOT valid): 1 no staging writes, 2 no copy-out, 3 loads only
+#define FLC_TK_PROBE 0               // A/B cost probes (outputs NOT valid): 1 no staging writes, 2 no copy-out, 3 loads only,
+                                     // 4 copy-out aimed at a small per-wave region that stays in the L2 (reservation and tab real)
+#endif
+
+// Copy-out of one 4-chunk group's staged entries (tot of them, indices at si, values at sv) to
+// position pos of row's list, as 16-B stores of 4 entries a lane (the group's whole quads) plus the
+// last partial quad's entries as 4-B stores: a FIXED sequence of 2 GCAP / 256 + 2 range-checked
+// buffer stores (none written when the group did not fit) instead of 2 GCAP / 64 exec-masked 4-B
+// stores.  The list position is any dword: the 16-B stores need only dword alignment.
+// wslot: the calling wave's number in the grid (FLC_TK_PROBE 4 only).  POL: the stores' cache policy.
+template <int POL = FLC_TK_STPOL>
+__device__ inline void tk_copy_out(const uint32_t* si, const uint32_t* sv, const SelWs& ws, int64_t n, int64_t row,
+                                   uint32_t pos, uint32_t tot, bool fits, int lane, int64_t wslot) {
+    int64_t at = row * ws.cap + pos;
+    if (FLC_TK_PROBE == 4) at = (wslot % max((n * ws.cap) >> 10, (int64_t)1)) << 10;   // 4 KB per wave and array, rewritten in place
+    const uint32_t nrec = (fits && FLC_TK_PROBE != 2) ? tot * 4u : 0u;
+    const auto di = __builtin_amdgcn_make_buffer_rsrc(ws.ent_idx + at, (short)0, (int)nrec, 0x00020000);
+    const auto dv = __builtin_amdgcn_make_buffer_rsrc(ws.ent_val + at, (short)0, (int)nrec, 0x00020000);
+    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+    const uint32_t nq = min(tot, (uint32_t)GCAP) >> 2;
+#pragma unroll
+    for (int k = 0; k < GCAP / 256; ++k) {
+        const uint32_t q = (uint32_t)(k * 64 + lane);
+        const uint4 a = reinterpret_cast<const uint4*>(si)[q];
+        const uint4 b = reinterpret_cast<const uint4*>(sv)[q];
+        const uint32_t off = q < nq ? q * 16u : 0x7FFFFFF0u;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, a), di, off, 0, POL);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, b), dv, off, 0, POL);
+    }
+    const uint32_t e = nq * 4u + (uint32_t)(lane & 3);          // the partial quad (range-checked)
+    const uint32_t off = lane < 3 ? e * 4u : 0x7FFFFFF0u;
+    __builtin_amdgcn_raw_buffer_store_b32(si[e], di, off, 0, POL);
+    __builtin_amdgcn_raw_buffer_store_b32(sv[e], dv, off, 0, POL);
+}
+
+// A chunk is 16 wave-loads of 1 KB.  RING float4 registers per lane hold a software pipeline RING-1
+// loads deep (the next chunk's descriptor is built up front; past the last item it has
+// num_records 0 and its loads return zeros without touching memory).
+// FGS: chunks per work item (group).
+template <int RING, int FGS, int LONE = 0>
+#ifndef FLC_TK_RING
+#define FLC_TK_RING 16               // loads in flight per wave (ring registers: 4 x RING VGPRs)
 #endif
 #ifndef FLC_TK_WPE
 #define FLC_TK_WPE 1                 // unconstrained (143 VGPRs); 4 waves per SIMD spilled and ran slower
@@ -1015,34 +1048,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FLC_TK_WPE)
         }
         if (!fits && lane == 0) atomicOr(&ws.flags[prow], F_OVERFLOW);
 #if FLC_TK_COPY4
-        {
-            // Copy-out as 16-B stores of 4 entries a lane (the group's whole quads) plus the last
-            // partial quad's entries as 4-B stores: a FIXED sequence of 2 GCAP / 256 + 2
-            // range-checked buffer stores (none written when the group did not fit) instead of
-            // 2 GCAP / 64 exec-masked 4-B stores — the copy-out cost the filter 0.5 ms of 6.9 per
-            // C3 step (probe, same allocation).  The list position is any dword: the 16-B
-            // stores need only dword alignment.
-            const uint32_t* si = st[pb][wv];
-            const uint32_t* sv = st[pb][wv] + SROW;
-            const uint32_t nrec = (fits && FLC_TK_PROBE != 2) ? ptot * 4u : 0u;
-            const auto di = __builtin_amdgcn_make_buffer_rsrc(ws.ent_idx + prow * ws.cap + base, (short)0, (int)nrec, 0x00020000);
-            const auto dv = __builtin_amdgcn_make_buffer_rsrc(ws.ent_val + prow * ws.cap + base, (short)0, (int)nrec, 0x00020000);
-            typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-            const uint32_t nq = ptot >> 2;
-#pragma unroll
-            for (int k = 0; k < GCAP / 256; ++k) {
-                const uint32_t q = (uint32_t)(k * 64 + lane);
-                const uint4 a = reinterpret_cast<const uint4*>(si)[q];
-                const uint4 b = reinterpret_cast<const uint4*>(sv)[q];
-                const uint32_t off = q < nq ? q * 16u : 0x7FFFFFF0u;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, a), di, off, 0, FLC_TK_STPOL);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, b), dv, off, 0, FLC_TK_STPOL);
-            }
-            const uint32_t e = nq * 4u + (uint32_t)(lane & 3);          // the partial quad (range-checked)
-            const uint32_t off = lane < 3 ? e * 4u : 0x7FFFFFF0u;
-            __builtin_amdgcn_raw_buffer_store_b32(si[e], di, off, 0, FLC_TK_STPOL);
-            __builtin_amdgcn_raw_buffer_store_b32(sv[e], dv, off, 0, FLC_TK_STPOL);
-        }
+        tk_copy_out(st[pb][wv], st[pb][wv] + SROW, ws, n, prow, base, ptot, fits, lane, (int64_t)blockIdx.x * 4 + wv);
 #else
         if (fits && FLC_TK_PROBE != 2) {
             const uint32_t* si = st[pb][wv];
@@ -1148,6 +1154,215 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FLC_TK_WPE)
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     finish(par ^ 1);
+}
+
+// ------------------------------------------------------------------------------------------
+// Many-row fast-path filter (one list per row, no zout): workgroup items.  An item is NL
+// consecutive 4-chunk groups of ONE row.  Waves 0 .. NL-1 are loaders: each streams one group of
+// the item exactly as k_topk_filter_fast does (the RING-deep nontemporal load pipeline across item
+// boundaries, ballot / mbcnt compaction into its own double-buffered staging, GCAP per group,
+// threshold max(T, 1)) and issues NO global store or atomic, so its vmcnt queue holds loads only.
+// Wave NL is the writer: it loads no rows; per item it takes the NL groups' counts from LDS, makes
+// ONE reservation on the row's counter for the groups that fit, writes the item's 4 NL tab entries
+// and the overflow flag, and copies the staged entries out as one contiguous piece per array.
+//
+// Hand-over through LDS words only, per (buffer, loader) {chunk counts lo, hi, total, filled} and
+// per buffer {freed}: a loader publishes filled = k + 1 after staging its k-th item (LDS executes a
+// wave's operations in order), the writer publishes freed = k + 1 after its last read of that
+// item's staging, and a loader refills a buffer (item k >= 2) only once freed == k - 1.
+// Progress: NO wave ever waits on another workgroup.  The writer waits only for the loaders of its
+// own workgroup to stage item k, a loader only for the writer to have drained item k - 2, and all
+// waves of a workgroup are resident together; by induction over k nothing waits for ever.
+// ------------------------------------------------------------------------------------------
+#ifndef FLC_TK_WG
+#define FLC_TK_WG 1                   // many-row TopK filter: 1 workgroup items, 0 the per-wave groups of k_topk_filter_fast
+#endif
+#ifndef FLC_TK_WG_NL
+#define FLC_TK_WG_NL 4                // loader waves (groups per item); the workgroup has one wave more (3: +0.02 ms at C3)
+#endif
+#ifndef FLC_TK_WG_RING
+#define FLC_TK_WG_RING FLC_TK_RING    // loads in flight per loader wave (8: 73 VGPRs, four workgroups per CU, the same step time,
+                                      // but the side stream's sample ran 1.19 instead of 0.14 ms beside it)
+#endif
+#ifndef FLC_TK_WG_STPOL
+#define FLC_TK_WG_STPOL 17            // the writer's copy-out stores: sc0 sc1, written through the L2 at once: C3 -0.11 .. -0.18 ms
+                                      // a step against k_topk_filter_fast, same allocation; 0 (default policy) -0.045, sc1 alone
+                                      // as 17, sc0 -0.03, nt 0, sc1 nt / sc0 sc1 nt +0.12 (profiles/r07/wgfilter/)
+#endif
+#ifndef FLC_TK_WG_WPE
+#define FLC_TK_WG_WPE 4               // 127 VGPRs: three 5-wave workgroups per CU (unconstrained: 129 VGPRs, two, +0.66 ms at C3)
+#endif
+__device__ inline uint32_t lds_addr(const void* p) {
+    return (uint32_t)(size_t)(const __attribute__((address_space(3))) void*)p;
+}
+// a word another wave of the workgroup writes: read and waited for in one statement
+__device__ inline uint32_t lds_peek(uint32_t addr) {
+    uint32_t v;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(addr) : "memory");
+    return __builtin_amdgcn_readfirstlane(v);
+}
+template <int RING, int NL>
+__global__ __launch_bounds__((NL + 1) * 64) __attribute__((amdgpu_waves_per_eu(FLC_TK_WG_WPE))) void k_topk_filter_fast_wg(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_t rb, int64_t d,
+                                                                        SelWs ws) {
+    static_assert(16 % RING == 0, "ring must divide the 16 loads of a chunk");
+    constexpr int FGS = 4;
+    constexpr int SROW = GCAP + 64;       // as k_topk_filter_fast: 64 spare slots take the wave-instruction that overflows
+    __shared__ __attribute__((aligned(16))) uint32_t st[2][NL][2 * SROW];
+    __shared__ __attribute__((aligned(16))) uint32_t hs[2][NL][4];   // chunk counts (4 x 16 bits), total, filled
+    __shared__ uint32_t fr[2];                                         // freed
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (threadIdx.x < 2 * NL * 4) (&hs[0][0][0])[threadIdx.x] = 0;
+    if (threadIdx.x < 2) fr[threadIdx.x] = 0;
+    __syncthreads();                                                   // the only barrier: before any load is issued
+    const int64_t C = nchunks(d);
+    const int64_t G = (C + FGS * NL - 1) / (FGS * NL);                  // items per row
+    const int64_t items = rn * G;
+    const int64_t stride = gridDim.x;
+    int64_t it = blockIdx.x;
+    if (it >= items) return;
+    // item order as k_topk_filter_fast: blocks of rb rows, inside a block (item, row) with the row fastest
+    auto item_at = [&](int64_t t, int64_t& r, int64_t& cc) {
+        const int64_t blk = t / (rb * G), rem = t - blk * rb * G;
+        const int64_t bn = min(rb, rn - blk * rb);
+        const int64_t g = rem / bn;
+        r = r0 + blk * rb + (rem - g * bn);
+        cc = g * (FGS * NL);
+    };
+    if (wv == NL) {
+        // ---- writer ----
+        for (uint32_t k = 0; it < items; it += stride, ++k) {
+            const int b = k & 1;
+            int64_t row, c0;
+            item_at(it, row, c0);
+            const uint32_t fa = lds_addr(&hs[b][min(lane, NL - 1)][3]);
+            for (;;) {
+                uint32_t f;
+                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(f) : "v"(fa) : "memory");
+                if (__ballot(f != k + 1) == 0) break;
+                __builtin_amdgcn_s_sleep(4);
+            }
+            uint32_t pre[NL], tot[NL], sum = 0;
+            uint64_t cc[NL];
+            bool allfit = true;
+#pragma unroll
+            for (int w = 0; w < NL; ++w) {
+                const uint4 h = *reinterpret_cast<const uint4*>(hs[b][w]);
+                cc[w] = (uint64_t)h.x | ((uint64_t)h.y << 32);
+                tot[w] = h.z;
+                pre[w] = sum;
+                sum += tot[w] <= GCAP ? tot[w] : 0u;                     // a group past GCAP contributes nothing
+                allfit = allfit && tot[w] <= GCAP;
+            }
+            uint32_t base = 0;
+            bool fits = true;                                            // the item's reservation is inside the row's list
+            if (sum) {
+                uint32_t res = 0;
+                if (lane == 0) res = atomicAdd(&ws.rowcnt[row * RCS], sum);
+                base = __shfl(res, 0, WAVE);
+                fits = (int64_t)base + sum <= ws.cap;
+            }
+            if (lane < FGS * NL && c0 + lane < C) {
+                uint32_t off = 0, cu = 0;
+                bool gf = false;
+#pragma unroll
+                for (int w = 0; w < NL; ++w)
+                    if ((lane >> 2) == w) {
+                        off = pre[w];
+                        gf = tot[w] <= GCAP;
+#pragma unroll
+                        for (int u = 0; u < FGS; ++u) {
+                            const uint32_t x = (uint32_t)(cc[w] >> (16 * u)) & 0xFFFFu;
+                            off += u < (lane & 3) ? x : 0u;
+                            cu = u == (lane & 3) ? x : cu;
+                        }
+                    }
+                ws.tab[(c0 + lane) * n + row] = make_uint2(base + off, fits && gf ? cu : 0u);
+            }
+            if (!(fits && allfit) && lane == 0) atomicOr(&ws.flags[row], F_OVERFLOW);
+#pragma unroll
+            for (int w = 0; w < NL; ++w)
+                tk_copy_out<FLC_TK_WG_STPOL>(st[b][w], st[b][w] + SROW, ws, n, row, base + pre[w], tot[w], fits && tot[w] <= GCAP, lane,
+                            (int64_t)blockIdx.x * NL + w);
+            // the staging reads above are done before the loaders may refill the buffer
+            asm volatile("s_waitcnt lgkmcnt(0)\n\tds_write_b32 %0, %1" ::"v"(lds_addr(&fr[b])), "v"(k + 1) : "memory");
+        }
+        return;
+    }
+    // ---- loaders ----
+    float4 ring[RING];
+    int64_t row, c;                                                      // current row, this wave's chunk
+    item_at(it, row, c);
+    c += wv * FGS;
+    auto rs = chunk_rsrc(rows.row_s(row), c * CHUNK, d);
+#pragma unroll
+    for (int L = 0; L < RING - 1; ++L) {
+        ring[L] = load_q(rs, lane, L);
+        __builtin_amdgcn_sched_barrier(0);   // issue in ring order: the loop's static vmcnt waits assume it
+    }
+    for (uint32_t k = 0; it < items; ++k) {
+        const int b = k & 1;
+        if (k >= 2) {
+            const uint32_t fa = lds_addr(&fr[b]);
+            while (lds_peek(fa) != k - 1) __builtin_amdgcn_s_sleep(2);
+        }
+        const uint32_t T = max(sload(ws.thr + row), 1u);                 // as k_topk_filter_fast
+        const int64_t nit = it + stride;
+        const uint32_t sla = __builtin_amdgcn_readfirstlane(lds_addr(st[b][wv]));
+        uint32_t cnt = 0;
+        uint64_t ccp = 0;
+        const int64_t cg0 = c;
+        int64_t nrow = row, nc = c;
+        // straight-line over the group; chunks past the row end (a short or empty last group) have
+        // empty descriptors and their loads return zeros
+#pragma unroll
+        for (int sub = 0; sub < FGS; ++sub, ++c) {
+            const int64_t j0 = c * CHUNK;
+            __amdgpu_buffer_rsrc_t rsn;
+            if (sub + 1 < FGS) {
+                rsn = chunk_rsrc(rows.row_s(row), j0 + CHUNK, d);
+            } else if (nit < items) {
+                item_at(nit, nrow, nc);
+                nc += wv * FGS;
+                rsn = chunk_rsrc(rows.row_s(nrow), nc * CHUNK, d);
+            } else {
+                rsn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rows.row_s(row)), (short)0, 0, 0x00020000);
+            }
+            const uint32_t cnt0 = cnt;
+            uint32_t lb = (uint32_t)j0 + (uint32_t)lane * 4u;   // row index of the lane's element 0 (opaque: see k_topk_filter_fast)
+            asm volatile("" : "+v"(lb));
+#pragma unroll
+            for (int L = 0; L < 16; ++L) {
+                const int P = L + RING - 1;
+                ring[P % RING] = P < 16 ? load_q(rs, lane, P) : load_q(rsn, lane, P - 16);
+                const float4 x = ring[L % RING];
+                const uint32_t jl = lb + (uint32_t)(L * 256);
+                const float vq[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const bool f = mag_key(vq[q]) >= T;
+                    const uint64_t m = __ballot(f);
+                    if (f) {
+                        const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+                        uint32_t sb = sla + min(cnt, (uint32_t)GCAP) * 4u;
+                        asm volatile("" : "+s"(sb));
+                        asm volatile("ds_write2st64_b32 %0, %1, %2 offset1:%3" ::"v"(sb + pre * 4u),
+                                     "v"(jl + q), "v"(__float_as_uint(vq[q])), "i"(SROW * 4 / 256) : "memory");
+                    }
+                    cnt += (uint32_t)__popcll(m);
+                }
+            }
+            ccp |= (uint64_t)min(cnt - cnt0, 0xFFFFu) << (16 * (c - cg0));
+            rs = rsn;
+        }
+        // counts, then filled: in this order behind the staging writes (one wave's LDS operations execute in order)
+        if (lane == 0)
+            asm volatile("ds_write_b64 %0, %1\n\tds_write_b32 %0, %2 offset:8\n\tds_write_b32 %0, %3 offset:12"
+                         ::"v"(lds_addr(hs[b][wv])), "v"(ccp), "v"(cnt), "v"(k + 1) : "memory");
+        it = nit;
+        row = nrow;
+        c = nc;
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3624,6 +3839,25 @@ static void launch_filter(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_
         return e ? std::max<int64_t>(1, atoll(e)) : (int64_t)64;
     }();
     ProfScope _pv(FGS == 4 ? "k_topk_filter_g4" : "k_topk_filter_g2", st);   // which variant ran (tests)
+    if constexpr (FGS == 4 && FLC_TK_WG != 0 && FLC_TK_PROBE != 1 && FLC_TK_PROBE != 3) {   // (probes 1 and 3 exist in k_topk_filter_fast only)
+        // many rows (one list per row, no zout): workgroup items; tuning builds FLC_FILTER_WG=0 keep
+        // the per-wave groups for the A/B
+        static const bool wg = [] { const char* e = tuning_env("FLC_FILTER_WG"); return !(e && atoi(e) == 0); }();
+        if (wg && shards == 1 && !zout) {
+            constexpr int NL = FLC_TK_WG_NL;
+            const int64_t items = rn * ((nchunks(d) + 4 * NL - 1) / (4 * NL));
+            const int gi = (int)std::max<int64_t>(1, std::min<int64_t>(items, 32768));
+            // rows per block of the item order: 16 and 1 measured 0.10 ms a C3 step under 64, 256 0.03 over it
+            // (each against k_topk_filter_fast in its own process, profiles/r07/wgfilter/rb.jsonl)
+            static const int64_t rbw = [] {
+                const char* e = tuning_env("FLC_TK_RB");  // tuning runs only
+                return e ? std::max<int64_t>(1, atoll(e)) : (int64_t)16;
+            }();
+            hipLaunchKernelGGL((k_topk_filter_fast_wg<FLC_TK_WG_RING, NL>), dim3(gi), dim3((NL + 1) * 64), 0, st, rows, n, r0,
+                               rn, std::min(rbw, std::max<int64_t>(rn, 1)), d, ws);
+            return;
+        }
+    }
     if (zout)
         hipLaunchKernelGGL((k_topk_filter_fast<FLC_TK_RING, FGS, 1>), dim3(gw), dim3(256), 0, st, rows, n, r0, rn,
                            std::min(rb, std::max<int64_t>(rn, 1)), d, ws, shards, zout);
