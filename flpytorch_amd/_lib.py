@@ -23,6 +23,8 @@ FLC_REDUCE_PLAIN, FLC_REDUCE_REL_X = 0, 1
 # execution hints (flc_codec_params.flags): how, never what — every choice gives the same bits
 FLC_PATH_AUTO, FLC_PATH_SPARSE, FLC_PATH_DENSE = 0, 1, 2
 FLC_TIE_LOWEST, FLC_TIE_HIGHEST = 0, 1
+# which p = 2 norm the fused dithering uplink encodes with (flc_encode_reduce_ex): a what, not a how
+FLC_NORMMODE_EXACT, FLC_NORMMODE_TORCH_CPU = 0, 1
 ABI_VERSION = 104
 
 
@@ -35,6 +37,7 @@ EXPORTS = [
     "flc_reduce_rows", "flc_reduce_matrix",
     "flc_encode_workspace_size", "flc_encode",
     "flc_encode_reduce_workspace_size", "flc_encode_reduce",
+    "flc_encode_reduce_ex_workspace_size", "flc_encode_reduce_ex",
     "flc_encode_shift_workspace_size", "flc_encode_shift",
     "flc_payload_bytes", "flc_payload_format", "flc_payload_validate", "flc_pack_workspace_size", "flc_pack", "flc_unpack",
     "flc_unpack_reduce_workspace_size", "flc_unpack_reduce",
@@ -145,6 +148,11 @@ def _bind(lib):
     lib.flc_encode_reduce_workspace_size.restype = sz
     lib.flc_encode_reduce.argtypes = [P(FlcCodecParams), P(FlcPattern), vp, i64, vp, i64, i64, vp, f32, vp, vp,
                                       vp, sz, vp]
+    if hasattr(lib, "flc_encode_reduce_ex"):        # (absent from A/B builds of older revisions)
+        lib.flc_encode_reduce_ex_workspace_size.argtypes = [P(FlcCodecParams), i64, i64, i32, i32]
+        lib.flc_encode_reduce_ex_workspace_size.restype = sz
+        lib.flc_encode_reduce_ex.argtypes = [P(FlcCodecParams), P(FlcPattern), vp, i64, vp, i64, i64, vp, f32, vp, i32,
+                                             vp, vp, vp, sz, vp]
     lib.flc_encode_shift_workspace_size.argtypes = [P(FlcCodecParams), i64]
     lib.flc_encode_shift_workspace_size.restype = sz
     lib.flc_encode_shift.argtypes = [P(FlcCodecParams), P(FlcPattern), vp, vp, i64, f32, vp, vp, f32, vp, vp, vp,
@@ -196,7 +204,7 @@ def _bind(lib):
             continue
         if name not in ("flc_version", "flc_build_id", "flc_last_error_string", "flc_device_uniform",
                         "flc_encode_workspace_size", "flc_encode_reduce_workspace_size",
-                        "flc_encode_shift_workspace_size", "flc_payload_bytes", "flc_pack_workspace_size",
+                        "flc_encode_reduce_ex_workspace_size", "flc_encode_shift_workspace_size", "flc_payload_bytes", "flc_pack_workspace_size",
                         "flc_unpack_reduce_workspace_size", "flc_combine_workspace_size",
                         "flc_combine_blocks_workspace_size", "flc_device_randk_counts_workspace_size",
                         "flc_norm2_torch_cpu_workspace_size"):

@@ -141,13 +141,16 @@ class Compressor:
         #   row_groups   None | g                   (folds pipelined under the next group's pass)
         self.dither_path = None
         self.row_groups = None
-        # what (not how): the p = 2 norm of standard dithering / QSGD in compressVector —
+        # what (not how): the p = 2 norm of standard dithering / QSGD in compressVector and in the
+        # fused uplink (UplinkReducer: flc_encode_reduce_ex's norm_mode) —
         #   "exact"      the correctly rounded norm (default; deterministic on every host)
         #   "torch_cpu"  the reference's own fp32 value, torch.norm(x, p=2) on a CPU tensor
         #                (compressors.py:272 / 303: standard and natural dithering) in torch's CPU
         #                reduction order, bit for bit on x86 hosts with AVX2 (torch's 8-lane AVX2
         #                norm kernel, which AVX512 hosts run too; without AVX2: unpinned)
-        #                (flc_norm2_torch_cpu; latency-bound: see bench.py --dropin --norm-mode)
+        #                (flc_norm2_torch_cpu; latency-bound: see bench.py --dropin --norm-mode;
+        #                fused: one more pass over the rows that composes the binade maps,
+        #                tools/probe_uplink_norm.py prices it)
         self.norm_mode = "exact"
         # what: TopK's choice among entries tied at the K-th magnitude when fewer places are left
         # than ties (compressors.py:332 leaves it to torch.topk) — "lowest" indices (default: the

@@ -64,9 +64,16 @@ class UplinkReducer:
             prm.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
         return prm, keep
 
-    def workspace_bytes(self, n, d):
+    def norm_mode(self):
+        """flc_encode_reduce_ex's norm_mode for this compressor: FLC_NORMMODE_TORCH_CPU when its
+        ``norm_mode`` is "torch_cpu" and it is a p = 2 dithering codec (p = inf: the maximum, exact
+        in any order; p = 1: NotImplementedError), else FLC_NORMMODE_EXACT."""
+        return _lib.FLC_NORMMODE_TORCH_CPU if self.comp._torch_norm() else _lib.FLC_NORMMODE_EXACT
+
+    def workspace_bytes(self, n, d, pnorms_in=False):
         prm, _ = self.params()
-        return _lib.load().flc_encode_reduce_workspace_size(ctypes.byref(prm), n, d)
+        mode = _lib.FLC_NORMMODE_EXACT if pnorms_in else self.norm_mode()
+        return _lib.load().flc_encode_reduce_ex_workspace_size(ctypes.byref(prm), n, d, 1 if pnorms_in else 0, mode)
 
     def randk_counts(self, n, d, client0=0, out=None):
         """The device sampler's chunk counts [ceil(d / 4096), n] (uint32 as int32) of clients
@@ -90,29 +97,34 @@ class UplinkReducer:
         return out
 
     def __call__(self, rows, out=None, weights=None, client0=0, randk_idx=None, uniforms=None, lazy_u=None,
-                 pnorms_out=None, stream=None, divisor=None, randk_counts=None):
+                 pnorms_out=None, stream=None, divisor=None, randk_counts=None, pnorms_in=None):
         """rows: [N, D] fp32 device tensor (row stride % 4 == 0 for the vector path) or a list of
         [D] device tensors.  Compat patterns: randk_idx [N, K] int64, uniforms [N, D] float64,
         lazy_u [N] float64 (device).  Without them (and with ``seed`` set) draws are on device.
         ``divisor`` overrides the fp32 divisor sum(w) (e.g. 1.0 for a partial sum across GPUs).
         ``stream``: every allocation, copy and the launch go to that stream (torch's stream
         semantics: the caller orders it after the producers of ``rows`` and the patterns).
-        ``randk_counts``: RandK device mode, the chunk counts from ``randk_counts(n, d, client0)``."""
+        ``randk_counts``: RandK device mode, the chunk counts from ``randk_counts(n, d, client0)``.
+        ``pnorms_in``: dithering codecs, an [N] fp32 device tensor of the rows' norms to encode with
+        instead of computing any (the norms a server received on the wire); it takes the place of
+        the compressor's ``norm_mode``.  ``pnorms_out`` reports the norms used in every mode: with
+        ``norm_mode = "torch_cpu"`` (p = 2) the reference's own torch.norm bits."""
         if stream is not None:
             if stream.device != self.device:
                 raise ValueError(f"stream is on {stream.device}, the reducer runs on {self.device}")
             with torch.cuda.stream(stream):
                 return self._run(rows, out, weights, client0, randk_idx, uniforms, lazy_u, pnorms_out, divisor,
-                                 randk_counts)
-        return self._run(rows, out, weights, client0, randk_idx, uniforms, lazy_u, pnorms_out, divisor, randk_counts)
+                                 randk_counts, pnorms_in)
+        return self._run(rows, out, weights, client0, randk_idx, uniforms, lazy_u, pnorms_out, divisor, randk_counts,
+                         pnorms_in)
 
-    def _run(self, rows, out, weights, client0, randk_idx, uniforms, lazy_u, pnorms_out, divisor, randk_counts=None):
+    def _run(self, rows, out, weights, client0, randk_idx, uniforms, lazy_u, pnorms_out, divisor, randk_counts=None,
+             pnorms_in=None):
         """The call on the current stream (allocations, uploads and the launch all on it)."""
         lib = _lib.load()
         dev = self.device
-        if self.comp._torch_norm():
-            raise NotImplementedError("UplinkReducer folds with exactly rounded norms; norm_mode='torch_cpu' "
-                                      "(the reference's CPU norm bits) is served by compressVector")
+        # which norm the dithering codecs encode with: the caller's, torch's CPU order, or the exact one
+        mode = _lib.FLC_NORMMODE_EXACT if pnorms_in is not None else self.norm_mode()
         prm, keep = self.params()
         pat = _lib.FlcPattern()
         pat.client0 = int(client0)
@@ -167,15 +179,36 @@ class UplinkReducer:
             w_ptr = wt.data_ptr()
         if divisor is not None:
             total = float(divisor)
-        ws_bytes = lib.flc_encode_reduce_workspace_size(ctypes.byref(prm), n, d)
-        ws = _lib.WORKSPACE.get(dev, ws_bytes)
+        pin_ptr = None
+        if pnorms_in is not None:
+            if (not torch.is_tensor(pnorms_in) or pnorms_in.dtype != torch.float32 or pnorms_in.device != dev
+                    or pnorms_in.numel() != n):
+                raise ValueError(f"pnorms_in must be an [N] fp32 tensor on {dev}")
+            pnorms_in = pnorms_in.reshape(-1).contiguous()
+            keep.append(pnorms_in)
+            pin_ptr = pnorms_in.data_ptr()
         st = _lib.stream_ptr(dev)
+        if not hasattr(lib, "flc_encode_reduce_ex"):
+            # an A/B build of an older revision (tools/ab_inproc.py): the same call without the selectors
+            if pin_ptr or mode != _lib.FLC_NORMMODE_EXACT:
+                raise NotImplementedError("this library build has no flc_encode_reduce_ex (pnorms_in / norm_mode)")
+            ws = _lib.WORKSPACE.get(dev, lib.flc_encode_reduce_workspace_size(ctypes.byref(prm), n, d))
+            with torch.cuda.device(dev):
+                rc = lib.flc_encode_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.c_void_p(base), ld,
+                                           ctypes.c_void_p(ptrs), n, d, ctypes.c_void_p(w_ptr), ctypes.c_float(total),
+                                           ctypes.c_void_p(pnorms_out.data_ptr() if pnorms_out is not None else None),
+                                           ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), st)
+            _lib.check(rc, "flc_encode_reduce")
+            return out
+        ws_bytes = lib.flc_encode_reduce_ex_workspace_size(ctypes.byref(prm), n, d, 1 if pin_ptr else 0, mode)
+        ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):
-            rc = lib.flc_encode_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.c_void_p(base), ld,
-                                       ctypes.c_void_p(ptrs), n, d, ctypes.c_void_p(w_ptr), ctypes.c_float(total),
-                                       ctypes.c_void_p(pnorms_out.data_ptr() if pnorms_out is not None else None),
-                                       ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), st)
-        _lib.check(rc, "flc_encode_reduce")
+            rc = lib.flc_encode_reduce_ex(ctypes.byref(prm), ctypes.byref(pat), ctypes.c_void_p(base), ld,
+                                          ctypes.c_void_p(ptrs), n, d, ctypes.c_void_p(w_ptr), ctypes.c_float(total),
+                                          ctypes.c_void_p(pin_ptr), mode,
+                                          ctypes.c_void_p(pnorms_out.data_ptr() if pnorms_out is not None else None),
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), st)
+        _lib.check(rc, "flc_encode_reduce_ex")
         return out
 
 

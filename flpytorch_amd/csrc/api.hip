@@ -193,11 +193,16 @@ extern "C" size_t flc_encode_workspace_size(const flc_codec_params* prm, int64_t
     return ew_workspace(prm, 1, d);
 }
 
-extern "C" size_t flc_encode_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+extern "C" size_t flc_encode_reduce_ex_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d, int norms_given,
+                                                      int norm_mode) {
     if (!prm || !known(prm->codec)) return 0;
     if (is_sel(prm->codec)) return sel_workspace(prm, n, d);
     if (prm->codec == FLC_RANK_K) return rk_workspace(prm, n, d, true);
-    return ew_workspace(prm, n, d);
+    return ew_workspace(prm, n, d, norms_given != 0, norm_mode);
+}
+
+extern "C" size_t flc_encode_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    return flc_encode_reduce_ex_workspace_size(prm, n, d, 0, FLC_NORMMODE_EXACT);
 }
 
 namespace flc {
@@ -310,11 +315,33 @@ extern "C" int flc_unpack_reduce(const flc_codec_params* prm, const void* d_payl
                              w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
-extern "C" int flc_encode_reduce(const flc_codec_params* prm, const flc_pattern* pat, const float* d_rows, int64_t ld,
-                                 const float* const* d_row_ptrs, int64_t n, int64_t d, const float* d_w, float w_total,
-                                 float* d_pnorms_out, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+namespace flc {
+// the torch-order mode restates p = 2 of the dithering codecs; p = inf: a maximum, exact in any order
+static bool dithering(int codec) { return codec == FLC_STD_DITHERING || codec == FLC_NAT_DITHERING; }
+}  // namespace flc
+
+extern "C" int flc_encode_reduce_ex(const flc_codec_params* prm, const flc_pattern* pat, const float* d_rows, int64_t ld,
+                                    const float* const* d_row_ptrs, int64_t n, int64_t d, const float* d_w, float w_total,
+                                    const float* d_pnorms_in, int norm_mode, float* d_pnorms_out, float* d_out, void* d_ws,
+                                    size_t ws_bytes, void* stream) {
     if (!prm || !known(prm->codec)) { set_error("flc_encode_reduce: unknown codec"); return FLC_ERR_UNSUPPORTED; }
     if (int rc = bad_params(prm, "flc_encode_reduce")) return rc;
+    if (norm_mode != FLC_NORMMODE_EXACT && norm_mode != FLC_NORMMODE_TORCH_CPU) {
+        set_error("flc_encode_reduce_ex: unknown norm_mode %d", norm_mode);
+        return FLC_ERR_ARG;
+    }
+    if (d_pnorms_in && norm_mode != FLC_NORMMODE_EXACT) {
+        set_error("flc_encode_reduce_ex: d_pnorms_in and a norm_mode are two sources for one norm");
+        return FLC_ERR_ARG;
+    }
+    if (!dithering(prm->codec)) { d_pnorms_in = nullptr; norm_mode = FLC_NORMMODE_EXACT; }
+    if (norm_mode == FLC_NORMMODE_TORCH_CPU) {
+        if (prm->norm == FLC_NORM_L1) {
+            set_error("flc_encode_reduce_ex: FLC_NORMMODE_TORCH_CPU restates torch's p = 2 reduction only (p = 1 asked)");
+            return FLC_ERR_UNSUPPORTED;
+        }
+        if (prm->norm != FLC_NORM_L2) norm_mode = FLC_NORMMODE_EXACT;
+    }
     if (n < 0 || d < 0 || (d > 0 && !d_out)) { set_error("flc_encode_reduce: bad n/d/out"); return FLC_ERR_ARG; }
     if (n > FLC_MAX_ROWS) {   // per-row kernels index rows by blockIdx.y
         set_error("flc_encode_reduce: n=%lld rows, at most %d per call (fold larger rounds as partials)", (long long)n,
@@ -344,7 +371,15 @@ extern "C" int flc_encode_reduce(const flc_codec_params* prm, const flc_pattern*
         return sel_run(prm, pat, r, vec, n, d, false, d_w, w_total, d_out, d_ws, ws_bytes, st);
     }
     RowSrc s{d_rows, ld, d_row_ptrs};
-    return ew_run(prm, pat, s, vec, n, d, nullptr, d_pnorms_out, false, d_out, d_w, w_total, d_ws, ws_bytes, st);
+    return ew_run(prm, pat, s, vec, n, d, d_pnorms_in, d_pnorms_out, false, d_out, d_w, w_total, d_ws, ws_bytes, st, nullptr,
+                  nullptr, norm_mode);
+}
+
+extern "C" int flc_encode_reduce(const flc_codec_params* prm, const flc_pattern* pat, const float* d_rows, int64_t ld,
+                                 const float* const* d_row_ptrs, int64_t n, int64_t d, const float* d_w, float w_total,
+                                 float* d_pnorms_out, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    return flc_encode_reduce_ex(prm, pat, d_rows, ld, d_row_ptrs, n, d, d_w, w_total, nullptr, FLC_NORMMODE_EXACT, d_pnorms_out,
+                                d_out, d_ws, ws_bytes, stream);
 }
 
 extern "C" size_t flc_device_randk_counts_workspace_size(int64_t n, int64_t d) {

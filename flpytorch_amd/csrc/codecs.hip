@@ -667,12 +667,22 @@ static EwWs carve_ew(void* base, int64_t n, int64_t d, size_t* bytes) {
 // the caller forced the sparse dithering path (flc_codec_params.flags hint)
 static bool lone_sparse(const flc_codec_params* prm) { return (prm->flags & FLC_PATH_MASK) == FLC_PATH_SPARSE; }
 
-size_t ew_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
+// the torch-order norm mode applies: p = 2 of a dithering codec (p = inf: a maximum, the exact one)
+static bool torch_norm_mode(const flc_codec_params* prm, int norm_mode) {
+    return norm_mode == FLC_NORMMODE_TORCH_CPU && prm->norm == FLC_NORM_L2 &&
+           (prm->codec == FLC_STD_DITHERING || prm->codec == FLC_NAT_DITHERING);
+}
+
+size_t ew_workspace(const flc_codec_params* prm, int64_t n, int64_t d, bool norms_given, int norm_mode) {
     if (prm->codec == FLC_IDENT || prm->codec == FLC_LAZY) return 0;
+    (void)norms_given;                      // given norms take the computed ones' places
+    const bool tn = torch_norm_mode(prm, norm_mode);
     size_t b = 0;
     carve_ew(nullptr, n, d, &b);
+    if (tn) b += norm_torch_ws_bytes(n, d);  // dense path: the maps and sums behind the row tables
     // fused dithering may take the sparse path (device draws; the pattern is not known here)
-    if ((n > 1 || lone_sparse(prm)) && ds_eligible(prm, nullptr, n, d)) b = std::max(b, ds_workspace(prm, n, d));
+    if ((n > 1 || lone_sparse(prm)) && ds_eligible(prm, nullptr, n, d))
+        b = std::max(b, ds_workspace(prm, n, d, tn ? FLC_NORMMODE_TORCH_CPU : FLC_NORMMODE_EXACT));
     return b;
 }
 
@@ -731,7 +741,7 @@ static int launch_lone_dither(const flc_codec_params* prm, const UniformSrc& us,
 // One row encode (compressVector) or fused reduce over n rows (n >= 1).
 int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool vec, int64_t n, int64_t d,
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt,
-           void* ws, size_t ws_bytes, hipStream_t st, const ShiftArgs* sh, const CodeArgs* ca) {
+           void* ws, size_t ws_bytes, hipStream_t st, const ShiftArgs* sh, const CodeArgs* ca, int norm_mode) {
     if ((sh || ca) && (!dense || n != 1)) { set_error("ew_run: the shift / code forms are one dense row"); return FLC_ERR_ARG; }
     const int codec = prm->codec;
     const bool compat = pat && pat->d_uniforms;
@@ -743,16 +753,21 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
         if (dense) return launch_dense(src.base, d, op, levels, s, out, st);
         return launch_accum(src, vec, n, d, op, levels, s, w, wt, out, st);
     };
-    if (!dense && !pnorm_in && n > 1 && ds_eligible(prm, pat, n, d))
-        return ds_run(prm, pat, src, n, d, w, wt, pnorm_out, out, ws, ws_bytes, st);
+    const bool tn = torch_norm_mode(prm, norm_mode);
+    // (given norms and the torch-order mode included: a row whose norm is outside its sampled
+    // bounds is folded dense there)
+    if (!dense && n > 1 && ds_eligible(prm, pat, n, d))
+        return ds_run(prm, pat, src, n, d, w, wt, pnorm_out, out, ws, ws_bytes, st, pnorm_in,
+                      tn ? FLC_NORMMODE_TORCH_CPU : FLC_NORMMODE_EXACT);
     // a lone compressVector row on the single-read sparse pass, when the caller forces it (the fold
     // of one row with weight 1 is the row's encode, -0 included: (1 * v) / 1 == v).  Not the
     // automatic choice: at D = 25 M the two-pass dense encode is 2.2 x faster (62 vs 218 us, device
     // draws; the one-row fold walks every tile of the row), profiles/r04/lone_ab.txt
     if (lone_sparse(prm) && dense && !sh && !ca && !pnorm_in && n == 1 && ds_eligible(prm, pat, 1, d))
         return ds_run(prm, pat, src, 1, d, nullptr, 1.f, pnorm_out, out, ws, ws_bytes, st);
-    if (ws_bytes < ew_workspace(prm, n, d)) { set_error("codec workspace too small"); return FLC_ERR_WORKSPACE; }
-    EwWs e = carve_ew(ws, n, d, nullptr);
+    if (ws_bytes < ew_workspace(prm, n, d, pnorm_in != nullptr, norm_mode)) { set_error("codec workspace too small"); return FLC_ERR_WORKSPACE; }
+    size_t ew_bytes = 0;
+    EwWs e = carve_ew(ws, n, d, &ew_bytes);
     switch (codec) {
         case FLC_IDENT: {
             IdentOp op;
@@ -778,6 +793,12 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
         case FLC_NAT_DITHERING: {
             int rc = check_dither(prm);
             if (rc) return rc;
+            if (tn && !pnorm_in) {
+                // the rows' norms in torch's CPU order (torch_norm.hip), then the encode as with given norms
+                rc = tn_run(src, n, 0, n, d, e.pn, static_cast<char*>(ws) + ew_bytes, nullptr, 0, st);
+                if (rc) return rc;
+                pnorm_in = e.pn;
+            }
             if (FLC_LONE_DITHER && codec == FLC_STD_DITHERING && dense && !sh && !ca && n == 1 && !pnorm_in &&
                 ((((uintptr_t)src.base | (uintptr_t)out) & 15u) == 0) && (!compat || ((uintptr_t)us.u & 15u) == 0))
                 return launch_lone_dither(prm, us, compat, src.base, d, e, pnorm_out, out, client0, st);

@@ -114,7 +114,9 @@ struct RowSrc {
 // Internal entry points of the codec families (reduce.hip, codecs.hip, select.hip).
 int reduce_impl(RowSrc src, bool rows_vec_ok, int64_t n, int64_t d, const float* x, const float* w, float wt,
                 int mode, float* out, hipStream_t st);
-size_t ew_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
+// norms_given / norm_mode: flc_encode_reduce_ex's selectors (0, FLC_NORMMODE_EXACT: flc_encode_reduce)
+size_t ew_workspace(const flc_codec_params* prm, int64_t n, int64_t d, bool norms_given = false,
+                    int norm_mode = FLC_NORMMODE_EXACT);
 // The shift codecs' epilogue (flc_encode_shift): b is subtracted from the input row before the
 // codec; msg = base + C * scale, hout = hin + alpha * C (null msg / hout: not written).
 struct ShiftArgs {
@@ -136,7 +138,8 @@ struct CodeArgs {
 };
 int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool vec, int64_t n, int64_t d,
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt, void* ws,
-           size_t ws_bytes, hipStream_t st, const ShiftArgs* sh = nullptr, const CodeArgs* ca = nullptr);
+           size_t ws_bytes, hipStream_t st, const ShiftArgs* sh = nullptr, const CodeArgs* ca = nullptr,
+           int norm_mode = FLC_NORMMODE_EXACT);
 size_t shift_workspace(const flc_codec_params* prm, int64_t d);
 int encode_row(const flc_codec_params* prm, const flc_pattern* pat, const float* d_x, int64_t d,
                const float* d_pnorm_in, float* d_pnorm_out, float* d_out, void* d_ws, size_t ws_bytes, hipStream_t st);
@@ -181,6 +184,8 @@ int norm_torch_run(const float* x, int64_t ld, int64_t n, int64_t d, float* out,
 size_t norm_torch_ws_bytes(int64_t n, int64_t d);
 int norm_torch_ws_run(const float* x, int64_t ld, int64_t n, int64_t d, float* out, void* wsp, size_t ws_bytes,
                       hipStream_t st);
+int tn_run(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_t d, float* out, void* wsp, const double* item_sums,
+           int64_t G, hipStream_t st);
 size_t sel_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 int sel_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bool vec, int64_t n, int64_t d,
             bool assign, const float* w, float wt, float* out, void* wsp, size_t ws_bytes, hipStream_t st);
@@ -188,9 +193,10 @@ int rs_debug(int mult, int64_t spin_ticks);
 int sel_row_flags(const flc_codec_params* prm, int64_t n, int64_t d, const void* wsp, size_t ws_bytes,
                   uint32_t* flags, hipStream_t st);
 bool ds_eligible(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d);
-size_t ds_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
+size_t ds_workspace(const flc_codec_params* prm, int64_t n, int64_t d, int norm_mode = FLC_NORMMODE_EXACT);
 int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d, const float* w,
-           float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes, hipStream_t st);
+           float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes, hipStream_t st,
+           const float* pnorm_in = nullptr, int norm_mode = FLC_NORMMODE_EXACT);
 size_t rk_workspace(const flc_codec_params* prm, int64_t n, int64_t d, bool reduce);
 int rk_run(const flc_codec_params* prm, RowSrc rows, int64_t n, int64_t d, bool reduce, const float* w, float wt,
            float* out, void* wsp, size_t ws_bytes, hipStream_t st);

@@ -45,6 +45,22 @@
 // so hi8 = h >> 24 > 255 - 256 |x| (1 + 2^-24) / (l1 n_lo) - 2^-15, and |x| qc + hi8 > 255 - 2^-15;
 // the fp32 fma loses < 2^-14 there, so > 254.98 keeps every nonzero.  Elements in higher
 // intervals (y >= l1) have |x| qc >= 256.
+//
+// Norms from elsewhere.  The argument above holds for ANY norm n in [n_lo, n_hi], whoever computed
+// it, so the row's norm may also be GIVEN by the caller (the norm a server received) or be the
+// reference's own fp32 value (FLC_NORMMODE_TORCH_CPU: torch.norm(x, 2) in torch's CPU reduction
+// order, torch_norm.hip): k_ds_final then takes it from an array instead of sqrt(sum of partials)
+// and checks it against the same bounds; a row whose norm lies outside is folded dense with that
+// norm, like any other.  Such a norm is not the exactly rounded one, so for rows sampled whole
+// (d <= DS_SMAX), whose bounds are otherwise norm (1 -+ 2^-20), these two modes give the bounds
+// the sampled case's relative margin (FLC_DS_MARGIN on the sum of squares): the fp32 chain's norm
+// is a few 1e-4 away at most there.  The wider band changes no result — the classification is
+// exact for every norm inside the bounds — it only makes more candidates ambiguous (resolved with
+// the norm) instead of sure.
+// In the torch-order mode the filter also emits, per item, the float64 sum of squares PER TORCH
+// LANE (an item is 1024 steps of each of torch's 8 accumulator lanes: one block of torch_norm.hip),
+// which replace k_tn_sums' extra read of the rows; they are a prediction only — k_tn_walk checks
+// every map against the real accumulator — so they cannot change a bit of the norm.
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -135,6 +151,7 @@ struct DsWs {
     int64_t cap;          // per row: G * GCAP (each filter item owns a fixed region)
     int64_t G;            // filter items per row
     int64_t n;            // rows
+    double* tsum;         // [N][G][8] torch-order mode: the item's sums of squares per torch lane
 };
 
 constexpr int HCHUNK = CHUNK / 2;          // the fold's tile: 2048 elements (8 KB of LDS per wave)
@@ -149,7 +166,7 @@ __device__ inline float f32_down(double v) { float f = (float)v; return (double)
 // Sample: one workgroup per row.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(DS_SNT) void k_ds_sample(RowSrc rows, int64_t n, int64_t d, const float* __restrict__ levels,
-                                                      int s, uint64_t seed, int64_t client0, DsWs ws, int64_t r_off) {
+                                                      int s, uint64_t seed, int64_t client0, DsWs ws, int64_t r_off, int wide) {
     constexpr int NW = DS_SNT / 64;
     __shared__ double r2[NW], r4[NW];
     const int64_t row = r_off + blockIdx.x;                               // (a launch may take a row range)
@@ -195,7 +212,10 @@ __global__ __launch_bounds__(DS_SNT) void k_ds_sample(RowSrc rows, int64_t n, in
         const float l0 = levels[0], l1 = levels[1];
         const bool bad = !(l0 == 0.f) || !(l1 > 0.f);   // the bounds need levels 0 < l1 < ...
         double nlo, nhi = __builtin_huge_val();
-        if (S == d) {
+        if (S == d && wide) {
+            nlo = sqrt(a2 * (1.0 - FLC_DS_MARGIN));        // the whole row, the norm not the exactly
+            nhi = sqrt(a2 * (1.0 + FLC_DS_MARGIN));        // rounded one (given / torch's order)
+        } else if (S == d) {
             nlo = sqrt(a2) * (1.0 - 0x1p-20);              // the whole row: the norm itself
             nhi = sqrt(a2) * (1.0 + 0x1p-20);
         } else {
@@ -276,12 +296,19 @@ __device__ inline __amdgpu_buffer_rsrc_t chunk_ursrc(const double* u, int64_t j0
 #ifndef FLC_DS_WPEC
 #define FLC_DS_WPEC 5                // compat: 5 (LDS: 32 KB of staging per block)
 #endif
-template <int RING, int GCAP, int PROBE = 0, bool COMPAT = false>
+//
+// TNS (the torch-order norm mode): instead of the item's one sum of squares (the partial of the
+// exact norm, not needed there) the float64 sums PER TORCH LANE go to tsum[row][item][8] — element
+// j of a row belongs to lane j % 8, i.e. lane 4 (t & 1) + q for thread t's q-th element of a
+// device-RNG step (4 t + 256 L + q) and 2 (t & 3) + (q & 1) for the compat filter's.
+template <int RING, int GCAP, int PROBE = 0, bool COMPAT = false, bool TNS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FLC_DS_WPEC : FLC_DS_WPE))) void k_ds_filter(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_t rb, int64_t d, DsWs ws, UniformSrc us) {
     constexpr int FGS = DS_FGS, NH = DS_NH;
     static_assert(16 % RING == 0, "ring must divide the 16 loads of a chunk");
     static_assert(GCAP % 512 == 0 && (GCAP & (GCAP - 1)) == 0, "copy-out in whole 16-B wave slots; wrap mask");
     static_assert(!COMPAT || PROBE == 0, "probes: device-RNG filter only");
+    static_assert(!TNS || PROBE == 0, "probes: the exact-norm filter only");
+    constexpr int NTA = TNS ? (COMPAT ? 2 : 4) : 1;        // TNS: a thread's torch lanes
     constexpr int DS_ITEM_STORES = 4 + GCAP / 128;   // partial, itm, tab, sure and ambiguous copy-outs
     // (entry word, x bits); 64 slots past GCAP take the writes of a wave-instruction that starts
     // at GCAP (its item has overflowed)
@@ -347,6 +374,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
         uint32_t cnt = 0;
         uint32_t lcnt = 0;                                   // PL: this lane's candidates in the item
         double a2 = 0.0;
+        double ta[NTA];                                      // TNS: sums of squares per torch lane
+#pragma unroll
+        for (int u = 0; u < NTA; ++u) ta[u] = 0.0;
         int64_t nrow = row, nc = c;
 #pragma unroll
         for (int sub = 0; sub < FGS; ++sub, ++c) {
@@ -378,7 +408,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
                         const double uq[4] = {sl.ua.x, sl.ua.y, sl.ub.x, sl.ub.y};
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            a2 = fma((double)vq[q], (double)vq[q], a2);
+                            if constexpr (TNS) ta[q & 1] = fma((double)vq[q], (double)vq[q], ta[q & 1]);
+                            else a2 = fma((double)vq[q], (double)vq[q], a2);
                             const float hf = (float)uq[q];                 // RN(u): |hf - u| <= 2^-25
                             const bool f = fmaf(fabsf(vq[q]), qc, hf * 256.f) > DS_QT;
                             const uint64_t m = __ballot(f);
@@ -391,7 +422,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
                             }
                             cnt += (uint32_t)__popcll(m);
                         }
-                        asm volatile("" : "+v"(a2));
+                        if constexpr (TNS) {
+#pragma unroll
+                            for (int u = 0; u < NTA; ++u) asm volatile("" : "+v"(ta[u]));
+                        } else {
+                            asm volatile("" : "+v"(a2));
+                        }
                     }
                 } else {
                 // item-local index of (L, q): 4096 sub + 4 lane + 256 L + q (opaque: keeps the 64
@@ -411,6 +447,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         if (PROBE == 1) a2 = (double)fmaf(vq[q], vq[q], (float)a2);
+                        else if constexpr (TNS) ta[q] = fma((double)vq[q], (double)vq[q], ta[q]);
                         else a2 = fma((double)vq[q], (double)vq[q], a2);
                         if (PROBE == 3) continue;
                         const float hi = (float)((hg >> (8 * q)) & 0xFFu);
@@ -464,13 +501,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
                     }
                     // keep the norm's fma chain here: left alone, the compiler sinks all 128 of an
                     // item's fmas to its end and holds the 128 x values live (218 VGPRs)
-                    asm volatile("" : "+v"(a2));
+                    if constexpr (TNS) {
+#pragma unroll
+                        for (int u = 0; u < NTA; ++u) asm volatile("" : "+v"(ta[u]));
+                    } else {
+                        asm volatile("" : "+v"(a2));
+                    }
                 }
             }
             rs = rsn;
             ru = run;
         }
-        a2 = wave_sum(a2);                                   // fixed butterfly: deterministic
+        if constexpr (TNS) {
+            // threads of one torch-lane set (t & 1 / t & 3) summed by the butterfly's upper steps;
+            // then wave lane l & 7 takes torch lane l & 7 from a thread that holds it
+            constexpr int SETS = COMPAT ? 4 : 2;
+            const int l7 = lane & 7;
+            double tv = 0.0;
+#pragma unroll
+            for (int u = 0; u < NTA; ++u) {
+                double v = ta[u];
+#pragma unroll
+                for (int o = 32; o >= SETS; o >>= 1) v += __shfl_xor(v, o, WAVE);
+                v = __shfl(v, l7 / NTA, WAVE);
+                tv = (l7 % NTA) == u ? v : tv;
+            }
+            a2 = tv;
+        } else {
+            a2 = wave_sum(a2);                               // fixed butterfly: deterministic
+        }
         if constexpr (PL) {
             // Compaction in place: slot row k of every lane with more than k candidates, in row
             // order, lanes in order within a row.  An entry's new position never exceeds its slot
@@ -602,7 +661,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
         // in-order vmcnt queue in front of the loads issued after them; with one fixed sequence on
         // every path (the prologue issues the same count of dropped stores) the compiler's static
         // vmcnt waits count them exactly instead of draining part of the ring.
-        ws.partial[row * G + gi] = a2;
+        if constexpr (TNS) ws.tsum[(row * G + gi) * 8 + (lane & 7)] = a2;   // (8 lanes' values, each 8 times)
+        else ws.partial[row * G + gi] = a2;
         ws.itm[gi * n + row] = ovf ? DS_OVF : na;
         {
             const uint32_t u = (uint32_t)lane & (NH - 1);
@@ -891,8 +951,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FLC_DS2_WPE
 // ------------------------------------------------------------------------------------------
 // Norm and row mode: one wave per row.
 // ------------------------------------------------------------------------------------------
+// GIVEN: the row's norm comes from `given` (the caller's norms, or k_tn_walk's in the torch-order
+// mode) instead of the filter's partials; everything else — the bounds, overflow and weight checks
+// that send a row to the dense fold, DS_FAST, rpn, pnorm_out — is the same.
+template <bool GIVEN>
 __global__ __launch_bounds__(256) void k_ds_final(int64_t r0, int64_t rn, DsWs ws, const float* __restrict__ w,
-                                                  float* __restrict__ pnorm_out) {
+                                                  float* __restrict__ pnorm_out, const float* given) {
     const int lane = threadIdx.x & 63;
     const int64_t row = r0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= r0 + rn) return;
@@ -903,15 +967,15 @@ __global__ __launch_bounds__(256) void k_ds_final(int64_t r0, int64_t rn, DsWs w
         double v[8];
         uint32_t t[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { v[u] = ws.partial[row * ws.G + k + u * 64]; t[u] = ws.itm[(k + u * 64) * ws.n + row]; }
+        for (int u = 0; u < 8; ++u) { v[u] = GIVEN ? 0.0 : ws.partial[row * ws.G + k + u * 64]; t[u] = ws.itm[(k + u * 64) * ws.n + row]; }
 #pragma unroll
         for (int u = 0; u < 8; ++u) { a += v[u]; ov |= t[u] == DS_OVF; }
     }
-    for (; k < ws.G; k += 64) { a += ws.partial[row * ws.G + k]; ov |= ws.itm[k * ws.n + row] == DS_OVF; }
+    for (; k < ws.G; k += 64) { a += GIVEN ? 0.0 : ws.partial[row * ws.G + k]; ov |= ws.itm[k * ws.n + row] == DS_OVF; }
     a = wave_sum(a);
     ov = __ballot(ov != 0u) != 0ull;
     if (lane == 0) {
-        const float nv = (float)sqrt(a);
+        const float nv = GIVEN ? given[row] : (float)sqrt(a);
         ws.pn[row] = nv;
         if (pnorm_out) pnorm_out[row] = nv;
         ws.rpn[row] = 1.0f / nv;
@@ -1625,10 +1689,17 @@ static_assert(FLC_DS_LASTPCT >= 1 && FLC_DS_LASTPCT <= 100, "FLC_DS_LASTPCT: the
 #ifndef FLC_DS_PROBE_DEF
 #define FLC_DS_PROBE_DEF 0           // A/B variant builds only (a probe's outputs are NOT valid)
 #endif
-struct DsVariant { bool resident; int gridpct; int probe; int64_t rb; int cring; };
+#ifndef FLC_DS_TNSUMS
+// torch-order norm mode: 1 = the filter emits the torch lanes' sums (the rows are read twice:
+// filter + k_tn_maps), 0 = the three-read composition (k_tn_sums reads them once more; the
+// yardstick and the fallback).  Tuning builds: FLC_DS_TNSUMS=0|1 in the environment.
+#define FLC_DS_TNSUMS 1
+#endif
+struct DsVariant { bool resident; int gridpct; int probe; int64_t rb; int cring; bool tnsums; };
 static const DsVariant& ds_variant() {
     static const DsVariant v = [] {
-        DsVariant r{false, 100, FLC_DS_PROBE_DEF, DS_RB, DS_RINGC};
+        DsVariant r{false, 100, FLC_DS_PROBE_DEF, DS_RB, DS_RINGC, FLC_DS_TNSUMS != 0};
+        if (const char* e = tuning_env("FLC_DS_TNSUMS")) r.tnsums = atoi(e) != 0;
         if (const char* e = tuning_env("FLC_DS_CRING")) r.cring = atoi(e);
         if (const char* e = tuning_env("FLC_DS_RB")) r.rb = std::max<int64_t>(1, atoll(e));
         if (const char* e = tuning_env("FLC_DS_PROBE")) r.probe = atoi(e);
@@ -1639,7 +1710,9 @@ static const DsVariant& ds_variant() {
     return v;
 }
 
-static DsWs carve_ds(void* base, int64_t n, int64_t d, size_t* bytes) {
+// tn (the torch-order norm mode): the filter's per-lane sums and torch_norm.hip's workspace
+// behind everything the exact mode carves (whose layout and size do not change)
+static DsWs carve_ds(void* base, int64_t n, int64_t d, size_t* bytes, bool tn = false, void** tnws = nullptr) {
     Carver cv(base);
     const int64_t C = std::max<int64_t>(nchunks(d), 1), H = std::max<int64_t>(nhalves(d), 1);
     const int64_t nn = std::max<int64_t>(n, 1);
@@ -1665,6 +1738,12 @@ static DsWs carve_ds(void* base, int64_t n, int64_t d, size_t* bytes) {
     w.rk = cv.take<uint32_t>(nn);
     w.part = cv.take<float>((size_t)std::max<int64_t>(d, 1));
     w.gtab = cv.take<float4>(DS_MAXS);
+    w.tsum = nullptr;
+    if (tn) {
+        w.tsum = cv.take<double>((size_t)nn * w.G * 8);
+        char* t = cv.take<char>(norm_torch_ws_bytes(nn, d));
+        if (tnws) *tnws = t;
+    }
     if (bytes) *bytes = cv.bytes();
     return w;
 }
@@ -1684,10 +1763,10 @@ bool ds_eligible(const flc_codec_params* prm, const flc_pattern* pat, int64_t n,
     return share * DS_FGS * CHUNK <= (FLC_DS_V2 ? FLC_DS2_CAP : DS_GCAP) / 1.4;
 }
 
-size_t ds_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
+size_t ds_workspace(const flc_codec_params* prm, int64_t n, int64_t d, int norm_mode) {
     (void)prm;
     size_t b = 0;
-    carve_ds(nullptr, n, d, &b);
+    carve_ds(nullptr, n, d, &b, norm_mode == FLC_NORMMODE_TORCH_CPU);
     return b;
 }
 
@@ -1722,12 +1801,17 @@ static int ds_groups(const flc_codec_params* prm, int64_t n) {
 }
 
 int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d, const float* w,
-           float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes, hipStream_t st) {
+           float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes, hipStream_t st, const float* pnorm_in,
+           int norm_mode) {
     const DsVariant& v = ds_variant();
+    // the rows' norms: the filter's partials (exact), the caller's, or torch's CPU order (tn)
+    const bool tn = norm_mode == FLC_NORMMODE_TORCH_CPU && !pnorm_in;
+    const bool tns = tn && v.tnsums;                        // the filter emits the torch lanes' sums
     size_t need = 0;
-    carve_ds(nullptr, n, d, &need);
+    carve_ds(nullptr, n, d, &need, tn);
     if (ws_bytes < need) { set_error("dithering (sparse): workspace %zu < %zu", ws_bytes, need); return FLC_ERR_WORKSPACE; }
-    DsWs ws = carve_ds(wsp, n, d, nullptr);
+    void* tnws = nullptr;
+    DsWs ws = carve_ds(wsp, n, d, nullptr, tn, &tnws);
     const int64_t client0 = pat ? pat->client0 : 0;
     const int64_t H = nhalves(d);
     const int K = ds_groups(prm, n);
@@ -1739,7 +1823,9 @@ int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int
     auto filter = [&](int64_t r0, int64_t rn, hipStream_t s2 = nullptr, bool beside = false) -> int {
         // s2: the row group's norm / resolve go to this stream (after an event on st), under the
         // next group's filter
-        auto kern = compat ? (v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true>)
+        auto kern = tns ? (!compat ? k_ds_filter<16, DS_GCAP, 0, false, true>
+                                   : v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true, true>)
+                  : compat ? (v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true>)
                   : v.probe == 1 ? k_ds_filter<16, DS_GCAP, 1> : v.probe == 2 ? k_ds_filter<16, DS_GCAP, 2>
                   : v.probe == 3 ? k_ds_filter<16, DS_GCAP, 3> : v.probe == 4 ? k_ds_filter<16, DS_GCAP, 4>
                   : v.probe == 5 ? k_ds_filter<16, DS_GCAP, 5> : v.probe == 6 ? k_ds_filter<16, DS_GCAP, 6>
@@ -1769,7 +1855,18 @@ int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int
             FLC_CHECK_HIP(hipStreamWaitEvent(s2, filt_ev, 0));
             sr = s2;
         }
-        hipLaunchKernelGGL(k_ds_final, dim3((unsigned)((rn + 3) / 4)), dim3(256), 0, sr, r0, rn, ws, w, pnorm_out);
+        if (tn) {
+            // the group's norms in torch's order (k_tn_maps: the one extra read of its rows; with
+            // k_tn_sums, the three-read composition, two), where the exact mode's k_ds_final
+            // runs: under the next group's filter when there is one
+            if (int rc = tn_run(rows, n, r0, rn, d, ws.pn, tnws, tns ? ws.tsum : nullptr, ws.G, sr)) return rc;
+        }
+        if (tn || pnorm_in)
+            hipLaunchKernelGGL(k_ds_final<true>, dim3((unsigned)((rn + 3) / 4)), dim3(256), 0, sr, r0, rn, ws, w, pnorm_out,
+                               tn ? ws.pn : pnorm_in);
+        else
+            hipLaunchKernelGGL(k_ds_final<false>, dim3((unsigned)((rn + 3) / 4)), dim3(256), 0, sr, r0, rn, ws, w, pnorm_out,
+                               (const float*)nullptr);
         FLC_CHECK_LAUNCH("k_ds_final");
         int rb = (int)std::max<int64_t>(1, std::min<int64_t>(((rn + 63) / 64 * ws.G + 3) / 4, 8192));
         // beside the next group's filter: a bounded grid (grid-stride), so the side kernel holds a
@@ -1798,7 +1895,7 @@ int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int
         if (b <= a) return FLC_OK;
         ProfScope _ps("k_ds_sample", sx);
         hipLaunchKernelGGL(k_ds_sample, dim3((unsigned)(b - a)), dim3(DS_SNT), 0, sx, rows, n, d, prm->d_levels, prm->s, prm->seed,
-                           client0, ws, a);
+                           client0, ws, a, (tn || pnorm_in) ? 1 : 0);
         FLC_CHECK_LAUNCH("k_ds_sample");
         return FLC_OK;
     };

@@ -101,10 +101,10 @@ __device__ inline float tn_value(int32_t A, int eu) { return ldexpf((float)A, eu
 // k_tn_sums: per (part, row) the float64 sums of x^2 of the part's steps, per lane (a prediction).
 // Thread t takes steps t, t + TN_T, .. of the part: two float4 loads each (the 8 lanes of a step).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TN_T) void k_tn_sums(const float* __restrict__ base, int64_t ld, int64_t d, TnWs ws) {
+__global__ __launch_bounds__(TN_T) void k_tn_sums(RowSrc rows, int64_t r0, int64_t d, TnWs ws) {
     __shared__ double red[TN_T / 64][8];
-    const int64_t P = tn_parts(d), p = blockIdx.x, row = blockIdx.y;
-    const float* r = base + row * ld;
+    const int64_t P = tn_parts(d), p = blockIdx.x, row = r0 + blockIdx.y;
+    const float* r = rows.row(row);
     const int64_t steps = (d - d % 8) / 8;
     const int64_t k0 = p * TN_PS, k1 = min(k0 + (int64_t)TN_PS, steps);
     double s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -165,15 +165,15 @@ constexpr int TN_MT = 1024;                  // threads of k_tn_maps
 constexpr int TN_MS = TN_PS / TN_MT;         // steps a thread (4)
 static_assert(TN_XB == (TN_MT / TN_BPP) * TN_MS, "k_tn_maps: a block is 256 threads' steps");
 
-__global__ __launch_bounds__(TN_MT) void k_tn_maps(const float* __restrict__ base, int64_t ld, int64_t d, TnWs ws) {
+__global__ __launch_bounds__(TN_MT) void k_tn_maps(RowSrc rows, int64_t r0, int64_t d, TnWs ws) {
     // per thread and lane: its steps' float64 sum, then (reused) its composite map — reduced in
     // order by 32 threads (block b, lane l), one LDS column each: no shuffle chains
     __shared__ double cell[TN_MT][8];
     __shared__ double pre[8], bpre[TN_BPP][8], bsum[TN_BPP][8];
-    const int64_t P = tn_parts(d), p = blockIdx.x, row = blockIdx.y;
+    const int64_t P = tn_parts(d), p = blockIdx.x, row = r0 + blockIdx.y;
     const int t = threadIdx.x, blk = t / (TN_MT / TN_BPP);
     constexpr int TPB = TN_MT / TN_BPP;                                // threads per block (256)
-    const float* r = base + row * ld;
+    const float* r = rows.row(row);
     const int64_t steps = (d - d % 8) / 8;
     const int64_t k0 = p * TN_PS, k1 = min(k0 + (int64_t)TN_PS, steps);
     const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(r + 8 * k0), (short)0,
@@ -309,14 +309,13 @@ __device__ float tn_block_exact(const float* r, int l, int64_t k0, int64_t k1, f
 // row to finish sums the 8 lanes left to right, adds the tail and takes the square root.
 constexpr int TN_G = 4;                      // blocks per wave lane in a window
 
-__global__ __launch_bounds__(64) void k_tn_walk(const float* __restrict__ base, int64_t ld, int64_t d, TnWs ws,
-                                                float* __restrict__ out) {
+__global__ __launch_bounds__(64) void k_tn_walk(RowSrc rows, int64_t r0, int64_t d, TnWs ws, float* __restrict__ out) {
     __shared__ uint32_t last_s;
     __shared__ __attribute__((aligned(16))) float stage[TN_XB];
     const int l = blockIdx.x;
-    const int64_t row = blockIdx.y;
+    const int64_t row = r0 + blockIdx.y;
     const int j = threadIdx.x;
-    const float* r = base + row * ld;
+    const float* r = rows.row(row);
     const int64_t m = d - d % 8, steps = m / 8;
     const int64_t B = tn_parts(d) * TN_BPP, nb = (steps + TN_XB - 1) / TN_XB;
     const TnMap* mp = ws.maps + (row * 8 + l) * B;
@@ -429,26 +428,151 @@ size_t norm_torch_ws_bytes(int64_t n, int64_t d) {
     return b;
 }
 
+// ------------------------------------------------------------------------------------------
+// The maps from block sums somebody else took (the sparse dithering filter: a work item of 8192
+// elements is one TN_XB block of every lane, dither_sparse.hip): isums [n][G][8], block g of a row
+// = steps [g TN_XB, (g + 1) TN_XB).  Predictions like k_tn_sums' (they may count the D % 8 tail
+// into the last block: harmless).  Built for MANY rows per call, where k_tn_maps' serial LDS
+// columns (fine for one row's 763 workgroups) cost 51 ms at 512 x 25 M:
+//   k_tn_item_prefix  per row: sums[row][p][l] = the float64 sum of lane l's blocks BEFORE part p
+//                     (a half wave per lane scans 32 parts a round)
+//   k_tn_maps_items   per (part, row): the blocks' predicted grids from that prefix and the item
+//                     sums (nothing summed here), each thread's 4 steps composed, then an ORDERED
+//                     shuffle tree per wave and the block's 4 waves in order.  compose is
+//                     associative (exact integer arithmetic; a saturated composite stays TN_BIG
+//                     whatever the grouping, the increments being >= 0), so the tree gives
+//                     k_tn_maps' maps.
+// ------------------------------------------------------------------------------------------
+constexpr int TN_FT = 256;                   // threads of k_tn_item_prefix: 8 lanes x 32 parts
+
+__global__ __launch_bounds__(TN_FT) void k_tn_item_prefix(const double* __restrict__ isums, int64_t G, int64_t r0, int64_t d,
+                                                          TnWs ws) {
+    const int64_t P = tn_parts(d), row = r0 + blockIdx.x;
+    const int l = threadIdx.x >> 5, s = threadIdx.x & 31;
+    double carry = 0;
+    for (int64_t p0 = 0; p0 < P; p0 += 32) {                           // (uniform trip count: shuffles inside)
+        const int64_t p = p0 + s;
+        double v = 0;
+        if (p < P)
+            for (int64_t g = p * TN_BPP; g < (p + 1) * TN_BPP && g < G; ++g) v += isums[(row * G + g) * 8 + l];
+        for (int o = 1; o < 32; o <<= 1) {
+            const double u = __shfl_up(v, o, 32);
+            if (s >= o) v += u;
+        }
+        const double ex = __shfl_up(v, 1, 32);                         // the parts before, this round
+        if (p < P) ws.sums[(row * P + p) * 8 + l] = carry + (s ? ex : 0.0);
+        carry += __shfl(v, 31, 32);
+    }
+    if (threadIdx.x == 0) ws.done[row] = 0u;                           // (as k_tn_sums)
+}
+
+__global__ __launch_bounds__(TN_MT) void k_tn_maps_items(RowSrc rows, int64_t r0, int64_t d, TnWs ws,
+                                                         const double* __restrict__ isums, int64_t G) {
+    __shared__ int eus[TN_BPP][8];
+    __shared__ int2 wm[TN_MT / 64][8];
+    const int64_t P = tn_parts(d), p = blockIdx.x, row = r0 + blockIdx.y;
+    const int t = threadIdx.x, blk = t / (TN_MT / TN_BPP), lane = t & 63;
+    const float* r = rows.row(row);
+    const int64_t steps = (d - d % 8) / 8;
+    const int64_t k0 = p * TN_PS, k1 = min(k0 + (int64_t)TN_PS, steps);
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(r + 8 * k0), (short)0,
+                                                      (int)((k1 - k0) * 32), 0x00020000);
+    typedef unsigned int u4v __attribute__((ext_vector_type(4)));
+    u4v va[TN_MS], vb[TN_MS];
+#pragma unroll
+    for (int i = 0; i < TN_MS; ++i) {                                  // past k1: zeros (identity steps)
+        const uint32_t k = (uint32_t)(t * TN_MS + i);
+        va[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, k * 32u, 0, 2);
+        vb[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, k * 32u + 16u, 0, 2);
+    }
+    if (t < 8 * TN_BPP) {                                              // block b's predicted grid of lane l
+        const int b = t >> 3, l = t & 7;
+        double a = ws.sums[(row * P + p) * 8 + l], bs = 0;
+        for (int q = 0; q <= b; ++q) {
+            const int64_t g = p * TN_BPP + q;
+            const double v = g < G ? isums[(row * G + g) * 8 + l] : 0.0;
+            if (q < b) a += v;
+            else bs = v;
+        }
+        eus[b][l] = tn_predict(a, a + bs);
+    }
+    __syncthreads();
+    int32_t a0[8], a1[8];
+#pragma unroll
+    for (int l = 0; l < 8; ++l) {
+        const int eu = eus[blk][l];
+        a0[l] = a1[l] = 0;
+#pragma unroll
+        for (int i = 0; i < TN_MS; ++i) {
+            int32_t s0, s1;
+            tn_step(__uint_as_float(l < 4 ? va[i][l & 3] : vb[i][l & 3]), eu, s0, s1);
+            tn_compose(a0[l], a1[l], s0, s1, a0[l], a1[l]);
+        }
+    }
+    // ordered tree: after the round with offset o, every wave lane that is a multiple of 2 o holds
+    // the composite of the steps of lanes [lane, lane + 2 o)
+#pragma unroll
+    for (int l = 0; l < 8; ++l)
+        for (int o = 1; o < 64; o <<= 1) {
+            const int32_t b0 = __shfl_down(a0[l], o, 64), b1 = __shfl_down(a1[l], o, 64);
+            if ((lane & (2 * o - 1)) == 0) tn_compose(a0[l], a1[l], b0, b1, a0[l], a1[l]);
+        }
+    if (lane == 0)
+#pragma unroll
+        for (int l = 0; l < 8; ++l) wm[t >> 6][l] = make_int2(a0[l], a1[l]);
+    __syncthreads();
+    if (t < 8 * TN_BPP) {                                              // block b's map of lane l: its 4 waves in order
+        const int b = t >> 3, l = t & 7;
+        constexpr int WPB = TN_MT / TN_BPP / 64;
+        int32_t c0 = 0, c1 = 0;
+        for (int w = 0; w < WPB; ++w) {
+            const int2 m = wm[b * WPB + w][l];
+            tn_compose(c0, c1, m.x, m.y, c0, c1);
+        }
+        const int e = eus[b][l];
+        ws.maps[(row * 8 + l) * (P * TN_BPP) + p * TN_BPP + b] = TnMap{c0, c1, e, e != TN_NOGRID ? 1 : 0};
+    }
+}
+
+// Rows [r0, r0 + rn) of `rows` (ws carved for n rows and indexed by the absolute row, like out).
+// item_sums: the blocks' sums are given ([n][G][8]) — the rows are then read once
+// (k_tn_maps_items) instead of twice.
+int tn_run(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_t d, float* out, void* wsp, const double* item_sums,
+           int64_t G, hipStream_t st) {
+    if (rn <= 0) return FLC_OK;
+    const TnWs ws = carve_tn(wsp, n, d, nullptr);
+    const int64_t P = tn_parts(d);
+    if (rn > 65535) { set_error("torch-order norm: more than 65535 rows"); return FLC_ERR_ARG; }
+    if (P > 0) {
+        if (item_sums) {
+            { ProfScope _ps("k_tn_item_prefix", st);
+            hipLaunchKernelGGL(k_tn_item_prefix, dim3((unsigned)rn), dim3(TN_FT), 0, st, item_sums, G, r0, d, ws); }
+            FLC_CHECK_LAUNCH("k_tn_item_prefix");
+            { ProfScope _ps("k_tn_maps", st);
+            hipLaunchKernelGGL(k_tn_maps_items, dim3((unsigned)P, (unsigned)rn), dim3(TN_MT), 0, st, rows, r0, d, ws, item_sums, G); }
+            FLC_CHECK_LAUNCH("k_tn_maps_items");
+        } else {
+            { ProfScope _ps("k_tn_sums", st);
+            hipLaunchKernelGGL(k_tn_sums, dim3((unsigned)P, (unsigned)rn), dim3(TN_T), 0, st, rows, r0, d, ws); }
+            FLC_CHECK_LAUNCH("k_tn_sums");
+            { ProfScope _ps("k_tn_maps", st);
+            hipLaunchKernelGGL(k_tn_maps, dim3((unsigned)P, (unsigned)rn), dim3(TN_MT), 0, st, rows, r0, d, ws); }
+            FLC_CHECK_LAUNCH("k_tn_maps");
+        }
+    }
+    if (P == 0) FLC_CHECK_HIP(hipMemsetAsync(ws.done + r0, 0, (size_t)rn * sizeof(uint32_t), st));   // (no k_tn_sums)
+    { ProfScope _ps("k_tn_walk", st);
+    hipLaunchKernelGGL(k_tn_walk, dim3(8u, (unsigned)rn), dim3(64), 0, st, rows, r0, d, ws, out); }
+    FLC_CHECK_LAUNCH("k_tn_walk");
+    return FLC_OK;
+}
+
 int norm_torch_ws_run(const float* x, int64_t ld, int64_t n, int64_t d, float* out, void* wsp, size_t ws_bytes,
                       hipStream_t st) {
     if (n <= 0) return FLC_OK;
     if (ws_bytes < norm_torch_ws_bytes(n, d)) { set_error("flc_norm2_torch_cpu_ws: workspace too small"); return FLC_ERR_WORKSPACE; }
-    const TnWs ws = carve_tn(wsp, n, d, nullptr);
-    const int64_t P = tn_parts(d);
-    if (P > 0) {
-        if (n > 65535) { set_error("flc_norm2_torch_cpu_ws: n > 65535"); return FLC_ERR_ARG; }
-        { ProfScope _ps("k_tn_sums", st);
-        hipLaunchKernelGGL(k_tn_sums, dim3((unsigned)P, (unsigned)n), dim3(TN_T), 0, st, x, ld, d, ws); }
-        FLC_CHECK_LAUNCH("k_tn_sums");
-        { ProfScope _ps("k_tn_maps", st);
-        hipLaunchKernelGGL(k_tn_maps, dim3((unsigned)P, (unsigned)n), dim3(TN_MT), 0, st, x, ld, d, ws); }
-        FLC_CHECK_LAUNCH("k_tn_maps");
-    }
-    if (P == 0) FLC_CHECK_HIP(hipMemsetAsync(ws.done, 0, (size_t)n * sizeof(uint32_t), st));   // (no k_tn_sums)
-    { ProfScope _ps("k_tn_walk", st);
-    hipLaunchKernelGGL(k_tn_walk, dim3(8u, (unsigned)n), dim3(64), 0, st, x, ld, d, ws, out); }
-    FLC_CHECK_LAUNCH("k_tn_walk");
-    return FLC_OK;
+    if (n > 65535) { set_error("flc_norm2_torch_cpu_ws: n > 65535"); return FLC_ERR_ARG; }
+    return tn_run(RowSrc{x, ld, nullptr}, n, 0, n, d, out, wsp, nullptr, 0, st);
 }
 
 }  // namespace flc

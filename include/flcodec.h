@@ -170,6 +170,33 @@ int flc_encode_reduce(const flc_codec_params* prm, const flc_pattern* pat, const
                       const float* d_w, float w_total, float* d_pnorms_out, float* d_out,
                       void* d_ws, size_t ws_bytes, void* stream);
 
+/* The same call with the dithering codecs' norms chosen by the caller (ABI 1.04, additive):
+ *   d_pnorms_in : [n] device fp32 norms to use instead of computing any — the norms a server
+ *                 receives on the wire (flc_encode's d_pnorm_in, per row) — or NULL: compute.
+ *                 Dithering codecs only; ignored by the others.
+ *   norm_mode   : FLC_NORMMODE_EXACT      the correctly rounded norm (flc_encode_reduce)
+ *                 FLC_NORMMODE_TORCH_CPU  p = 2 of standard / natural dithering as the reference
+ *                                         computes it: torch.norm(x, p=2) on a CPU fp32 tensor
+ *                                         (compressors.py:272 / 303), in torch's reduction order,
+ *                                         bit for bit (flc_norm2_torch_cpu_ws per row).  p = inf:
+ *                                         the same as EXACT (a maximum has no order); p = 1:
+ *                                         FLC_ERR_UNSUPPORTED before any launch.
+ * Both selectors at once: FLC_ERR_ARG.  d_pnorms_out reports the norms used in every mode.
+ * The workspace size depends on the selectors (norms given: yes / no, and the mode); a smaller
+ * workspace is FLC_ERR_WORKSPACE before any launch.  flc_encode_reduce is this call with
+ * (NULL, FLC_NORMMODE_EXACT); its results and its workspace size are the same as before.
+ * A row whose given norm is outside the bounds the sparse QSGD path sampled is encoded by the
+ * dense fold: every norm gives the bits of flc_encode with that d_pnorm_in, reduced in order. */
+#define FLC_NORMMODE_EXACT 0
+#define FLC_NORMMODE_TORCH_CPU 1
+size_t flc_encode_reduce_ex_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d,
+                                           int norms_given, int norm_mode);
+int flc_encode_reduce_ex(const flc_codec_params* prm, const flc_pattern* pat, const float* d_rows,
+                         int64_t ld, const float* const* d_row_ptrs, int64_t n, int64_t d,
+                         const float* d_w, float w_total, const float* d_pnorms_in, int norm_mode,
+                         float* d_pnorms_out, float* d_out, void* d_ws, size_t ws_bytes,
+                         void* stream);
+
 /* ----------------------------------------------------------------------------------------
  * Shift codecs — the client-side update of the compressed algorithms,
  * one client row, with e = C(a - b) never stored for the elementwise codecs:
