@@ -39,6 +39,7 @@ EXPORTS = [
     "flc_encode_reduce_workspace_size", "flc_encode_reduce",
     "flc_encode_reduce_ex_workspace_size", "flc_encode_reduce_ex",
     "flc_encode_shift_workspace_size", "flc_encode_shift",
+    "flc_encode_shift_reduce_workspace_size", "flc_encode_shift_reduce",
     "flc_payload_bytes", "flc_payload_format", "flc_payload_validate", "flc_pack_workspace_size", "flc_pack", "flc_unpack",
     "flc_unpack_reduce_workspace_size", "flc_unpack_reduce",
     "flc_combine_workspace_size", "flc_combine_partials",
@@ -76,6 +77,20 @@ class FlcPattern(ctypes.Structure):
         ("uniforms_ld", ctypes.c_int64),
         ("idx_ld", ctypes.c_int64),
         ("d_randk_counts", ctypes.c_void_p),
+    ]
+
+
+class FlcShiftRows(ctypes.Structure):
+    """flc_shift_rows: the operands of flc_encode_shift_reduce, row i of each at ptr + i * ld."""
+    _fields_ = [
+        ("d_a", ctypes.c_void_p), ("lda", ctypes.c_int64),
+        ("d_b", ctypes.c_void_p), ("ldb", ctypes.c_int64),
+        ("d_base", ctypes.c_void_p), ("ldbase", ctypes.c_int64),
+        ("msg_scale", ctypes.c_float),
+        ("d_msg", ctypes.c_void_p), ("ldmsg", ctypes.c_int64),
+        ("shift_alpha", ctypes.c_float),
+        ("d_shift_in", ctypes.c_void_p), ("ldin", ctypes.c_int64),
+        ("d_shift_out", ctypes.c_void_p), ("ldout", ctypes.c_int64),
     ]
 
 
@@ -157,6 +172,11 @@ def _bind(lib):
     lib.flc_encode_shift_workspace_size.restype = sz
     lib.flc_encode_shift.argtypes = [P(FlcCodecParams), P(FlcPattern), vp, vp, i64, f32, vp, vp, f32, vp, vp, vp,
                                      vp, sz, vp]
+    if hasattr(lib, "flc_encode_shift_reduce"):     # (absent from A/B builds of older revisions)
+        lib.flc_encode_shift_reduce_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_encode_shift_reduce_workspace_size.restype = sz
+        lib.flc_encode_shift_reduce.argtypes = [P(FlcCodecParams), P(FlcPattern), P(FlcShiftRows), i64, i64, vp, f32,
+                                                vp, vp, vp, sz, vp]
     lib.flc_payload_bytes.argtypes = [P(FlcCodecParams), i64]
     lib.flc_payload_bytes.restype = i64
     lib.flc_payload_format.argtypes = [P(FlcCodecParams)]
@@ -204,7 +224,8 @@ def _bind(lib):
             continue
         if name not in ("flc_version", "flc_build_id", "flc_last_error_string", "flc_device_uniform",
                         "flc_encode_workspace_size", "flc_encode_reduce_workspace_size",
-                        "flc_encode_reduce_ex_workspace_size", "flc_encode_shift_workspace_size", "flc_payload_bytes", "flc_pack_workspace_size",
+                        "flc_encode_reduce_ex_workspace_size", "flc_encode_shift_workspace_size",
+                        "flc_encode_shift_reduce_workspace_size", "flc_payload_bytes", "flc_pack_workspace_size",
                         "flc_unpack_reduce_workspace_size", "flc_combine_workspace_size",
                         "flc_combine_blocks_workspace_size", "flc_device_randk_counts_workspace_size",
                         "flc_norm2_torch_cpu_workspace_size"):

@@ -16,6 +16,7 @@ Pattern sources
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from .. import _lib
@@ -210,6 +211,165 @@ class UplinkReducer:
                                           ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), st)
         _lib.check(rc, "flc_encode_reduce_ex")
         return out
+
+
+class ShiftUplinkReducer:
+    """A DIANA / EF21 / MARINA / FRECON / COFIG round of N resident clients in one call
+    (flc_encode_shift_reduce):
+
+        msg_i = base_i + C_i(a_i - b_i) * scale;   shift_i' = shift_i + alpha * C_i(a_i - b_i)
+        out   = (sum_i w_i * msg_i) / sum(w)
+
+    Row i gets exactly the bits ``Compressor.compressShift`` gives for (a_i, b_i, base_i, shift_i)
+    under pattern row i / client ``client0 + i``, and ``out`` the bits of ``reduce_rows`` over the N
+    messages in client order — without storing them.  Elementwise codecs run one tile-owner pass
+    (k_ew_shift_accum, after one norm pass over the differences for dithering); RandK / TopK /
+    Rank-K run their rows in order with a fold step each (correct, not a fast path).  Dithering
+    encodes with the exactly rounded norm of a_i - b_i, like ``compressShift``: the compressor's
+    ``norm_mode = "torch_cpu"`` does not apply to shifted steps."""
+
+    def __init__(self, compressor: Compressor, device=None, seed=None):
+        _lib.require_gpu()
+        self.comp = compressor
+        self.device = _device(device)
+        self.seed = seed
+
+    def params(self):
+        prm, keep = self.comp.codec_params(self.device)
+        if self.seed is not None:
+            prm.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
+        return prm, keep
+
+    def workspace_bytes(self, n, d):
+        prm, _ = self.params()
+        return _lib.load().flc_encode_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
+
+    def __call__(self, a, b, *, scale=1.0, base=None, msg_out=None, alpha=None, shift=None, shift_out=None, out=None,
+                 weights=None, divisor=None, client0=0, randk_idx=None, uniforms=None, lazy_u=None, pnorms_out=None,
+                 stream=None):
+        """a, b: [N, D] fp32 row-contiguous device matrices (local gradients; shifts / previous
+        estimators / previous gradients).  ``base``: None, [N, D], or ONE [D] vector for every row
+        (MARINA's g_prev).  ``msg_out``: None (the messages are not stored) or [N, D]; it may be ``b``
+        / ``base`` (EF21 in place).  ``alpha`` with ``shift`` [N, D]: the updated shifts go to
+        ``shift_out`` (a new matrix when None; it may be ``shift`` / ``b``: DIANA in place).
+        Patterns, ``weights``, ``divisor`` and ``stream`` as in ``UplinkReducer``; ``lazy_u`` is read
+        back to the host once for the wire statistics.  Returns ``(out, msg_out, shift_out)``.  The
+        compressor's wire statistics advance as N consecutive ``compressShift`` calls would leave them.
+        The vector kernel needs every operand 16-byte aligned with a row stride that is a multiple
+        of 4; anything else runs the scalar kernel (same bits)."""
+        args = (a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx, uniforms,
+                lazy_u, pnorms_out)
+        if stream is not None:
+            if stream.device != self.device:
+                raise ValueError(f"stream is on {stream.device}, the reducer runs on {self.device}")
+            with torch.cuda.stream(stream):
+                return self._run(*args)
+        return self._run(*args)
+
+    def _run(self, a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx,
+             uniforms, lazy_u, pnorms_out):
+        lib = _lib.load()
+        if not hasattr(lib, "flc_encode_shift_reduce"):
+            raise NotImplementedError("this library build has no flc_encode_shift_reduce")
+        dev = self.device
+        for name, v in (("a", a), ("b", b), ("base", base), ("msg_out", msg_out), ("shift", shift),
+                        ("shift_out", shift_out), ("out", out)):
+            if v is not None and (not torch.is_tensor(v) or v.dtype != torch.float32 or not v.is_cuda):
+                raise TypeError(f"ShiftUplinkReducer: {name} must be an fp32 device tensor")
+        if a.dim() != 2:
+            raise ValueError("ShiftUplinkReducer: a must be an [N, D] matrix")
+        n, d = a.shape
+
+        def rows(name, v):
+            if tuple(v.shape) != (n, d):
+                raise ValueError(f"ShiftUplinkReducer: {name} must be [{n}, {d}] like a (got {tuple(v.shape)})")
+            if d > 1 and v.stride(1) != 1:
+                raise ValueError(f"ShiftUplinkReducer: {name} must be row-contiguous")
+            return v.data_ptr(), v.stride(0)
+        sr = _lib.FlcShiftRows()
+        sr.d_a, sr.lda = rows("a", a)
+        sr.d_b, sr.ldb = rows("b", b)
+        if base is not None:
+            if base.dim() == 1:
+                if base.numel() != d or (d > 1 and base.stride(0) != 1):
+                    raise ValueError(f"ShiftUplinkReducer: a shared base must be a contiguous [{d}] vector")
+                sr.d_base, sr.ldbase = base.data_ptr(), 0
+            else:
+                sr.d_base, sr.ldbase = rows("base", base)
+                if n > 1 and sr.ldbase == 0:
+                    raise ValueError("ShiftUplinkReducer: pass a shared base as a [D] vector")
+        if alpha is not None and shift is None:
+            raise ValueError("ShiftUplinkReducer: alpha given without a shift matrix")
+        if alpha is None and shift_out is not None:
+            raise ValueError("ShiftUplinkReducer: shift_out given without alpha")
+        if msg_out is not None:
+            sr.d_msg, sr.ldmsg = rows("msg_out", msg_out)
+        if alpha is not None:
+            sr.d_shift_in, sr.ldin = rows("shift", shift)
+            if shift_out is None:
+                shift_out = torch.empty((n, d), dtype=torch.float32, device=dev)
+            sr.d_shift_out, sr.ldout = rows("shift_out", shift_out)
+        sr.msg_scale = float(np.float32(scale))
+        sr.shift_alpha = float(np.float32(alpha if alpha is not None else 0.0))
+        if out is None:
+            out = torch.empty(d, dtype=torch.float32, device=dev)
+        elif out.numel() != d or not out.is_contiguous():
+            raise ValueError(f"ShiftUplinkReducer: out must be a contiguous [{d}] vector")
+        if n == 0:
+            return out.zero_(), msg_out, shift_out               # no clients (algorithms.py:2117-2118)
+        prm, keep = self.params()
+        pat = _lib.FlcPattern()
+        pat.client0 = int(client0)
+        t = self.comp.compressorType
+        if t == CompressorType.RANDK_COMPRESSOR and randk_idx is not None:
+            pat.d_randk_idx = randk_idx.data_ptr()
+            pat.idx_ld = randk_idx.stride(0)
+        if uniforms is not None:
+            pat.d_uniforms = uniforms.data_ptr()
+            pat.uniforms_ld = uniforms.stride(0)
+        lazy_host = None
+        if t == CompressorType.LAZY_COMPRESSOR:
+            if lazy_u is None:
+                raise ValueError("lazy codec needs lazy_u [N] draws")
+            lazy_u = torch.as_tensor(lazy_u, dtype=torch.float64)
+            if lazy_u.numel() != n:
+                raise ValueError(f"lazy_u must hold {n} draws")
+            lazy_host = [float(x) for x in lazy_u.detach().cpu().reshape(-1).tolist()]
+            lazy_u = lazy_u.to(dev).contiguous()
+            keep.append(lazy_u)
+            pat.d_lazy_u = lazy_u.data_ptr()
+        needs_seed = (t == CompressorType.RANDK_COMPRESSOR and randk_idx is None) or \
+                     (t in (CompressorType.NATURAL_COMPRESSOR_FP32, CompressorType.STANDARD_DITHERING_FP32)
+                      and uniforms is None)
+        if needs_seed and self.seed is None and self.comp.device_rng is None:
+            raise ValueError("no compat pattern given and no device-RNG seed set")
+        w_ptr, total = None, float(n)
+        if weights is not None:
+            weights = [float(w) for w in weights]
+            if len(weights) != n:
+                raise ValueError(f"weights must hold {n} values")
+            total = weights[0]
+            for w in weights[1:]:
+                total += w
+            wt = torch.tensor(weights, dtype=torch.float32, device=dev)
+            keep.append(wt)
+            w_ptr = wt.data_ptr()
+        if divisor is not None:
+            total = float(divisor)
+        if d > 0:
+            ws = _lib.WORKSPACE.get(dev, lib.flc_encode_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
+            with torch.cuda.device(dev):
+                rc = lib.flc_encode_shift_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.byref(sr), n, d,
+                                                 ctypes.c_void_p(w_ptr), ctypes.c_float(total),
+                                                 ctypes.c_void_p(pnorms_out.data_ptr() if pnorms_out is not None else None),
+                                                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                                 ws.numel(), _lib.stream_ptr(dev))
+            _lib.check(rc, "flc_encode_shift_reduce")
+        for i in range(n):                                        # N compressShift calls' statistics
+            if lazy_host is not None:
+                self.comp.testp = lazy_host[i]
+            self.comp._account(d)
+        return out, msg_out, shift_out
 
 
 class PayloadReducer:

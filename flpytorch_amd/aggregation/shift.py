@@ -29,3 +29,38 @@ def marinaStep(compressor, grad_cur, grad_prev, g_prev):
     """MARINA / PP-MARINA (algorithms.py:537, 691): ``g_next = g_prev + C(grad_cur - grad_prev)``."""
     msg, _ = compressor.compressShift(grad_cur, grad_prev, base=g_prev)
     return msg
+
+
+# -- a whole round of N resident clients in one call (flc_encode_shift_reduce) --------------------
+def _uplink(compressor, like, seed):
+    from .fused import ShiftUplinkReducer
+    if seed is None and compressor.device_rng is not None:
+        seed = compressor.device_rng[0]
+    return ShiftUplinkReducer(compressor, device=like.device, seed=seed)
+
+
+def dianaUplink(compressor, G, H, alpha, *, seed=None, **kw):
+    """The DIANA round of N resident clients (rows of ``G`` and ``H``), also FRECON's / COFIG's u_i:
+    ``m_i = C_i(G_i - H_i); H_i += alpha * m_i`` in place, and the fold ``(sum_i w_i m_i) / sum(w)``
+    is returned — the server's ``gs`` before it adds its own shift — without storing any m_i.  Same
+    bits as N ``dianaStep(in_place=True)`` calls and ``reduce_rows`` of their messages.  ``kw``:
+    ``ShiftUplinkReducer.__call__``'s weights / divisor / client0 / patterns / out / stream."""
+    out, _, _ = _uplink(compressor, G, seed)(G, H, alpha=alpha, shift=H, shift_out=H, **kw)
+    return out
+
+
+def ef21Uplink(compressor, G, G_prev, *, seed=None, **kw):
+    """The EF21 round: ``G_prev_i += C_i(G_i - G_prev_i) * mult`` in place (``mult`` as in
+    ``ef21Step``) and the fold of the new estimators is returned."""
+    mult = 1.0
+    if not compressor.isContractionCompressor():
+        mult = 1.0 / (1.0 + compressor.getW())
+    out, _, _ = _uplink(compressor, G, seed)(G, G_prev, scale=mult, base=G_prev, msg_out=G_prev, **kw)
+    return out
+
+
+def marinaUplink(compressor, G_cur, G_prev_rows, g_prev, *, seed=None, **kw):
+    """The MARINA / PP-MARINA compressed round: the fold of ``g_prev + C_i(G_cur_i - G_prev_rows_i)``
+    with ONE shared ``g_prev`` [D] vector; no message is stored."""
+    out, _, _ = _uplink(compressor, G_cur, seed)(G_cur, G_prev_rows, base=g_prev, **kw)
+    return out

@@ -260,6 +260,59 @@ extern "C" int flc_encode_shift(const flc_codec_params* prm, const flc_pattern* 
     return shift_run(prm, pat, d_a, d, sh, d_pnorm_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+extern "C" size_t flc_encode_shift_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (!prm || !known(prm->codec) || n < 0 || d < 0) return 0;
+    return shift_reduce_workspace(prm, n, d);
+}
+
+namespace flc {
+// the element range [lo, hi) that n rows of d elements at p + i * ld cover
+static void row_span(const float* p, int64_t ld, int64_t n, int64_t d, uintptr_t* lo, uintptr_t* hi) {
+    const int64_t last = (n - 1) * ld;
+    const float* a = p + std::min<int64_t>(0, last);
+    const float* b = p + std::max<int64_t>(0, last) + d;
+    *lo = (uintptr_t)a;
+    *hi = (uintptr_t)b;
+}
+}  // namespace flc
+
+extern "C" int flc_encode_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
+                                       int64_t n, int64_t d, const float* d_w, float w_total, float* d_pnorms_out,
+                                       float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_encode_shift_reduce";
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (int rc = bad_params(prm, me)) return rc;
+    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) {
+        set_error("%s: n=%lld rows, at most %d per call (fold larger rounds as partials)", me, (long long)n, FLC_MAX_ROWS);
+        return FLC_ERR_ARG;
+    }
+    if (n == 0 || d == 0) return FLC_OK;
+    if (!rows || !rows->d_a || !rows->d_b || !d_out) { set_error("%s: need rows, a, b and out", me); return FLC_ERR_ARG; }
+    flc_shift_rows sr = *rows;
+    if (sr.d_shift_out && !sr.d_shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
+    if (!sr.d_shift_out) { sr.d_shift_in = nullptr; sr.ldin = sr.ldout = 0; }   // a shift nobody stores is not read
+    if (!sr.d_base) sr.ldbase = 0;
+    if (!sr.d_msg) sr.ldmsg = 0;
+    auto short_ld = [&](int64_t ld) { return n > 1 && (ld < 0 ? -ld : ld) < d; };
+    if (sr.d_msg && short_ld(sr.ldmsg)) { set_error("%s: the d_msg rows overlap (|ldmsg| < d)", me); return FLC_ERR_ARG; }
+    if (sr.d_shift_out && short_ld(sr.ldout)) { set_error("%s: the d_shift_out rows overlap (|ldout| < d)", me); return FLC_ERR_ARG; }
+    if (sr.d_base && sr.ldbase == 0 && n > 1) {
+        // one base vector for every row: an output that overlaps it would change it under the later rows
+        const uintptr_t b0 = (uintptr_t)sr.d_base, b1 = (uintptr_t)(sr.d_base + d);
+        uintptr_t lo, hi;
+        if (sr.d_msg) {
+            row_span(sr.d_msg, sr.ldmsg, n, d, &lo, &hi);
+            if (lo < b1 && b0 < hi) { set_error("%s: d_msg overlaps the shared base", me); return FLC_ERR_ARG; }
+        }
+        if (sr.d_shift_out) {
+            row_span(sr.d_shift_out, sr.ldout, n, d, &lo, &hi);
+            if (lo < b1 && b0 < hi) { set_error("%s: d_shift_out overlaps the shared base", me); return FLC_ERR_ARG; }
+        }
+    }
+    return shift_reduce_run(prm, pat, sr, n, d, d_w, w_total, d_pnorms_out, d_out, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
 extern "C" int64_t flc_payload_bytes(const flc_codec_params* prm, int64_t d) {
     if (!prm || !known(prm->codec) || d < 0) return 0;
     return payload_bytes(prm, d);

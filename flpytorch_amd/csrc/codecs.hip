@@ -53,13 +53,14 @@ __device__ inline double ncomb(double a, double b) {
 // nonzero |v| below 2^-80: the row cannot use the unguarded fast division (div_fast)
 __device__ inline uint32_t is_tiny(float v) { const float a = fabsf(v); return (a != 0.f && a < 0x1p-80f) ? 1u : 0u; }
 
-// DIFF: the row is the fp32 difference src.row(0) - sub (the shift codecs' C(a - b), one row)
+// DIFF: row i is the fp32 difference src.row(i) - subs.row(i) (the shift codecs' C(a_i - b_i))
 template <int NORM, bool VEC, bool DIFF, bool KEEP = false>
-__global__ __launch_bounds__(256) void k_norm_partials(RowSrc src, const float* __restrict__ sub, int64_t d,
+__global__ __launch_bounds__(256) void k_norm_partials(RowSrc src, RowSrc subs, int64_t d,
                                                        int64_t parts, int64_t plen, double* __restrict__ partial,
                                                        uint32_t* __restrict__ tinyp) {
     const int64_t row = blockIdx.y;
     const float* r = src.row(row);
+    const float* sub = DIFF ? subs.row(row) : nullptr;
     auto ld1 = [&](int64_t j) -> float { return DIFF ? r[j] - sub[j] : r[j]; };
     __shared__ double red[4];
     __shared__ uint32_t redt[4];
@@ -161,8 +162,9 @@ int64_t norm_parts(int64_t n, int64_t d) { const int64_t l = norm_part_len(n, d)
 
 int launch_norms(RowSrc src, bool vec, int64_t n, int64_t d, int norm, double* partial, uint32_t* tinyp,
                  float* pn, float* rpn, uint32_t* rowfast, uint64_t seed, int64_t client0, uint32_t* rk,
-                 hipStream_t st, const float* sub) {
-    if (sub && n != 1) { set_error("launch_norms: a difference source is one row"); return FLC_ERR_ARG; }
+                 hipStream_t st, const RowSrc* subp) {
+    const bool sub = subp != nullptr;   // the rows subtracted before the norm (vec: they are aligned too)
+    const RowSrc subs = sub ? *subp : RowSrc{nullptr, 0, nullptr};
     const int64_t parts = norm_parts(n, d), plen = norm_part_len(n, d);
     if (n == 0) return FLC_OK;
     if (parts == 0) {  // d == 0: norm of an empty vector
@@ -175,10 +177,10 @@ int launch_norms(RowSrc src, bool vec, int64_t n, int64_t d, int norm, double* p
     dim3 grid((unsigned)std::min<int64_t>(parts, std::max<int64_t>(64, 4096 / std::max<int64_t>(n, 1))), (unsigned)n);
 #define FLC_NORM_CASE(NK)                                                                           \
     { ProfScope _ps("k_norm_partials", st);                                                         \
-    if (sub && vec) hipLaunchKernelGGL((k_norm_partials<NK, true, true>), grid, dim3(256), 0, st, src, sub, d, parts, plen, partial, tinyp); \
-    else if (sub) hipLaunchKernelGGL((k_norm_partials<NK, false, true>), grid, dim3(256), 0, st, src, sub, d, parts, plen, partial, tinyp); \
-    else if (vec) hipLaunchKernelGGL((k_norm_partials<NK, true, false>), grid, dim3(256), 0, st, src, sub, d, parts, plen, partial, tinyp); \
-    else hipLaunchKernelGGL((k_norm_partials<NK, false, false>), grid, dim3(256), 0, st, src, sub, d, parts, plen, partial, tinyp); } \
+    if (sub && vec) hipLaunchKernelGGL((k_norm_partials<NK, true, true>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp); \
+    else if (sub) hipLaunchKernelGGL((k_norm_partials<NK, false, true>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp); \
+    else if (vec) hipLaunchKernelGGL((k_norm_partials<NK, true, false>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp); \
+    else hipLaunchKernelGGL((k_norm_partials<NK, false, false>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp); } \
     FLC_CHECK_LAUNCH("k_norm_partials");                                                            \
     hipLaunchKernelGGL((k_norm_final<NK>), dim3((unsigned)n), dim3(64), 0, st, partial, tinyp, parts, n, pn, rpn,   \
                        rowfast, seed, client0, rk);                                                 \
@@ -543,6 +545,159 @@ __global__ __launch_bounds__(256) void k_ew_accum_scalar(RowSrc src, int64_t n, 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Fused shifted uplink over N rows (flc_encode_shift_reduce; DIANA / EF21 / MARINA / FRECON / COFIG
+// rounds of N resident clients): the tile owner of k_ew_accum_vec with k_ew_shift's epilogue.  Per
+// row i, every op rounded separately exactly as k_ew_shift / shift_epi1:
+//     v = a_i - b_i;  e = C_i(v);  t = e * scale;  m = base_i + t (or t);  acc (+)= w_i * m
+//     msg_i = m (when stored);  h_i' = hin_i + alpha * e (when stored);  at the end out = acc / wt
+// Only a and b go through the register ring (PF rows in flight); base / hin are the ring's b value
+// when they are the b rows (EF21's base, DIANA's shift: BASE_B / hin_b), one hoisted float4 per
+// column for a shared base (MARINA's g_prev: BASE_SHARED), else loaded at use.  Every element of
+// every row is read and written by one thread, all of a row's loads before its stores, so msg_i /
+// h_i' may be row i of b, base or hin (the in-place rounds).
+// ------------------------------------------------------------------------------------------
+enum { BASE_NONE = 0, BASE_ROWS = 1, BASE_SHARED = 2, BASE_B = 3 };
+// tile shape: float4 columns per thread x rows in flight, 2 x 2 as k_ew_accum_vec
+// (-DFLC_SHIFT_COLS / -DFLC_SHIFT_PF for A/B builds; on the same matrices at N = 128, D = 25 M the
+// natural codec's 1 x 2 and 2 x 1 time within the repeats' spread of 2 x 2, 11.4-11.7 ms, and
+// dithering's round is 1-3 % slower with 1 x 2, 2 x 1 or 1 x 4: 11.29-11.49 against 11.15 ms)
+#ifndef FLC_SHIFT_COLS
+#define FLC_SHIFT_COLS 2
+#endif
+#ifndef FLC_SHIFT_PF
+#define FLC_SHIFT_PF 2
+#endif
+
+__device__ inline float4 shift_msg4(float4 e, float scale, bool has_base, float4 bs) {
+    const float4 t = make_float4(e.x * scale, e.y * scale, e.z * scale, e.w * scale);
+    return has_base ? make_float4(bs.x + t.x, bs.y + t.y, bs.z + t.z, bs.w + t.w) : t;
+}
+
+template <class Op, int COLS, int PF, bool W>
+__global__ __launch_bounds__(256) void k_ew_shift_accum(flc_shift_rows sr, int base_mode, int hin_b, int64_t n,
+                                                        int64_t d, Op op, const float* __restrict__ levels, int s,
+                                                        const float* __restrict__ w, float wt, float* out) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem_tab[];
+    if (Op::TABLE) op.set_table_ok(load_table(levels, s, smem_tab));
+    const int64_t groups = d / 4;
+    const int64_t tile_groups = (int64_t)blockDim.x * COLS;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t t0 = (int64_t)blockIdx.x * tile_groups; t0 < groups; t0 += (int64_t)gridDim.x * tile_groups) {
+        int64_t gi[COLS];
+        bool ok[COLS];
+        uint32_t cs[COLS][4];
+        float4 shared_bs[COLS];
+#pragma unroll
+        for (int c = 0; c < COLS; ++c) {
+            gi[c] = t0 + threadIdx.x + c * 256;
+            ok[c] = gi[c] < groups;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) cs[c][q] = op.col(gi[c] * 4 + q);
+            shared_bs[c] = (base_mode == BASE_SHARED && ok[c]) ? reinterpret_cast<const float4*>(sr.d_base)[gi[c]] : zero4;
+        }
+        float4 ra[PF][COLS], rb[PF][COLS];
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            if (p < n) {
+                const float4* pa = reinterpret_cast<const float4*>(sr.d_a + p * sr.lda);
+                const float4* pb = reinterpret_cast<const float4*>(sr.d_b + p * sr.ldb);
+#pragma unroll
+                for (int c = 0; c < COLS; ++c) {
+                    ra[p][c] = ok[c] ? ld_row4(pa + gi[c]) : zero4;
+                    rb[p][c] = ok[c] ? ld_row4(pb + gi[c]) : zero4;
+                }
+            }
+        }
+        float4 acc[COLS];
+        for (int64_t i0 = 0; i0 < n; i0 += PF) {
+#pragma unroll
+            for (int p = 0; p < PF; ++p) {
+                const int64_t i = i0 + p;
+                if (i < n) {
+                    op.setup(i);
+                    const float wi = W ? w[i] : 1.f;
+                    // the row's remaining loads (operands that are not the b rows), before any store
+                    float4 bs[COLS], hv[COLS], v[COLS];
+#pragma unroll
+                    for (int c = 0; c < COLS; ++c) {
+                        bs[c] = base_mode == BASE_B ? rb[p][c] : shared_bs[c];
+                        if (base_mode == BASE_ROWS)
+                            bs[c] = ok[c] ? reinterpret_cast<const float4*>(sr.d_base + i * sr.ldbase)[gi[c]] : zero4;
+                        hv[c] = rb[p][c];
+                        if (sr.d_shift_out && !hin_b)
+                            hv[c] = ok[c] ? reinterpret_cast<const float4*>(sr.d_shift_in + i * sr.ldin)[gi[c]] : zero4;
+                        v[c] = make_float4(ra[p][c].x - rb[p][c].x, ra[p][c].y - rb[p][c].y, ra[p][c].z - rb[p][c].z,
+                                           ra[p][c].w - rb[p][c].w);
+                    }
+                    float4 e[COLS];
+                    if (op.row_fast())     // row-uniform: the whole difference row inside the fast-division window
+                        apply_cols<true, COLS>(op, v, gi, cs, smem_tab, e);
+                    else
+                        apply_cols<false, COLS>(op, v, gi, cs, smem_tab, e);
+#pragma unroll
+                    for (int c = 0; c < COLS; ++c) {
+                        const float4 m = shift_msg4(e[c], sr.msg_scale, base_mode != BASE_NONE, bs[c]);
+                        const float4 t = W ? make_float4(wi * m.x, wi * m.y, wi * m.z, wi * m.w) : m;
+                        if (i == 0) acc[c] = t;
+                        else {
+                            acc[c].x = acc[c].x + t.x; acc[c].y = acc[c].y + t.y;
+                            acc[c].z = acc[c].z + t.z; acc[c].w = acc[c].w + t.w;
+                        }
+                        if (sr.d_msg && ok[c]) reinterpret_cast<float4*>(sr.d_msg + i * sr.ldmsg)[gi[c]] = m;
+                        if (sr.d_shift_out && ok[c])
+                            reinterpret_cast<float4*>(sr.d_shift_out + i * sr.ldout)[gi[c]] =
+                                make_float4(hv[c].x + sr.shift_alpha * e[c].x, hv[c].y + sr.shift_alpha * e[c].y,
+                                            hv[c].z + sr.shift_alpha * e[c].z, hv[c].w + sr.shift_alpha * e[c].w);
+                    }
+                    if (i + PF < n) {
+                        const float4* pa = reinterpret_cast<const float4*>(sr.d_a + (i + PF) * sr.lda);
+                        const float4* pb = reinterpret_cast<const float4*>(sr.d_b + (i + PF) * sr.ldb);
+#pragma unroll
+                        for (int c = 0; c < COLS; ++c) {
+                            ra[p][c] = ok[c] ? ld_row4(pa + gi[c]) : zero4;
+                            rb[p][c] = ok[c] ? ld_row4(pb + gi[c]) : zero4;
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < COLS; ++c)
+            if (ok[c])
+                reinterpret_cast<float4*>(out)[gi[c]] =
+                    make_float4(acc[c].x / wt, acc[c].y / wt, acc[c].z / wt, acc[c].w / wt);
+    }
+}
+
+// the same fold one element at a time: unaligned rows, a leading dimension that is no multiple of
+// 4, and the d % 4 tail of the vector launch
+template <class Op>
+__global__ __launch_bounds__(256) void k_ew_shift_accum_scalar(flc_shift_rows sr, int64_t n, int64_t j0, int64_t d, Op op,
+                                                               const float* __restrict__ levels, int s,
+                                                               const float* __restrict__ w, float wt, float* out) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem_tab[];
+    if (Op::TABLE) op.set_table_ok(load_table(levels, s, smem_tab));
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t j = j0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < d; j += stride) {
+        const uint32_t cs = op.col(j);
+        float acc = 0.f;
+        for (int64_t i = 0; i < n; ++i) {
+            op.setup(i);
+            const float bs = sr.d_base ? sr.d_base[i * sr.ldbase + j] : 0.f;
+            const float hv = sr.d_shift_out ? sr.d_shift_in[i * sr.ldin + j] : 0.f;
+            const float e = op.template apply<false>(sr.d_a[i * sr.lda + j] - sr.d_b[i * sr.ldb + j], j, cs, smem_tab);
+            const float t = e * sr.msg_scale;
+            const float m = sr.d_base ? bs + t : t;
+            const float wm = w ? w[i] * m : m;
+            acc = (i == 0) ? wm : acc + wm;
+            if (sr.d_msg) sr.d_msg[i * sr.ldmsg + j] = m;
+            if (sr.d_shift_out) sr.d_shift_out[i * sr.ldout + j] = hv + sr.shift_alpha * e;
+        }
+        out[j] = acc / wt;
+    }
+}
+
 // device-RNG row keys (natural codec; dithering gets them from k_norm_final)
 __global__ void k_row_keys(int64_t n, uint64_t seed, int64_t client0, uint32_t* __restrict__ rk) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
@@ -639,6 +794,45 @@ static int launch_accum(RowSrc src, bool vec, int64_t n, int64_t d, Op op, const
     return FLC_OK;
 }
 
+// The shifted fold: the vector launch needs every operand in use 16-byte aligned with a leading
+// dimension that is a multiple of 4 (a shared base has none); one profile record per call.
+template <class Op>
+static int launch_shift_accum(const flc_shift_rows& sr, int64_t n, int64_t d, Op op, const float* levels, int s,
+                              const float* w, float wt, float* out, hipStream_t st) {
+    if (d == 0) return FLC_OK;
+    const size_t lds = Op::TABLE ? (size_t)s * sizeof(float4) : 0;
+    uintptr_t pal = (uintptr_t)sr.d_a | (uintptr_t)sr.d_b | (uintptr_t)out;   // pointers: low 4 bits clear
+    uint64_t lal = (uint64_t)sr.lda | (uint64_t)sr.ldb;                       // leading dimensions: low 2
+    if (sr.d_base) { pal |= (uintptr_t)sr.d_base; lal |= (uint64_t)sr.ldbase; }
+    if (sr.d_msg) { pal |= (uintptr_t)sr.d_msg; lal |= (uint64_t)sr.ldmsg; }
+    if (sr.d_shift_out) {
+        pal |= (uintptr_t)sr.d_shift_in | (uintptr_t)sr.d_shift_out;
+        lal |= (uint64_t)sr.ldin | (uint64_t)sr.ldout;
+    }
+    const bool vec = (pal & 15u) == 0 && (lal & 3u) == 0;
+    int base_mode = BASE_NONE;
+    if (sr.d_base) base_mode = sr.ldbase == 0 ? BASE_SHARED : (sr.d_base == sr.d_b && sr.ldbase == sr.ldb) ? BASE_B : BASE_ROWS;
+    const int hin_b = sr.d_shift_out && sr.d_shift_in == sr.d_b && sr.ldin == sr.ldb;
+    ProfScope _ps("k_ew_shift_accum", st);
+    int64_t j0 = 0;
+    if (vec && d / 4 > 0) {
+        const int grid = grid_cap(d / 4, 256 * FLC_SHIFT_COLS, 1 << 20);
+        if (w) hipLaunchKernelGGL((k_ew_shift_accum<Op, FLC_SHIFT_COLS, FLC_SHIFT_PF, true>), dim3(grid), dim3(256), lds, st, sr, base_mode, hin_b,
+                                  n, d, op, levels, s, w, wt, out);
+        else hipLaunchKernelGGL((k_ew_shift_accum<Op, FLC_SHIFT_COLS, FLC_SHIFT_PF, false>), dim3(grid), dim3(256), lds, st, sr, base_mode, hin_b,
+                                n, d, op, levels, s, w, wt, out);
+        FLC_CHECK_LAUNCH("k_ew_shift_accum");
+        j0 = (d / 4) * 4;
+    }
+    if (j0 < d) {
+        const int grid = grid_cap(d - j0, 256, 4096);
+        hipLaunchKernelGGL((k_ew_shift_accum_scalar<Op>), dim3(grid), dim3(256), lds, st, sr, n, j0, d, op, levels, s, w,
+                           wt, out);
+        FLC_CHECK_LAUNCH("k_ew_shift_accum_scalar");
+    }
+    return FLC_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // Entry points used by api.hip
 // ------------------------------------------------------------------------------------------
@@ -671,6 +865,14 @@ static bool lone_sparse(const flc_codec_params* prm) { return (prm->flags & FLC_
 static bool torch_norm_mode(const flc_codec_params* prm, int norm_mode) {
     return norm_mode == FLC_NORMMODE_TORCH_CPU && prm->norm == FLC_NORM_L2 &&
            (prm->codec == FLC_STD_DITHERING || prm->codec == FLC_NAT_DITHERING);
+}
+
+// the shifted fold: the per-row tables and the norm partials of the dense two-pass form
+size_t ew_shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (prm->codec == FLC_IDENT || prm->codec == FLC_LAZY) return 0;
+    size_t b = 0;
+    carve_ew(nullptr, n, d, &b);
+    return b;
 }
 
 size_t ew_workspace(const flc_codec_params* prm, int64_t n, int64_t d, bool norms_given, int norm_mode) {
@@ -713,7 +915,7 @@ static int launch_lone_dither(const flc_codec_params* prm, const UniformSrc& us,
         constexpr int NK = decltype(nk)::value;
         constexpr bool CM = decltype(cm)::value;
         { ProfScope _ps("k_norm_partials", st);
-        hipLaunchKernelGGL((k_norm_partials<NK, true, false, (bool)FLC_LONE_KEEP>), pg, dim3(256), 0, st, src, nullptr, d, parts, LONE_PLEN,
+        hipLaunchKernelGGL((k_norm_partials<NK, true, false, (bool)FLC_LONE_KEEP>), pg, dim3(256), 0, st, src, RowSrc{nullptr, 0, nullptr}, d, parts, LONE_PLEN,
                            e.partial, e.tinyp); }
         FLC_CHECK_LAUNCH("k_norm_partials");
         DitherOp<false, CM> op;
@@ -741,13 +943,18 @@ static int launch_lone_dither(const flc_codec_params* prm, const UniformSrc& us,
 // One row encode (compressVector) or fused reduce over n rows (n >= 1).
 int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool vec, int64_t n, int64_t d,
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt,
-           void* ws, size_t ws_bytes, hipStream_t st, const ShiftArgs* sh, const CodeArgs* ca, int norm_mode) {
+           void* ws, size_t ws_bytes, hipStream_t st, const ShiftArgs* sh, const CodeArgs* ca, int norm_mode,
+           const flc_shift_rows* sr) {
+    // sr: the shifted fold over n rows (flc_encode_shift_reduce): src holds the a rows, the dense
+    // two-pass form only (the sparse QSGD pass reads plain rows, not differences)
+    if (sr && (dense || sh || ca || pnorm_in || norm_mode != FLC_NORMMODE_EXACT)) { set_error("ew_run: the shifted fold takes no other form"); return FLC_ERR_ARG; }
     if ((sh || ca) && (!dense || n != 1)) { set_error("ew_run: the shift / code forms are one dense row"); return FLC_ERR_ARG; }
     const int codec = prm->codec;
     const bool compat = pat && pat->d_uniforms;
     const int64_t client0 = pat ? pat->client0 : 0;
     UniformSrc us{compat ? pat->d_uniforms : nullptr, (pat && pat->uniforms_ld) ? pat->uniforms_ld : d};
     auto go = [&](auto op, const float* levels, int s) -> int {
+        if (sr) return launch_shift_accum(*sr, n, d, op, levels, s, w, wt, out, st);
         if (sh) return launch_shift(src.base, d, op, levels, s, *sh, st);
         if (ca) return launch_code(src.base, d, op, levels, s, *ca, st);
         if (dense) return launch_dense(src.base, d, op, levels, s, out, st);
@@ -756,7 +963,7 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
     const bool tn = torch_norm_mode(prm, norm_mode);
     // (given norms and the torch-order mode included: a row whose norm is outside its sampled
     // bounds is folded dense there)
-    if (!dense && n > 1 && ds_eligible(prm, pat, n, d))
+    if (!sr && !dense && n > 1 && ds_eligible(prm, pat, n, d))
         return ds_run(prm, pat, src, n, d, w, wt, pnorm_out, out, ws, ws_bytes, st, pnorm_in,
                       tn ? FLC_NORMMODE_TORCH_CPU : FLC_NORMMODE_EXACT);
     // a lone compressVector row on the single-read sparse pass, when the caller forces it (the fold
@@ -765,7 +972,7 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
     // draws; the one-row fold walks every tile of the row), profiles/r04/lone_ab.txt
     if (lone_sparse(prm) && dense && !sh && !ca && !pnorm_in && n == 1 && ds_eligible(prm, pat, 1, d))
         return ds_run(prm, pat, src, 1, d, nullptr, 1.f, pnorm_out, out, ws, ws_bytes, st);
-    if (ws_bytes < ew_workspace(prm, n, d, pnorm_in != nullptr, norm_mode)) { set_error("codec workspace too small"); return FLC_ERR_WORKSPACE; }
+    if (ws_bytes < (sr ? ew_shift_reduce_workspace(prm, n, d) : ew_workspace(prm, n, d, pnorm_in != nullptr, norm_mode))) { set_error("codec workspace too small"); return FLC_ERR_WORKSPACE; }
     size_t ew_bytes = 0;
     EwWs e = carve_ew(ws, n, d, &ew_bytes);
     switch (codec) {
@@ -804,8 +1011,10 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
                 return launch_lone_dither(prm, us, compat, src.base, d, e, pnorm_out, out, client0, st);
             RowTabs rt{pnorm_in, nullptr, nullptr, e.rk};
             if (!pnorm_in) {
+                // the shift forms take the norm of a_i - b_i (one row, or the shifted fold's n rows)
+                const RowSrc subs{sr ? sr->d_b : sh ? sh->b : nullptr, sr ? sr->ldb : d, nullptr};
                 rc = launch_norms(src, vec, n, d, prm->norm, e.partial, e.tinyp, e.pn, e.rpn, e.fast, prm->seed,
-                                  client0, e.rk, st, sh ? sh->b : nullptr);
+                                  client0, e.rk, st, (sr || sh) ? &subs : nullptr);
                 if (rc) return rc;
                 rt = RowTabs{e.pn, e.rpn, e.fast, e.rk};
             } else if (!compat) {

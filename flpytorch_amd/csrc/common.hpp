@@ -139,8 +139,14 @@ struct CodeArgs {
 int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool vec, int64_t n, int64_t d,
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt, void* ws,
            size_t ws_bytes, hipStream_t st, const ShiftArgs* sh = nullptr, const CodeArgs* ca = nullptr,
-           int norm_mode = FLC_NORMMODE_EXACT);
+           int norm_mode = FLC_NORMMODE_EXACT, const flc_shift_rows* sr = nullptr);
+size_t ew_shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 size_t shift_workspace(const flc_codec_params* prm, int64_t d);
+// the shifted fold over n rows (flc_encode_shift_reduce): the elementwise codecs in one tile-owner
+// pass (codecs.hip k_ew_shift_accum), RandK / TopK / Rank-K row by row (shift.hip)
+size_t shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
+int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
+                     const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st);
 int encode_row(const flc_codec_params* prm, const flc_pattern* pat, const float* d_x, int64_t d,
                const float* d_pnorm_in, float* d_pnorm_out, float* d_out, void* d_ws, size_t ws_bytes, hipStream_t st);
 size_t encode_row_workspace(const flc_codec_params* prm, int64_t d);

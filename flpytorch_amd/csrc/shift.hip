@@ -98,4 +98,67 @@ int shift_run(const flc_codec_params* prm, const flc_pattern* pat, const float* 
     return FLC_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// The shifted fold over n rows (flc_encode_shift_reduce).  Elementwise codecs: one tile-owner pass
+// (codecs.hip k_ew_shift_accum).  RandK / TopK / Rank-K: the rows in order through shift_run into
+// a message row (the workspace's, or the caller's d_msg row i), each followed by one fold step
+// into d_out — acc = first ? w m : acc + w m, divided after the last row.  Correct and bounded in
+// workspace, not a fast path (n selections, 2 n small launches; a list-based fold is future work).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_shift_fold(const float* __restrict__ m, int64_t d, const float* __restrict__ w,
+                                                    int64_t i, int last, float wt, float* __restrict__ acc) {
+    const float wi = w ? w[i] : 1.f;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < d; j += (int64_t)gridDim.x * blockDim.x) {
+        const float t = w ? wi * m[j] : m[j];
+        float a = (i == 0) ? t : acc[j] + t;
+        if (last) a = a / wt;
+        acc[j] = a;
+    }
+}
+
+size_t shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (shift_elementwise(prm->codec)) return ew_shift_reduce_workspace(prm, n, d);
+    Carver c(nullptr);
+    c.take<float>((size_t)d);
+    c.take<char>(shift_workspace(prm, d));
+    return c.bytes();
+}
+
+int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
+                     const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (n == 0 || d == 0) return FLC_OK;
+    if (ws_bytes < shift_reduce_workspace(prm, n, d)) { set_error("flc_encode_shift_reduce: workspace too small"); return FLC_ERR_WORKSPACE; }
+    if (shift_elementwise(prm->codec)) {
+        const bool vec = ((((uintptr_t)sr.d_a | (uintptr_t)sr.d_b) & 15u) == 0) && (((sr.lda | sr.ldb) & 3) == 0);
+        RowSrc a{sr.d_a, sr.lda, nullptr};
+        return ew_run(prm, pat, a, vec, n, d, nullptr, pnorms_out, /*dense=*/false, out, w, wt, ws, ws_bytes, st, nullptr,
+                      nullptr, FLC_NORMMODE_EXACT, &sr);
+    }
+    if (prm->codec == FLC_RANDK && !(pat && pat->d_randk_idx) && prm->k > d) { set_error("randk: K > D"); return FLC_ERR_ARG; }
+    Carver c(ws);
+    float* mrow = c.take<float>((size_t)d);
+    const size_t inner = shift_workspace(prm, d);
+    void* iws = c.take<char>(inner);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((d + 255) / 256, 8192));
+    for (int64_t i = 0; i < n; ++i) {
+        flc_pattern pi;
+        memset(&pi, 0, sizeof(pi));
+        if (pat) {
+            pi = *pat;
+            if (pat->d_randk_idx) pi.d_randk_idx = pat->d_randk_idx + i * (pat->idx_ld ? pat->idx_ld : prm->k);
+            if (pat->d_uniforms) pi.d_uniforms = pat->d_uniforms + i * (pat->uniforms_ld ? pat->uniforms_ld : d);
+            if (pat->d_lazy_u) pi.d_lazy_u = pat->d_lazy_u + i;
+            pi.d_randk_counts = nullptr;        // (laid out [chunk][n]: one row's are computed inside)
+        }
+        pi.client0 = (pat ? pat->client0 : 0) + i;
+        float* m = sr.d_msg ? sr.d_msg + i * sr.ldmsg : mrow;
+        ShiftArgs sh{sr.d_b + i * sr.ldb, sr.msg_scale, sr.d_base ? sr.d_base + i * sr.ldbase : nullptr, m, sr.shift_alpha,
+                     sr.d_shift_out ? sr.d_shift_in + i * sr.ldin : nullptr, sr.d_shift_out ? sr.d_shift_out + i * sr.ldout : nullptr};
+        if (int rc = shift_run(prm, &pi, sr.d_a + i * sr.lda, d, sh, nullptr, iws, inner, st)) return rc;
+        hipLaunchKernelGGL(k_shift_fold, dim3(grid), dim3(256), 0, st, m, d, w, i, i == n - 1 ? 1 : 0, wt, out);
+        FLC_CHECK_LAUNCH("k_shift_fold");
+    }
+    return FLC_OK;
+}
+
 }  // namespace flc

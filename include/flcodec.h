@@ -221,6 +221,59 @@ int flc_encode_shift(const flc_codec_params* prm, const flc_pattern* pat, const 
                      float* d_pnorm_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Fused shifted uplink — a DIANA / EF21 / MARINA / FRECON / COFIG round of n resident clients in
+ * one call (additive: flc_version() stays 104, detect the entry by its symbol):
+ *     msg_i  = base_i + C_i(a_i - b_i) * msg_scale          (without a base: C_i(a_i - b_i) * msg_scale)
+ *     h_i'   = shift_in_i + shift_alpha * C_i(a_i - b_i)    (when d_shift_out is given)
+ *     d_out  = (sum_i w_i * msg_i) / w_total
+ * Row i of an operand is at ptr + i * ld (elements).  msg_i and h_i' are exactly the bits
+ * flc_encode_shift gives for (a_i, b_i, base_i, shift_in_i) under pattern row i (d_uniforms +
+ * i * uniforms_ld, d_randk_idx + i * idx_ld, d_lazy_u[i]) and client client0 + i; d_out is folded
+ * in row order with fp32 rounding per operation, the first term assigned, d_w == NULL meaning no
+ * multiply: flc_reduce_matrix(FLC_REDUCE_PLAIN) over the stored messages, without storing them.
+ * Dithering uses the exactly rounded norm of a_i - b_i, as flc_encode_shift does (no
+ * FLC_NORMMODE_TORCH_CPU for shifted steps); d_pnorms_out: optional [n] norms used.
+ *   DIANA  a = g, b = shift_in = shift_out = h rows (in place), msg_scale 1, no base, no d_msg
+ *   EF21   a = g, b = base = d_msg = g_prev rows (in place), msg_scale = mult
+ *   MARINA a = g_cur, b = previous gradients, base = g_prev: ONE shared [d] vector (ldbase == 0)
+ * Aliasing: row i of d_msg / d_shift_out may be row i of d_b, d_base or d_shift_in (same pointer and
+ * leading dimension); any other overlap of an output with an operand is the caller's error.
+ *
+ * Elementwise codecs (ident, lazy, natural, standard / natural dithering): ONE pass — a_i and b_i
+ * read once (after the norm pass over a_i - b_i for dithering), h_i' / msg_i written once, the sum
+ * kept in registers: 12 n d bytes for an in-place DIANA round (20 n d with the norm pass) against
+ * 20 / 28 n d for n flc_encode_shift calls and a fold of their stored messages.  The vector path
+ * needs every operand 16-byte aligned with ld % 4 == 0; anything else runs the scalar kernel
+ * (same bits).
+ * RandK / TopK / Rank-K select or factor the whole difference: their rows run in order through
+ * flc_encode_shift's path into a workspace row (or d_msg row i), each followed by a fold step into
+ * d_out.  Correct and bounded in workspace (one message row + flc_encode_shift's own), NOT a fast
+ * path: n selection passes and 2 n small launches.  d_randk_counts is ignored there.
+ *
+ * Checked before any launch — FLC_ERR_ARG: null rows / d_a / d_b / d_out with n * d > 0,
+ * n > FLC_MAX_ROWS, d_shift_out without d_shift_in, an output operand whose rows overlap
+ * (|ld| < d, n > 1), d_msg or d_shift_out overlapping a shared base (the fold always consumes a
+ * base, so "base without a consumer" cannot occur here); FLC_ERR_WORKSPACE: ws_bytes below
+ * flc_encode_shift_reduce_workspace_size; FLC_ERR_UNSUPPORTED: unknown codec.  n == 0 or d == 0:
+ * FLC_OK, the device is not touched (no clients: d_out is the caller's to zero).
+ * -------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* d_a;    int64_t lda;     /* [n] rows a_i (local gradients) */
+    const float* d_b;    int64_t ldb;     /* [n] rows b_i (shift h_i / g_prev_i / previous gradient) */
+    const float* d_base; int64_t ldbase;  /* NULL; or [n] rows; or ldbase == 0: ONE shared [d] vector (MARINA's g_prev) */
+    float msg_scale;
+    float* d_msg;        int64_t ldmsg;   /* NULL: messages are not stored; else [n] rows (EF21's g_next, may be d_b/d_base rows) */
+    float shift_alpha;
+    const float* d_shift_in; int64_t ldin;   /* NULL or [n] rows */
+    float* d_shift_out;      int64_t ldout;  /* NULL or [n] rows (may be the d_shift_in / d_b rows: in place) */
+} flc_shift_rows;
+
+size_t flc_encode_shift_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_encode_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
+                            int64_t n, int64_t d, const float* d_w, float w_total, float* d_pnorms_out,
+                            float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * Wire format: the message a client sends, and the server's decode +
  * reduce straight from the N messages.  The reference counts these bits
  * (last_need_to_send_advance, compressors.py:223-224, 367-368) but moves the dense decoded
@@ -349,7 +402,8 @@ int flc_selftest_division(const float* d_divisors, int n, unsigned long long* d_
  * bracketed by hipEvents recorded on the launch stream; flc_profile_collect() waits for them
  * and returns the summed duration and launch count for one kernel name, then forgets them.
  * Names: k_topk_filter, k_topk_sample, k_radix_hist, k_chunk_accum, k_ew_accum_vec,
- * k_norm_partials, k_reduce_vec, k_randk_scatter; the TopK filter's variant is recorded too
+ * k_norm_partials, k_reduce_vec, k_randk_scatter, k_ew_shift (flc_encode_shift's elementwise pass),
+ * k_ew_shift_accum (flc_encode_shift_reduce's: one record per call); the TopK filter's variant is recorded too
  * (k_topk_filter_g4: 4-chunk work items, the many-row path of large launches; k_topk_filter_g2:
  * 2-chunk items), so a test can assert which one ran.
  * -------------------------------------------------------------------------------------- */

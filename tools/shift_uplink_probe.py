@@ -1,0 +1,169 @@
+#!/usr/bin/env python3
+"""Price of a shifted round (DIANA in place) three ways, in ONE process on ONE allocation (GPU box).
+
+Per codec, interleaved repeat by repeat (as tools/ab_inproc.py does: the rows' placement moves a
+step by up to ~10 % between allocations, so the variants share one):
+
+  fused        ShiftUplinkReducer(G, H, alpha, shift = shift_out = H)       flc_encode_shift_reduce
+  composition  N x compressShift(G_i, H_i) into stored message rows, then reduce_rows over them — what
+               the library offered before the fused call
+  yardstick    UplinkReducer's dense fold of the same codec over the G rows alone: the read-only
+               tile-owner pass (k_ew_accum_vec) the fused kernel is modelled on
+
+fused and composition start from equal shifts and update their own copy, so after every repeat
+their outputs and shifts must agree bit for bit (checked).  Algorithmic bytes: fused 12 N D + 4 D
+(natural: read G and H, write H) or 20 N D + 4 D (dithering: the norm pass reads G and H once
+more); composition 20 / 28 N D + 4 D (the message rows written and read back); yardstick 4 / 8 N D
++ 4 D.  A last pass with the library's kernel timers on gives the kernels' own times.
+
+usage: python tools/shift_uplink_probe.py [--specs natural,qsgd:127] [--n 128] [--d 25000000]
+           [--repeats 5] [--steps 2] [--out-dir profiles/r09/shift_uplink] [--fused-libs tagA,tagB]
+--fused-libs: A/B builds of the library (abvar/libflcodec_<tag>.so, tools/ab_build.sh) whose fused
+call is timed in the same rounds as "fused@<tag>" ON THE SAME shift matrix as "fused" (a matrix of
+their own reads up to ~10 % differently: placement).  A timing-only mode: the shifts then take several
+updates per repeat, so the bit check against the composition is off.
+Writes <out-dir>/<spec>.jsonl: one line per (repeat, variant) and a summary line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SEED = 20241015
+
+
+def byte_model(spec, n, d):
+    dither = not spec.startswith("natural")
+    return {"fused": (20 if dither else 12) * n * d + 4 * d,
+            "composition": (28 if dither else 20) * n * d + 4 * d,
+            "yardstick": (8 if dither else 4) * n * d + 4 * d}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--specs", default="natural,qsgd:127")
+    ap.add_argument("--n", type=int, default=128)
+    ap.add_argument("--d", type=int, default=25_000_000)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "r09", "shift_uplink"))
+    ap.add_argument("--fused-libs", default="")
+    a = ap.parse_args()
+    if a.repeats < 1 or a.steps < 1 or a.n < 1 or a.d < 1:
+        ap.error("--repeats, --steps, --n and --d are positive")
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d = a.n, a.d
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev).manual_seed(1000)
+
+    def filled():
+        t = torch.empty((n, d), dtype=torch.float32, device=dev)
+        for i in range(0, n, 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    G, H0 = filled(), filled()
+    Hf, Hc, M = torch.empty_like(H0), torch.empty_like(H0), torch.empty_like(H0)
+    outs = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in ("fused", "composition", "yardstick")}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    extra = {t: _lib.open_variant(t) for t in a.fused_libs.split(",") if t}
+    for spec in a.specs.split(","):
+        comp_f, comp_c, comp_y = (ag.initCompressor(spec, d) for _ in range(3))
+        if spec.startswith("qsgd") or spec.startswith("std.dithering"):
+            comp_y.dither_path = "dense"               # the two-pass dense fold, not the sparse QSGD path
+        alpha = 1.0 / (1.0 + comp_f.getW())
+        fused = ag.ShiftUplinkReducer(comp_f, device=dev, seed=SEED)
+        yard = ag.UplinkReducer(comp_y, device=dev, seed=SEED)
+        Hf.copy_(H0)
+        Hc.copy_(H0)
+
+        def run_fused():
+            fused(G, Hf, alpha=alpha, shift=Hf, shift_out=Hf, out=outs["fused"])
+
+        def run_composition():
+            for i in range(n):
+                comp_c.device_rng = (SEED, i)
+                comp_c.compressShift(G[i], Hc[i], out=M[i], alpha=alpha, shift=Hc[i], shift_out=Hc[i])
+            ag.reduce_rows(outs["composition"], M, relative=False, out=outs["composition"])
+
+        def run_yardstick():
+            yard(G, out=outs["yardstick"])
+        runs = {"fused": run_fused, "composition": run_composition, "yardstick": run_yardstick}
+        model = byte_model(spec, n, d)
+
+        def run_variant(lib):
+            def f():
+                with _lib.use(lib):
+                    fused(G, Hf, alpha=alpha, shift=Hf, shift_out=Hf, out=outs["fused"])
+            return f
+        for t, lib in extra.items():
+            runs["fused@" + t] = run_variant(lib)
+            model["fused@" + t] = model["fused"]
+        for f in runs.values():                        # warm: code objects, workspaces
+            f()
+        torch.cuda.synchronize()
+
+        def agree():
+            return bool(extra) or (torch.equal(outs["fused"].view(torch.int32), outs["composition"].view(torch.int32))
+                    and torch.equal(Hf.view(torch.int32), Hc.view(torch.int32)))
+        if not agree():
+            raise SystemExit(f"{spec}: fused and composition differ after the warm-up round")
+        ms = {v: [] for v in runs}
+        path = os.path.join(a.out_dir, spec.replace(":", "_").replace(".", "_") + ".jsonl")
+        with open(path, "w") as fh:
+            def emit(rec):
+                line = json.dumps(rec)
+                fh.write(line + "\n")
+                fh.flush()
+                print(line, flush=True)
+            for r in range(a.repeats):
+                for v, f in runs.items():
+                    e0.record()
+                    for _ in range(a.steps):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    t = e0.elapsed_time(e1) / a.steps
+                    ms[v].append(t)
+                    emit({"spec": spec, "n": n, "d": d, "repeat": r, "variant": v, "ms_per_call": round(t, 4),
+                          "algorithmic_bytes": model[v], "GBps": round(model[v] / t / 1e6, 1)})
+                if not agree():
+                    raise SystemExit(f"{spec}: fused and composition differ after repeat {r}")
+            # the kernels' own times (the library's event timers), one call each, outside the timed repeats
+            kernels = ("k_ew_shift_accum", "k_norm_partials", "k_ew_accum_vec", "k_ew_shift", "k_reduce_vec")
+            kms = {}
+            for v, f in runs.items():
+                _lib.profile_enable(True)
+                for k in kernels:
+                    _lib.profile_collect(k)
+                f()
+                torch.cuda.synchronize()
+                _lib.profile_enable(False)
+                kms[v] = {k: round(t, 4) for k in kernels for t, c in [_lib.profile_collect(k)] if c}
+            med = {v: statistics.median(ms[v]) for v in runs}
+            emit({"spec": spec, "n": n, "d": d, "summary": True, "repeats": a.repeats, "steps": a.steps,
+                  "median_ms": {v: round(med[v], 4) for v in runs},
+                  "min_ms": {v: round(min(ms[v]), 4) for v in runs},
+                  "max_ms": {v: round(max(ms[v]), 4) for v in runs},
+                  "algorithmic_bytes": model,
+                  "GBps_at_median": {v: round(model[v] / med[v] / 1e6, 1) for v in runs},
+                  "composition_over_fused": round(med["composition"] / med["fused"], 3),
+                  "fused_over_yardstick": round(med["fused"] / med["yardstick"], 3),
+                  "byte_model_composition_over_fused": round(model["composition"] / model["fused"], 3),
+                  "fused_faster_beyond_spread": max(ms["fused"]) < min(ms["composition"]),
+                  "bits_equal_every_repeat": not extra,
+                  "kernel_ms_one_call": kms})
+        print("wrote", path, flush=True)
+
+
+if __name__ == "__main__":
+    main()
