@@ -226,7 +226,16 @@ class ShiftUplinkReducer:
     (k_ew_shift_accum, after one norm pass over the differences for dithering); RandK / TopK /
     Rank-K run their rows in order with a fold step each (correct, not a fast path).  Dithering
     encodes with the exactly rounded norm of a_i - b_i, like ``compressShift``: the compressor's
-    ``norm_mode = "torch_cpu"`` does not apply to shifted steps."""
+    ``norm_mode = "torch_cpu"`` does not apply to shifted steps.
+
+    ``sparse=True`` (RandK only) runs the round through ``flc_randk_shift_reduce``: work
+    proportional to N K, not N D.  It takes the in-place DIANA shape (``shift is shift_out is b``,
+    no base / msg_out), the in-place EF21 shape (``base is msg_out is b``), MARINA's shared [D]
+    base, and the plain fold of C(a - b); anything else raises ``NotImplementedError``.  Elements
+    of the in-place operand OUTSIDE a row's index set are not written (the general entry stores
+    ``x + 0`` there: the same bits except that a stored -0 becomes +0); selected elements and
+    ``out`` carry the general entry's bits whenever the operand holds no -0 at an unselected
+    place."""
 
     def __init__(self, compressor: Compressor, device=None, seed=None):
         _lib.require_gpu()
@@ -240,13 +249,18 @@ class ShiftUplinkReducer:
             prm.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
         return prm, keep
 
-    def workspace_bytes(self, n, d):
+    def workspace_bytes(self, n, d, sparse=False, compat=False):
+        """``sparse``: flc_randk_shift_reduce's workspace (``compat``: with numpy-stream index rows)."""
         prm, _ = self.params()
+        if sparse:
+            pat = _lib.FlcPattern()
+            pat.d_randk_idx = 1 if compat else None             # (the size query only tells the modes apart)
+            return _lib.load().flc_randk_shift_reduce_workspace_size(ctypes.byref(prm), ctypes.byref(pat), n, d)
         return _lib.load().flc_encode_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
 
     def __call__(self, a, b, *, scale=1.0, base=None, msg_out=None, alpha=None, shift=None, shift_out=None, out=None,
                  weights=None, divisor=None, client0=0, randk_idx=None, uniforms=None, lazy_u=None, pnorms_out=None,
-                 stream=None):
+                 stream=None, sparse=False, randk_counts=None):
         """a, b: [N, D] fp32 row-contiguous device matrices (local gradients; shifts / previous
         estimators / previous gradients).  ``base``: None, [N, D], or ONE [D] vector for every row
         (MARINA's g_prev).  ``msg_out``: None (the messages are not stored) or [N, D]; it may be ``b``
@@ -256,9 +270,16 @@ class ShiftUplinkReducer:
         back to the host once for the wire statistics.  Returns ``(out, msg_out, shift_out)``.  The
         compressor's wire statistics advance as N consecutive ``compressShift`` calls would leave them.
         The vector kernel needs every operand 16-byte aligned with a row stride that is a multiple
-        of 4; anything else runs the scalar kernel (same bits)."""
+        of 4; anything else runs the scalar kernel (same bits).  ``sparse=True``: the class docstring's
+        RandK round (``NotImplementedError`` when the library refuses the codec or the shape — no
+        silent fallback; ``pnorms_out`` is a ``ValueError``); ``randk_counts``: its device draws' chunk
+        counts from ``UplinkReducer.randk_counts(n, d, client0)`` with the same seed, as in ``UplinkReducer``."""
+        if sparse and pnorms_out is not None:
+            raise ValueError("ShiftUplinkReducer: pnorms_out is not available with sparse=True (RandK uses no norm)")
+        if randk_counts is not None and not sparse:
+            raise ValueError("ShiftUplinkReducer: randk_counts is read by the sparse round only (sparse=True)")
         args = (a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx, uniforms,
-                lazy_u, pnorms_out)
+                lazy_u, pnorms_out, sparse, randk_counts)
         if stream is not None:
             if stream.device != self.device:
                 raise ValueError(f"stream is on {stream.device}, the reducer runs on {self.device}")
@@ -267,10 +288,14 @@ class ShiftUplinkReducer:
         return self._run(*args)
 
     def _run(self, a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx,
-             uniforms, lazy_u, pnorms_out):
+             uniforms, lazy_u, pnorms_out, sparse=False, randk_counts=None):
         lib = _lib.load()
         if not hasattr(lib, "flc_encode_shift_reduce"):
             raise NotImplementedError("this library build has no flc_encode_shift_reduce")
+        if sparse and not hasattr(lib, "flc_randk_shift_reduce"):
+            raise NotImplementedError("this library build has no flc_randk_shift_reduce")
+        if sparse and alpha is not None and shift_out is None:
+            raise NotImplementedError("ShiftUplinkReducer: sparse=True updates the shift in place (shift_out = shift = b)")
         dev = self.device
         for name, v in (("a", a), ("b", b), ("base", base), ("msg_out", msg_out), ("shift", shift),
                         ("shift_out", shift_out), ("out", out)):
@@ -356,7 +381,19 @@ class ShiftUplinkReducer:
             w_ptr = wt.data_ptr()
         if divisor is not None:
             total = float(divisor)
-        if d > 0:
+        if randk_counts is not None and randk_idx is None:      # device draws: UplinkReducer.randk_counts(n, d, client0)
+            if tuple(randk_counts.shape) != ((d + 4095) // 4096, n) or not randk_counts.is_cuda:
+                raise ValueError("randk_counts must be a [ceil(d / 4096), n] device tensor")
+            pat.d_randk_counts = randk_counts.data_ptr()
+        if d > 0 and sparse:
+            ws = _lib.WORKSPACE.get(dev, lib.flc_randk_shift_reduce_workspace_size(ctypes.byref(prm), ctypes.byref(pat), n, d))
+            with torch.cuda.device(dev):
+                rc = lib.flc_randk_shift_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.byref(sr), n, d,
+                                                ctypes.c_void_p(w_ptr), ctypes.c_float(total),
+                                                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                                ws.numel(), _lib.stream_ptr(dev))
+            _lib.check(rc, "flc_randk_shift_reduce")          # (a refusal: NotImplementedError with the reason)
+        elif d > 0:
             ws = _lib.WORKSPACE.get(dev, lib.flc_encode_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
             with torch.cuda.device(dev):
                 rc = lib.flc_encode_shift_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.byref(sr), n, d,

@@ -209,6 +209,27 @@ int rk_run(const flc_codec_params* prm, RowSrc rows, int64_t n, int64_t d, bool 
 size_t randk_device_workspace(int64_t n, int64_t d);
 int randk_device_counts(uint64_t seed, int64_t client0, int64_t n, int64_t d, int64_t k, uint32_t* cnt, void* ws,
                         size_t ws_bytes, hipStream_t st);
+// chunk counts [C][n] (the pattern's d_randk_counts or computed) and client keys [n] of a device-draw
+// fold; wsp: randk_device_workspace(n, d) bytes
+int randk_device_prepare(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, void* wsp,
+                         const uint32_t** cnt, const uint64_t** ckey, hipStream_t st);
+// The compat RandK lists by themselves: row r's entries of chunk c are idx / val[r * cap + tab[c * n + r].x + t],
+// t < tab[c * n + r].y (element index within the row; randk_scale * rows[r][idx]).  A caller may
+// rewrite val before randk_lists_fold (k_chunk_accum) folds the lists into out.
+struct RkLists {
+    const uint2* tab;
+    const uint32_t* idx;
+    float* val;
+    int64_t cap;
+};
+size_t randk_lists_workspace(int64_t n, int64_t d, int64_t K);
+int randk_lists_build(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d, void* wsp,
+                      RkLists* lists, hipStream_t st);
+int randk_lists_fold(int64_t n, int64_t d, int64_t K, void* wsp, const float* w, float wt, float* out, hipStream_t st);
+// the sparse in-place RandK shifted round (flc_randk_shift_reduce, randk_shift.hip)
+size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n, int64_t d);
+int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
+                    const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
 int randk_dense(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, float* out, void* ws,
                 size_t ws_bytes,
                 hipStream_t st);

@@ -1,0 +1,434 @@
+// The sparse in-place RandK shifted round (flc_randk_shift_reduce).
+//
+// RandK's index set does not depend on the data, so of a DIANA / EF21 / MARINA round
+//     v = a_i[j] - b_i[j];  e = randk_scale * v;  t = e * msg_scale;  m = base ? base[j] + t : t;
+//     h' = shift_in[j] + shift_alpha * e
+// only the K selected elements of a row are ever needed: nothing dense is formed, an in-place
+// operand is written at the row's K members only, and the work is proportional to N K (plus the
+// 128-B line granularity of the gathers), not to N D.  Every operation is rounded separately, in
+// the order above: a selected element and d_out carry flc_encode_shift_reduce's bits.
+//
+//   shape A  DIANA / FRECON / COFIG in place   shift_in == shift_out == b       h' stored, fold of t
+//   shape B  EF21 in place                     base == msg == b (rows)          m stored, then reduce_impl
+//   shape C  MARINA                            ONE shared base, nothing stored  fold of base + t
+//   shape D  C(a - b) fold                     nothing stored                   fold of t
+//
+// Device draws: k_randk_shift, k_randk_fold's walk (select.hip) with two gathers per member and an
+// epilogue — one wave per chunk (or 1/2, 1/4 of its columns), rows in order, AP rows' gathers in
+// flight.  The lane that loaded b_q[j] is the only one that stores to (q, j), and a row's members
+// are distinct, so in place is safe.  Shape C keeps the sum in registers (the LDS tile holds the
+// current row's t by column, +0 elsewhere): every column takes w_q * (base[j] + tile[j]) per row,
+// which is w_q * (base[j] + 0.0f * msg_scale) outside the row's set (msg_scale is finite and > 0).
+// Compat draws: the chunk-bucketed lists of select.hip (k_randk_coarse / k_randk_fine), their values
+// rewritten to t by k_randk_shift_lists (which also stores the in-place element), then k_chunk_accum
+// (A, D) or the list form of the shape C fold.  Shape B needs no lists.
+#include <algorithm>
+#include <cmath>
+
+#include "chunks.hpp"
+#include "randk_tree.hpp"
+
+namespace flc {
+
+enum { RKS_D = 0, RKS_A = 1, RKS_C = 2, RKS_B = 3 };
+
+struct RksArgs {
+    const float* a; int64_t lda;
+    float* b;       int64_t ldb;      // written at the members in shapes A (h') and B (m)
+    const float* base;                // shape C: the shared [d] vector
+    float scale;                      // randk_scale (D / K)
+    float ms;                         // msg_scale
+    float alpha;                      // shift_alpha
+};
+
+__device__ inline uint64_t rks_join64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | (uint64_t)lo; }
+
+struct RksMeta {           // lane = row of a 64-row batch
+    uint32_t m;            // members of this chunk
+    uint32_t klo, khi;     // client key
+    float w;
+};
+
+__device__ inline RksMeta rks_meta(const uint32_t* cnt, const uint64_t* ckey, const float* w, int64_t c, int64_t n,
+                                   int64_t r, uint32_t clen) {
+    RksMeta m{0u, 0u, 0u, 1.f};
+    if (r < n) {
+        m.m = min(cnt[c * n + r], clen);                 // <= clen by construction; never index past it
+        const uint64_t k = ckey[r];
+        m.klo = (uint32_t)k;
+        m.khi = (uint32_t)(k >> 32);
+        if (w) m.w = w[r];
+    }
+    return m;
+}
+
+// The lanes of a wave exchange values through its LDS tile.  To the compiler every lane is a thread of
+// its own: without a fence it forwards a lane's own earlier store (the tile's reset) to its later
+// load on the paths where that lane stored nothing, although another lane did.  Wavefront scope:
+// no instruction is emitted (a wave's LDS operations execute in order).
+__device__ inline void rks_tile_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+constexpr int RKS_AP = 8;                                 // rows in flight (their two gathers)
+
+template <int TS, int MODE>
+__global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64_t d, const uint32_t* __restrict__ cnt,
+                                                     const uint64_t* __restrict__ ckey, const float* __restrict__ w,
+                                                     float wt, float* __restrict__ out) {
+    constexpr int PARTS = CHUNK / TS;
+    constexpr int AP = RKS_AP;
+    constexpr int NR = MODE == RKS_C ? TS / 64 : 1;        // shape C: columns per lane, summed in registers
+    constexpr uint32_t NOCOL = 0xFFFFu;                    // past the chunk: the buffer load returns 0
+    static_assert(64 % AP == 0, "the ring walks a 64-row batch in whole turns");
+    __shared__ __attribute__((aligned(16))) float tile[4][TS];
+    __shared__ uint32_t zmask[4][TS / 32];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t C = nchunks(d);
+    float* tl = tile[wv];
+    const int64_t nb = (n + 63) / 64;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wv; t < C * PARTS; t += (int64_t)gridDim.x * 4) {
+        const int64_t c = t / PARTS;
+        const uint32_t pbase = (uint32_t)((t % PARTS) * TS);
+        const int64_t cbase = c * CHUNK;
+        const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - cbase);
+        float acc[NR], bs[NR];
+        if (MODE == RKS_C) {
+#pragma unroll
+            for (int k = 0; k < NR; ++k) {
+                const uint32_t col = pbase + (uint32_t)(k * 64 + lane);
+                acc[k] = -0.f;                                 // the additive identity: the first term is assigned
+                bs[k] = col < clen ? g.base[cbase + col] : 0.f;
+                tl[k * 64 + lane] = 0.f;
+            }
+        } else {
+            for (int i = lane; i < TS; i += 64) tl[i] = -0.f;
+        }
+        uint32_t ro[AP];                                      // ring: part-local column (>= TS: none)
+        float ra[AP], rb[AP];                                 //       gathered a, b
+        // row r's members of this part for this lane: two gathers in flight
+        auto fetch = [&](int slot, int64_t r, uint32_t m, uint64_t k) {
+            const int64_t rr = min(r, n - 1);                 // (rows past n have m == 0: nothing is loaded)
+            const rktree::ChunkPerm P(k, c, clen);
+            uint32_t col = (uint32_t)lane < m ? P((uint32_t)lane) : NOCOL;
+            if (PARTS > 1 && col - pbase >= (uint32_t)TS) col = NOCOL;   // another wave's part: no gather
+            const auto rsa = chunk_rsrc(g.a + rr * g.lda, cbase, d);
+            const auto rsb = chunk_rsrc(g.b + rr * g.ldb, cbase, d);
+            ro[slot] = col - pbase;
+            ra[slot] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsa, (int)(col * 4u), 0, 0));
+            rb[slot] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsb, (int)(col * 4u), 0, 0));
+        };
+        // one member (part-local column loc < TS) of row r: the epilogue, the in-place store, the fold
+        auto member = [&](uint32_t loc, float av, float bv, int64_t r, float wi) {
+            const float v = av - bv;
+            const float e = g.scale * v;
+            const float tt = e * g.ms;
+            if (MODE == RKS_A) {
+                const auto rsb = chunk_rsrc(g.b + r * g.ldb, cbase, d);
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bv + g.alpha * e), rsb, (int)((pbase + loc) * 4u), 0, 0);
+            }
+            if (MODE == RKS_C) tl[loc] = tt;
+            else tl[loc] = tl[loc] + wi * tt;
+        };
+        RksMeta cur = rks_meta(cnt, ckey, w, c, n, lane, clen), nxt;
+#pragma unroll
+        for (int q = 0; q < AP; ++q)
+            fetch(q, q, (uint32_t)__builtin_amdgcn_readlane(cur.m, q),
+                  rks_join64((uint32_t)__builtin_amdgcn_readlane(cur.khi, q), (uint32_t)__builtin_amdgcn_readlane(cur.klo, q)));
+        for (int64_t b = 0; b < nb; ++b) {
+            const int64_t i0 = b * 64;
+            nxt = rks_meta(cnt, ckey, w, c, n, i0 + 64 + lane, clen);
+#pragma unroll 1
+            for (int q0 = 0; q0 < 64; q0 += AP) {
+                const bool wrap = q0 + AP >= 64;              // the refills come from the next batch
+#pragma unroll
+                for (int z = 0; z < AP; ++z) {
+                    const int q = q0 + z;
+                    const int64_t r = i0 + q;
+                    if (r < n) {
+                        const float wi = __uint_as_float((uint32_t)__builtin_amdgcn_readlane(__float_as_uint(cur.w), q));
+                        const uint32_t m = (uint32_t)__builtin_amdgcn_readlane(cur.m, q);
+                        if (ro[z] < (uint32_t)TS) member(ro[z], ra[z], rb[z], r, wi);
+                        if (m > 64u) {                        // a row with more than 64 members here: its tail in place
+                            const uint64_t k = rks_join64((uint32_t)__builtin_amdgcn_readlane(cur.khi, q),
+                                                          (uint32_t)__builtin_amdgcn_readlane(cur.klo, q));
+                            const rktree::ChunkPerm P(k, c, clen);
+                            const float* ap = g.a + r * g.lda + cbase;
+                            const float* bp = g.b + r * g.ldb + cbase;
+                            for (uint32_t e = 64u + lane; e < m; e += 64) {
+                                const uint32_t col = P(e), l2 = col - pbase;
+                                if (l2 < (uint32_t)TS) member(l2, ap[col], bp[col], r, wi);
+                            }
+                        }
+                        if (MODE == RKS_C) {                  // every column: w * (base + t), t = +0 outside the set
+                            rks_tile_fence();
+#pragma unroll
+                            for (int k = 0; k < NR; ++k) {
+                                acc[k] = acc[k] + wi * (bs[k] + tl[k * 64 + lane]);
+                                tl[k * 64 + lane] = 0.f;
+                            }
+                        }
+                    }
+                    const int qq = (q + AP) & 63;
+                    const uint32_t mn = (uint32_t)(wrap ? __builtin_amdgcn_readlane(nxt.m, qq) : __builtin_amdgcn_readlane(cur.m, qq));
+                    const uint32_t kh = (uint32_t)(wrap ? __builtin_amdgcn_readlane(nxt.khi, qq) : __builtin_amdgcn_readlane(cur.khi, qq));
+                    const uint32_t kl = (uint32_t)(wrap ? __builtin_amdgcn_readlane(nxt.klo, qq) : __builtin_amdgcn_readlane(cur.klo, qq));
+                    fetch(z, r + AP, mn, rks_join64(kh, kl));
+                }
+            }
+            cur = nxt;
+        }
+        const int64_t len = min((int64_t)TS, (int64_t)clen - (int64_t)pbase);
+        rks_tile_fence();
+        if (MODE == RKS_C) {
+#pragma unroll
+            for (int k = 0; k < NR; ++k)
+                if (k * 64 + lane < len) out[cbase + pbase + k * 64 + lane] = acc[k] / wt;
+        } else {
+            rk_resolve_neg_zero<TS>(tl, zmask[wv], cnt, ckey, c, n, pbase, clen, len, w, lane);
+            for (int64_t i = lane; i < len; i += 64) out[cbase + pbase + i] = tl[i] / wt;
+        }
+    }
+}
+
+// Shape B, device draws: no fold here (reduce_impl reads the updated rows afterwards), so the walk is
+// row-major like k_randk_gen — a wave stays inside one row, chunk after chunk.
+__global__ __launch_bounds__(256) void k_randk_shift_scatter(RksArgs g, int64_t n, int64_t d,
+                                                             const uint32_t* __restrict__ cnt,
+                                                             const uint64_t* __restrict__ ckey) {
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t C = nchunks(d);
+    for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
+        const uint64_t k = ckey[row];
+        const float* ap = g.a + row * g.lda;
+        float* bp = g.b + row * g.ldb;
+        for (int64_t c = (int64_t)blockIdx.x * 4 + wv; c < C; c += (int64_t)gridDim.x * 4) {
+            const int64_t cbase = c * CHUNK;
+            const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - cbase);
+            const uint32_t m = min(cnt[c * n + row], clen);
+            const rktree::ChunkPerm P(k, c, clen);
+            for (uint32_t t = (uint32_t)lane; t < m; t += 64) {
+                const int64_t j = cbase + P(t);               // < cbase + clen <= d
+                const float bv = bp[j];
+                const float e = g.scale * (ap[j] - bv);
+                bp[j] = bv + e * g.ms;
+            }
+        }
+    }
+}
+
+// Compat, shapes A / C / D: entry (row, t) of the bucketed lists gets its value t = e * msg_scale and,
+// in shape A, the thread that gathered b[j] stores h'.  An index >= d stores nothing.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_randk_shift_lists(RksArgs g, int64_t n, int64_t d, int64_t K, RkLists L) {
+    for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
+        const float* ap = g.a + row * g.lda;
+        float* bp = g.b + row * g.ldb;
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < K; t += (int64_t)gridDim.x * 256) {
+            const int64_t j = (int64_t)L.idx[row * L.cap + t];
+            float tt = 0.f;
+            if (j < d) {
+                const float bv = bp[j];
+                const float e = g.scale * (ap[j] - bv);
+                tt = e * g.ms;
+                if (MODE == RKS_A) bp[j] = bv + g.alpha * e;
+            }
+            L.val[row * L.cap + t] = tt;
+        }
+    }
+}
+
+// Compat, shape B: one thread per (row, t) straight from the caller's index rows
+__global__ __launch_bounds__(256) void k_randk_shift_idx(RksArgs g, int64_t n, int64_t d, int64_t K,
+                                                         const int64_t* __restrict__ idx, int64_t ldi) {
+    for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
+        const float* ap = g.a + row * g.lda;
+        float* bp = g.b + row * g.ldb;
+        for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < K; t += (int64_t)gridDim.x * 256) {
+            const int64_t j = idx[row * ldi + t];
+            if ((uint64_t)j < (uint64_t)d) {
+                const float bv = bp[j];
+                const float e = g.scale * (ap[j] - bv);
+                bp[j] = bv + e * g.ms;
+            }
+        }
+    }
+}
+
+// Compat, shape C: the fold of base + t from the lists, the form of k_randk_shift<TS, RKS_C>
+template <int TS>
+__global__ __launch_bounds__(256) void k_randk_shift_lfold(const float* __restrict__ base, int64_t n, int64_t d, RkLists L,
+                                                           const float* __restrict__ w, float wt, float* __restrict__ out) {
+    constexpr int PARTS = CHUNK / TS;
+    constexpr int NR = TS / 64;
+    __shared__ __attribute__((aligned(16))) float tile[4][TS];
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t C = nchunks(d);
+    float* tl = tile[wv];
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wv; t < C * PARTS; t += (int64_t)gridDim.x * 4) {
+        const int64_t c = t / PARTS;
+        const uint32_t pbase = (uint32_t)((t % PARTS) * TS);
+        const int64_t cbase = c * CHUNK;
+        const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - cbase);
+        float acc[NR], bs[NR];
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            const uint32_t col = pbase + (uint32_t)(k * 64 + lane);
+            acc[k] = -0.f;
+            bs[k] = col < clen ? base[cbase + col] : 0.f;
+            tl[k * 64 + lane] = 0.f;
+        }
+        for (int64_t r = 0; r < n; ++r) {
+            const uint2 te = L.tab[c * n + r];
+            const float wi = w ? w[r] : 1.f;
+            for (uint32_t e = (uint32_t)lane; e < te.y; e += 64) {
+                const int64_t p = r * L.cap + te.x + e;
+                const uint32_t loc = L.idx[p] - (uint32_t)cbase - pbase;
+                if (loc < (uint32_t)TS) tl[loc] = L.val[p];
+            }
+            rks_tile_fence();
+#pragma unroll
+            for (int k = 0; k < NR; ++k) {
+                acc[k] = acc[k] + wi * (bs[k] + tl[k * 64 + lane]);
+                tl[k * 64 + lane] = 0.f;
+            }
+        }
+        const int64_t len = min((int64_t)TS, (int64_t)clen - (int64_t)pbase);
+#pragma unroll
+        for (int k = 0; k < NR; ++k)
+            if (k * 64 + lane < len) out[cbase + pbase + k * 64 + lane] = acc[k] / wt;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// Host
+// ------------------------------------------------------------------------------------------
+constexpr int RKS_CTS = 1024;                               // shape C's part: 16 sums + 16 base values per lane
+
+static int64_t rks_chunks(int64_t d) { return (d + CHUNK - 1) / CHUNK; }
+static int rks_blocks(int64_t items, int64_t cap) { return (int)std::max<int64_t>(1, std::min<int64_t>(items, cap)); }
+
+// The accepted shape of a round (flcodec.h), or -1 with the reason set.  sr: api.hip's normalised copy
+// (no shift_in without a shift_out, leading dimensions of absent operands zeroed).
+static int rks_shape(const flc_shift_rows& sr) {
+    const char* me = "flc_randk_shift_reduce";
+    if (!(std::isfinite(sr.msg_scale) && sr.msg_scale > 0.f)) {
+        set_error("%s: msg_scale must be finite and > 0 (got %g)", me, (double)sr.msg_scale);
+        return -1;
+    }
+    if (sr.d_shift_out) {
+        if (sr.d_base || sr.d_msg) { set_error("%s: a shift together with a base or stored messages is not a sparse shape", me); return -1; }
+        if ((const float*)sr.d_shift_out != sr.d_b || sr.d_shift_in != sr.d_b || sr.ldout != sr.ldb || sr.ldin != sr.ldb) {
+            set_error("%s: the shift must be updated in place over the b rows (d_shift_in == d_shift_out == d_b, equal leading dimensions)", me);
+            return -1;
+        }
+        if (!(std::isfinite(sr.shift_alpha) && sr.shift_alpha > 0.f)) {
+            set_error("%s: shift_alpha must be finite and > 0 (got %g)", me, (double)sr.shift_alpha);
+            return -1;
+        }
+        return RKS_A;
+    }
+    if (sr.d_msg) {
+        if (sr.d_base != sr.d_b || (const float*)sr.d_msg != sr.d_b || sr.ldbase != sr.ldb || sr.ldmsg != sr.ldb) {
+            set_error("%s: stored messages only as the in-place EF21 step (d_base == d_msg == d_b, equal leading dimensions)", me);
+            return -1;
+        }
+        return RKS_B;
+    }
+    if (sr.d_base) {
+        if (sr.ldbase != 0) { set_error("%s: a per-row base that is not d_msg == d_b (only ONE shared base, ldbase == 0, folds without a store)", me); return -1; }
+        return RKS_C;
+    }
+    return RKS_D;
+}
+
+size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n, int64_t d) {
+    if (n <= 0 || d <= 0) return 0;
+    if (compat) return randk_lists_workspace(n, d, std::max<int64_t>(1, prm->k));
+    return randk_device_workspace(n, d);
+}
+
+int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
+                    const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+    const char* me = "flc_randk_shift_reduce";
+    const int shape = rks_shape(sr);
+    if (shape < 0) return FLC_ERR_UNSUPPORTED;
+    const bool compat = pat && pat->d_randk_idx;
+    const int64_t K = prm->k;
+    if (K < 1 || K > d) { set_error("%s: K=%lld outside [1, D=%lld]", me, (long long)K, (long long)d); return FLC_ERR_ARG; }
+    if (d >= (int64_t)0xFFFFFFFF) { set_error("%s: D too large for 32-bit entry indices", me); return FLC_ERR_ARG; }
+    if (n > 1 && (shape == RKS_A || shape == RKS_B) && (sr.ldb < 0 ? -sr.ldb : sr.ldb) < d) {
+        set_error("%s: the in-place rows overlap (|ldb| < d)", me);
+        return FLC_ERR_ARG;
+    }
+    if (ws_bytes < randk_shift_workspace(prm, compat, n, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
+    const int64_t C = rks_chunks(d);
+    RksArgs g{sr.d_a, sr.lda, const_cast<float*>(sr.d_b), sr.ldb, sr.d_base, prm->randk_scale, sr.msg_scale, sr.shift_alpha};
+    const unsigned gy = (unsigned)std::min<int64_t>(n, 65535);
+    auto fold_b = [&]() {                                   // shape B: the dense fold of the updated rows
+        const bool vec = (((uintptr_t)sr.d_b & 15u) == 0) && (sr.ldb % 4 == 0);
+        RowSrc rows{sr.d_b, sr.ldb, nullptr};
+        return reduce_impl(rows, vec, n, d, nullptr, w, wt, FLC_REDUCE_PLAIN, out, st);
+    };
+    if (compat) {
+        if (shape == RKS_B) {
+            {
+                ProfScope _ps("k_randk_shift_lists", st);
+                const int gx = rks_blocks((K + 255) / 256, 1024);
+                hipLaunchKernelGGL(k_randk_shift_idx, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, pat->d_randk_idx,
+                                   pat->idx_ld ? pat->idx_ld : K);
+                FLC_CHECK_LAUNCH("k_randk_shift_idx");
+            }
+            return fold_b();
+        }
+        RkLists L;
+        RowSrc rows{sr.d_a, sr.lda, nullptr};
+        if (int rc = randk_lists_build(prm, pat, rows, n, d, ws, &L, st)) return rc;
+        {
+            ProfScope _ps("k_randk_shift_lists", st);
+            const int gx = rks_blocks((K + 255) / 256, 1024);
+            if (shape == RKS_A) hipLaunchKernelGGL(k_randk_shift_lists<RKS_A>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L);
+            else hipLaunchKernelGGL(k_randk_shift_lists<RKS_D>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L);
+            FLC_CHECK_LAUNCH("k_randk_shift_lists");
+        }
+        if (shape != RKS_C) return randk_lists_fold(n, d, K, ws, w, wt, out, st);
+        ProfScope _ps("k_randk_shift_lfold", st);
+        const int ab = rks_blocks((C * (CHUNK / RKS_CTS) + 3) / 4, 16384);
+        hipLaunchKernelGGL(k_randk_shift_lfold<RKS_CTS>, dim3(ab), dim3(256), 0, st, sr.d_base, n, d, L, w, wt, out);
+        FLC_CHECK_LAUNCH("k_randk_shift_lfold");
+        return FLC_OK;
+    }
+    const uint32_t* cnt = nullptr;
+    const uint64_t* ckey = nullptr;
+    if (int rc = randk_device_prepare(prm, pat, n, d, ws, &cnt, &ckey, st)) return rc;
+    if (shape == RKS_B) {
+        {
+            ProfScope _ps("k_randk_shift", st);
+            const int gx = rks_blocks((C + 3) / 4, 4096);
+            hipLaunchKernelGGL(k_randk_shift_scatter, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, cnt, ckey);
+            FLC_CHECK_LAUNCH("k_randk_shift_scatter");
+        }
+        return fold_b();
+    }
+    ProfScope _ps("k_randk_shift", st);
+    // few chunks (short rows): split each chunk's columns over 2 or 4 waves, as k_chunk_accum does
+    const int parts = shape == RKS_C ? CHUNK / RKS_CTS : (C >= 1024 ? 1 : (C >= 256 ? 2 : 4));
+    const int ab = rks_blocks((C * parts + 3) / 4, 16384);
+    auto go = [&](auto ts, auto mode) {
+        hipLaunchKernelGGL((k_randk_shift<decltype(ts)::value, decltype(mode)::value>), dim3(ab), dim3(256), 0, st, g, n, d,
+                           cnt, ckey, w, wt, out);
+    };
+    auto by_parts = [&](auto mode) {
+        if (parts == 1) go(std::integral_constant<int, CHUNK>{}, mode);
+        else if (parts == 2) go(std::integral_constant<int, CHUNK / 2>{}, mode);
+        else go(std::integral_constant<int, CHUNK / 4>{}, mode);
+    };
+    if (shape == RKS_C) go(std::integral_constant<int, RKS_CTS>{}, std::integral_constant<int, RKS_C>{});
+    else if (shape == RKS_A) by_parts(std::integral_constant<int, RKS_A>{});
+    else by_parts(std::integral_constant<int, RKS_D>{});
+    FLC_CHECK_LAUNCH("k_randk_shift");
+    return FLC_OK;
+}
+
+}  // namespace flc

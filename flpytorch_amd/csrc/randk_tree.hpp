@@ -86,4 +86,61 @@ struct ChunkPerm {
 };
 
 }  // namespace rktree
+
+#if defined(__HIPCC__)
+// -0 columns after the fold (every kept term was -0, or no row kept the column): the reference's
+// sum is -0 only if every row's term is -0, and a row that did not keep the column adds w * (+0)
+// (resolve_neg_zero above, the same rule).  Walk the rows with a positive-signed weight, regenerate
+// their members of this part, and turn +0 every -0 column some such row does not keep; stops as
+// soon as no candidate is left (normally after the first row).
+template <int TS>
+__device__ void rk_resolve_neg_zero(float* tl, uint32_t* rm, const uint32_t* cnt, const uint64_t* ckey, int64_t c,
+                                    int64_t n, uint32_t pbase, uint32_t clen, int64_t len, const float* w, int lane) {
+    constexpr int NW = TS / 32;
+    constexpr int WL = (NW + 63) / 64;
+    bool any = false;
+    for (int k = 0; k < TS / 64; ++k) {
+        const int64_t i = (int64_t)k * 64 + lane;
+        const uint64_t b = __ballot(i < len && __float_as_uint(tl[i]) == 0x80000000u);
+        if (lane == 0) { rm[2 * k] = (uint32_t)b; rm[2 * k + 1] = (uint32_t)(b >> 32); }
+        any |= b != 0ull;
+    }
+    if (!any) return;
+    uint32_t z0[WL], zc[WL];
+#pragma unroll
+    for (int j = 0; j < WL; ++j) {
+        const int k = lane + 64 * j;
+        z0[j] = k < NW ? rm[k] : 0u;
+        zc[j] = z0[j];
+    }
+    for (int64_t r = 0; r < n; ++r) {
+        if (w && (__float_as_uint(w[r]) >> 31)) continue;
+#pragma unroll
+        for (int j = 0; j < WL; ++j) if (lane + 64 * j < NW) rm[lane + 64 * j] = 0u;
+        const uint32_t m = min(cnt[c * n + r], clen);
+        const rktree::ChunkPerm P(ckey[r], c, clen);
+        for (uint32_t t = (uint32_t)lane; t < m; t += 64) {
+            const uint32_t loc = P(t) - pbase;
+            if (loc < (uint32_t)TS) atomicOr(&rm[loc >> 5], 1u << (loc & 31));
+        }
+        bool left = false;
+#pragma unroll
+        for (int j = 0; j < WL; ++j) {
+            if (lane + 64 * j < NW) zc[j] &= rm[lane + 64 * j];
+            left |= zc[j] != 0u;
+        }
+        if (__ballot(left) == 0ull) break;
+    }
+#pragma unroll
+    for (int j = 0; j < WL; ++j) {
+        uint32_t dead = z0[j] & ~zc[j];
+        while (dead) {
+            const int b = __builtin_ctz(dead);
+            dead &= dead - 1u;
+            tl[(lane + 64 * j) * 32 + b] = 0.f;
+        }
+    }
+}
+#endif
+
 }  // namespace flc

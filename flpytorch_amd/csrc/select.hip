@@ -2420,59 +2420,7 @@ __device__ inline RkMeta rk_meta(RowSrc rows, const uint32_t* cnt, const uint64_
     return m;
 }
 
-// -0 columns after the fold (every kept term was -0, or no row kept the column): the reference's
-// sum is -0 only if every row's term is -0, and a row that did not keep the column adds w * (+0)
-// (resolve_neg_zero above, the same rule).  Walk the rows with a positive-signed weight, regenerate
-// their members of this part, and turn +0 every -0 column some such row does not keep; stops as
-// soon as no candidate is left (normally after the first row).
-template <int TS>
-__device__ void rk_resolve_neg_zero(float* tl, uint32_t* rm, const uint32_t* cnt, const uint64_t* ckey, int64_t c,
-                                    int64_t n, uint32_t pbase, uint32_t clen, int64_t len, const float* w, int lane) {
-    constexpr int NW = TS / 32;
-    constexpr int WL = (NW + 63) / 64;
-    bool any = false;
-    for (int k = 0; k < TS / 64; ++k) {
-        const int64_t i = (int64_t)k * 64 + lane;
-        const uint64_t b = __ballot(i < len && __float_as_uint(tl[i]) == 0x80000000u);
-        if (lane == 0) { rm[2 * k] = (uint32_t)b; rm[2 * k + 1] = (uint32_t)(b >> 32); }
-        any |= b != 0ull;
-    }
-    if (!any) return;
-    uint32_t z0[WL], zc[WL];
-#pragma unroll
-    for (int j = 0; j < WL; ++j) {
-        const int k = lane + 64 * j;
-        z0[j] = k < NW ? rm[k] : 0u;
-        zc[j] = z0[j];
-    }
-    for (int64_t r = 0; r < n; ++r) {
-        if (w && (__float_as_uint(w[r]) >> 31)) continue;
-#pragma unroll
-        for (int j = 0; j < WL; ++j) if (lane + 64 * j < NW) rm[lane + 64 * j] = 0u;
-        const uint32_t m = min(cnt[c * n + r], clen);
-        const rktree::ChunkPerm P(ckey[r], c, clen);
-        for (uint32_t t = (uint32_t)lane; t < m; t += 64) {
-            const uint32_t loc = P(t) - pbase;
-            if (loc < (uint32_t)TS) atomicOr(&rm[loc >> 5], 1u << (loc & 31));
-        }
-        bool left = false;
-#pragma unroll
-        for (int j = 0; j < WL; ++j) {
-            if (lane + 64 * j < NW) zc[j] &= rm[lane + 64 * j];
-            left |= zc[j] != 0u;
-        }
-        if (__ballot(left) == 0ull) break;
-    }
-#pragma unroll
-    for (int j = 0; j < WL; ++j) {
-        uint32_t dead = z0[j] & ~zc[j];
-        while (dead) {
-            const int b = __builtin_ctz(dead);
-            dead &= dead - 1u;
-            tl[(lane + 64 * j) * 32 + b] = 0.f;
-        }
-    }
-}
+// (rk_resolve_neg_zero, the -0 column rule after the fold: randk_tree.hpp, shared with randk_shift.hip)
 
 #ifndef FLC_RK_AP
 #define FLC_RK_AP 8
@@ -3935,6 +3883,30 @@ static int randk_counts(const flc_codec_params* prm, const flc_pattern* pat, int
     return FLC_OK;
 }
 
+// chunk counts of a fold: the caller's (flc_pattern.d_randk_counts, made by flc_device_randk_counts) or
+// computed into ws; the client keys are cheap and always computed here
+static int randk_counts_or_given(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, RkdWs* rw,
+                                 hipStream_t st) {
+    if (pat && pat->d_randk_counts) {
+        rw->cnt = const_cast<uint32_t*>(pat->d_randk_counts);          // read only by the folds
+        hipLaunchKernelGGL(k_randk_ckeys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, prm->seed,
+                           pat->client0, rw->ckey);
+        FLC_CHECK_LAUNCH("k_randk_ckeys");
+        return FLC_OK;
+    }
+    return randk_counts(prm, pat, n, d, *rw, st);
+}
+
+// the same for randk_shift.hip: wsp holds randk_device_workspace(n, d) bytes
+int randk_device_prepare(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, void* wsp,
+                         const uint32_t** cnt, const uint64_t** ckey, hipStream_t st) {
+    RkdWs rw = carve_rkd(wsp, n, d, nullptr);
+    if (int rc = randk_counts_or_given(prm, pat, n, d, &rw, st)) return rc;
+    *cnt = rw.cnt;
+    *ckey = rw.ckey;
+    return FLC_OK;
+}
+
 // the device sampler's chunk counts of n clients (flc_device_randk_counts: the sampler's test hook)
 int randk_device_counts(uint64_t seed, int64_t client0, int64_t n, int64_t d, int64_t k, uint32_t* cnt, void* wsp,
                         size_t ws_bytes, hipStream_t st) {
@@ -3965,16 +3937,7 @@ int randk_device_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc
     // over the lists with its column split (k_chunk_accum).
     // chunk counts: the caller's (flc_pattern.d_randk_counts, made by flc_device_randk_counts) or
     // computed here; the client keys are cheap and always computed here
-    auto counts = [&]() -> int {
-        if (pat && pat->d_randk_counts) {
-            rw.cnt = const_cast<uint32_t*>(pat->d_randk_counts);          // read only below
-            hipLaunchKernelGGL(k_randk_ckeys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, prm->seed,
-                               pat->client0, rw.ckey);
-            FLC_CHECK_LAUNCH("k_randk_ckeys");
-            return FLC_OK;
-        }
-        return randk_counts(prm, pat, n, d, rw, st);
-    };
+    auto counts = [&]() -> int { return randk_counts_or_given(prm, pat, n, d, &rw, st); };
     if (C >= 1024) {
         if (int rc = counts()) return rc;
         ProfScope _ps("k_randk_fold", st);
@@ -4050,6 +4013,51 @@ static int launch_chunk_accum(int64_t n, int64_t d, SelWs ws, bool assign, const
     return FLC_OK;
 }
 
+// The compat RandK lists on their own (randk_shift.hip: the sparse shifted round rewrites the entry
+// values between the bucketing and the fold).  build: k_randk_coarse / k_randk_fine over `rows`
+// exactly as sel_run launches them; fold: k_chunk_accum over the lists as they then stand.
+size_t randk_lists_workspace(int64_t n, int64_t d, int64_t K) {
+    size_t b = 0;
+    carve_sel(nullptr, FLC_RANDK, n, d, K, &b);
+    return b;
+}
+
+static int randk_lists_launch(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d,
+                              SelWs ws, hipStream_t st) {
+    const int64_t K = prm->k, C = host_chunks(d);
+    const int64_t ldi = pat->idx_ld ? pat->idx_ld : K;
+    const int64_t spc = rk_spc(C), sb = (C + spc - 1) / spc;
+    { ProfScope _ps("k_randk_coarse", st);
+    if (spc == 1)
+        hipLaunchKernelGGL(k_randk_coarse<true>, dim3((unsigned)n), dim3(RK_T), 0, st, rows, n, d, K, *pat, ldi,
+                           prm->randk_scale, ws);
+    else
+        hipLaunchKernelGGL(k_randk_coarse<false>, dim3((unsigned)n), dim3(RK_T), 0, st, rows, n, d, K, *pat, ldi,
+                           prm->randk_scale, ws); }
+    FLC_CHECK_LAUNCH("k_randk_coarse");
+    if (spc > 1) {
+        ProfScope _ps("k_randk_fine", st);
+        hipLaunchKernelGGL(k_randk_fine, dim3((unsigned)sb, (unsigned)n), dim3(RK_FTHR), (size_t)spc * sizeof(uint32_t),
+                           st, rows, n, d, K, prm->randk_scale, ws);
+        FLC_CHECK_LAUNCH("k_randk_fine");
+    }
+    return FLC_OK;
+}
+
+int randk_lists_build(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d, void* wsp,
+                      RkLists* lists, hipStream_t st) {
+    SelWs ws = carve_sel(wsp, FLC_RANDK, n, d, prm->k, nullptr);
+    lists->tab = ws.tab;
+    lists->idx = ws.ent_idx;
+    lists->val = ws.ent_val;
+    lists->cap = ws.cap;
+    return randk_lists_launch(prm, pat, rows, n, d, ws, st);
+}
+
+int randk_lists_fold(int64_t n, int64_t d, int64_t K, void* wsp, const float* w, float wt, float* out, hipStream_t st) {
+    return launch_chunk_accum(n, d, carve_sel(wsp, FLC_RANDK, n, d, K, nullptr), false, w, wt, out, st);
+}
+
 int sel_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bool vec, int64_t n, int64_t d,
             bool assign, const float* w, float wt, float* out, void* wsp, size_t ws_bytes, hipStream_t st) {
     const int codec = prm->codec;
@@ -4073,22 +4081,7 @@ int sel_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bo
     // TopK, few rows: sharded candidate lists (k_topk_filter_fast) and the spread select (k_cs_pass)
     const bool few = codec == FLC_TOPK && n <= CS_FEW && !cs_single() && sel_capacity(codec, d, K) >= (int64_t)CS_SH * GCAP;
     if (codec == FLC_RANDK) {
-        const int64_t ldi = pat->idx_ld ? pat->idx_ld : K;
-        const int64_t spc = rk_spc(C), sb = (C + spc - 1) / spc;
-        { ProfScope _ps("k_randk_coarse", st);
-        if (spc == 1)
-            hipLaunchKernelGGL(k_randk_coarse<true>, dim3((unsigned)n), dim3(RK_T), 0, st, rows, n, d, K, *pat, ldi,
-                               prm->randk_scale, ws);
-        else
-            hipLaunchKernelGGL(k_randk_coarse<false>, dim3((unsigned)n), dim3(RK_T), 0, st, rows, n, d, K, *pat, ldi,
-                               prm->randk_scale, ws); }
-        FLC_CHECK_LAUNCH("k_randk_coarse");
-        if (spc > 1) {
-            ProfScope _ps("k_randk_fine", st);
-            hipLaunchKernelGGL(k_randk_fine, dim3((unsigned)sb, (unsigned)n), dim3(RK_FTHR), (size_t)spc * sizeof(uint32_t),
-                               st, rows, n, d, K, prm->randk_scale, ws);
-            FLC_CHECK_LAUNCH("k_randk_fine");
-        }
+        if (int rc = randk_lists_launch(prm, pat, rows, n, d, ws, st)) return rc;
     } else {  // TOPK
         // a lone compressVector row up to RS_U * 4096 elements per CU (any K): in registers, one
         // launch.  Not inside a stream capture (the call's sequence number and the cross-stream

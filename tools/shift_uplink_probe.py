@@ -23,6 +23,15 @@ call is timed in the same rounds as "fused@<tag>" ON THE SAME shift matrix as "f
 their own reads up to ~10 % differently: placement).  A timing-only mode: the shifts then take several
 updates per repeat, so the bit check against the composition is off.
 Writes <out-dir>/<spec>.jsonl: one line per (repeat, variant) and a summary line.
+
+--sparse (RandK specs, e.g. --specs randk:1%,randk:10%): the same in-place DIANA round three ways,
+  sparse     ShiftUplinkReducer(..., sparse=True)                           flc_randk_shift_reduce
+  general    ShiftUplinkReducer(...) on its own copy of the shifts          flc_encode_shift_reduce
+  yardstick  UplinkReducer's RandK fold of the G rows alone (for scale: one gather per member, no store)
+interleaved in one process on one allocation; after every repeat the two outputs and the two shift
+matrices must agree bit for bit (Gaussian shifts hold no -0).  The summary carries the 128-B line
+floor of the sparse round: the expected number of lines a row's K members touch, (D / 32) *
+(1 - (1 - K / D)^32), times 128 B, for a, for b and for the write-back, N rows.
 """
 import argparse
 import json
@@ -43,6 +52,103 @@ def byte_model(spec, n, d):
             "yardstick": (8 if dither else 4) * n * d + 4 * d}
 
 
+def main_sparse(a):
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d = a.n, a.d
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev).manual_seed(1000)
+
+    def filled():
+        t = torch.empty((n, d), dtype=torch.float32, device=dev)
+        for i in range(0, n, 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    G, H0 = filled(), filled()
+    Hs, Hg = torch.empty_like(H0), torch.empty_like(H0)
+    outs = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in ("sparse", "general", "yardstick")}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for spec in a.specs.split(","):
+        if not spec.startswith("randk"):
+            raise SystemExit("--sparse times RandK specs only")
+        comp_s, comp_g, comp_y = (ag.initCompressor(spec, d) for _ in range(3))
+        k = comp_s.K
+        alpha = 1.0 / (1.0 + comp_s.getW())
+        red_s = ag.ShiftUplinkReducer(comp_s, device=dev, seed=SEED)
+        red_g = ag.ShiftUplinkReducer(comp_g, device=dev, seed=SEED)
+        yard = ag.UplinkReducer(comp_y, device=dev, seed=SEED)
+        Hs.copy_(H0)
+        Hg.copy_(H0)
+        runs = {"sparse": lambda: red_s(G, Hs, alpha=alpha, shift=Hs, shift_out=Hs, out=outs["sparse"], sparse=True),
+                "general": lambda: red_g(G, Hg, alpha=alpha, shift=Hg, shift_out=Hg, out=outs["general"]),
+                "yardstick": lambda: yard(G, out=outs["yardstick"])}
+        lines = (d / 32.0) * (1.0 - (1.0 - k / d) ** 32)
+        model = {"sparse": int(3 * n * lines * 128) + 4 * d,          # the line floor: a, b, the write-back
+                 "general": 44 * n * d,                               # sub 12, scatter 4 + memset-free dense e 4, epi 16, fold 12 (- first row)
+                 "yardstick": int(n * lines * 128) + 4 * d}
+        for f in runs.values():                        # warm: code objects, workspaces
+            f()
+        torch.cuda.synchronize()
+
+        def agree():
+            return (torch.equal(outs["sparse"].view(torch.int32), outs["general"].view(torch.int32))
+                    and torch.equal(Hs.view(torch.int32), Hg.view(torch.int32)))
+        if not agree():
+            raise SystemExit(f"{spec}: the sparse and the general round differ after the warm-up round")
+        ms = {v: [] for v in runs}
+        path = os.path.join(a.out_dir, spec.replace(":", "_").replace(".", "_").replace("%", "pct") + ".jsonl")
+        with open(path, "w") as fh:
+            def emit(rec):
+                line = json.dumps(rec)
+                fh.write(line + "\n")
+                fh.flush()
+                print(line, flush=True)
+            for r in range(a.repeats):
+                for v, f in runs.items():
+                    e0.record()
+                    for _ in range(a.steps):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    t = e0.elapsed_time(e1) / a.steps
+                    ms[v].append(t)
+                    emit({"spec": spec, "n": n, "d": d, "k": k, "repeat": r, "variant": v, "ms_per_call": round(t, 4)})
+                if not agree():
+                    raise SystemExit(f"{spec}: the sparse and the general round differ after repeat {r}")
+            kernels = ("k_randk_shift", "k_randk_counts", "k_randk_fold", "k_randk_gen", "k_chunk_accum")
+            kms = {}
+            for v in ("sparse", "yardstick"):         # (the general round's kernels carry no timers)
+                _lib.profile_enable(True)
+                for kn in kernels:
+                    _lib.profile_collect(kn)
+                runs[v]()
+                torch.cuda.synchronize()
+                _lib.profile_enable(False)
+                kms[v] = {kn: round(t, 4) for kn in kernels for t, c in [_lib.profile_collect(kn)] if c}
+            if not agree():
+                raise SystemExit(f"{spec}: the sparse and the general round differ after the timer pass")
+            med = {v: statistics.median(ms[v]) for v in runs}
+            emit({"spec": spec, "n": n, "d": d, "k": k, "summary": True, "repeats": a.repeats, "steps": a.steps,
+                  "median_ms": {v: round(med[v], 4) for v in runs},
+                  "min_ms": {v: round(min(ms[v]), 4) for v in runs},
+                  "max_ms": {v: round(max(ms[v]), 4) for v in runs},
+                  "general_over_sparse": round(med["general"] / med["sparse"], 3),
+                  "sparse_over_yardstick": round(med["sparse"] / med["yardstick"], 3),
+                  "sparse_faster_beyond_spread": max(ms["sparse"]) < min(ms["general"]),
+                  "touched_lines_per_row": round(lines, 1), "lines_per_row": d / 32.0,
+                  "line_floor_bytes": model["sparse"], "general_model_bytes": model["general"],
+                  "line_floor_ratio": round(model["general"] / model["sparse"], 2),
+                  "GBps_of_line_floor_at_median": round(model["sparse"] / med["sparse"] / 1e6, 1),
+                  "bits_equal_every_repeat": True,
+                  "kernel_ms_one_call": kms})
+        print("wrote", path, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--specs", default="natural,qsgd:127")
@@ -52,9 +158,12 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "r09", "shift_uplink"))
     ap.add_argument("--fused-libs", default="")
+    ap.add_argument("--sparse", action="store_true", help="RandK specs: flc_randk_shift_reduce against the general entry")
     a = ap.parse_args()
     if a.repeats < 1 or a.steps < 1 or a.n < 1 or a.d < 1:
         ap.error("--repeats, --steps, --n and --d are positive")
+    if a.sparse:
+        return main_sparse(a)
     import torch
 
     from flpytorch_amd import _lib
