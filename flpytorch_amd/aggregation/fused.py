@@ -235,7 +235,14 @@ class ShiftUplinkReducer:
     of the in-place operand OUTSIDE a row's index set are not written (the general entry stores
     ``x + 0`` there: the same bits except that a stored -0 becomes +0); selected elements and
     ``out`` carry the general entry's bits whenever the operand holds no -0 at an unselected
-    place."""
+    place.
+
+    ``batched=True`` (TopK only) runs the round through ``flc_topk_shift_reduce``: the N
+    differences formed in one launch, the many-row selection of the fused uplink over them, a sparse
+    epilogue and a list fold — a constant number of launches instead of N lone selections.  Same
+    four shapes, same contract and same bits as ``sparse=True`` states them for RandK (unselected
+    elements of the in-place operand are not written); any other compressor or shape raises
+    ``NotImplementedError``."""
 
     def __init__(self, compressor: Compressor, device=None, seed=None):
         _lib.require_gpu()
@@ -249,9 +256,12 @@ class ShiftUplinkReducer:
             prm.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
         return prm, keep
 
-    def workspace_bytes(self, n, d, sparse=False, compat=False):
-        """``sparse``: flc_randk_shift_reduce's workspace (``compat``: with numpy-stream index rows)."""
+    def workspace_bytes(self, n, d, sparse=False, compat=False, batched=False):
+        """``sparse``: flc_randk_shift_reduce's workspace (``compat``: with numpy-stream index rows);
+        ``batched``: flc_topk_shift_reduce's (the selection state, then the [n, d] difference matrix)."""
         prm, _ = self.params()
+        if batched:
+            return _lib.load().flc_topk_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
         if sparse:
             pat = _lib.FlcPattern()
             pat.d_randk_idx = 1 if compat else None             # (the size query only tells the modes apart)
@@ -260,7 +270,7 @@ class ShiftUplinkReducer:
 
     def __call__(self, a, b, *, scale=1.0, base=None, msg_out=None, alpha=None, shift=None, shift_out=None, out=None,
                  weights=None, divisor=None, client0=0, randk_idx=None, uniforms=None, lazy_u=None, pnorms_out=None,
-                 stream=None, sparse=False, randk_counts=None):
+                 stream=None, sparse=False, randk_counts=None, batched=False):
         """a, b: [N, D] fp32 row-contiguous device matrices (local gradients; shifts / previous
         estimators / previous gradients).  ``base``: None, [N, D], or ONE [D] vector for every row
         (MARINA's g_prev).  ``msg_out``: None (the messages are not stored) or [N, D]; it may be ``b``
@@ -273,13 +283,23 @@ class ShiftUplinkReducer:
         of 4; anything else runs the scalar kernel (same bits).  ``sparse=True``: the class docstring's
         RandK round (``NotImplementedError`` when the library refuses the codec or the shape — no
         silent fallback; ``pnorms_out`` is a ``ValueError``); ``randk_counts``: its device draws' chunk
-        counts from ``UplinkReducer.randk_counts(n, d, client0)`` with the same seed, as in ``UplinkReducer``."""
+        counts from ``UplinkReducer.randk_counts(n, d, client0)`` with the same seed, as in ``UplinkReducer``.
+        ``batched=True``: the class docstring's TopK round (``NotImplementedError`` for another
+        compressor, before any operand is looked at, or when the library refuses the shape — no silent
+        fallback; together with ``sparse``, ``pnorms_out`` or ``randk_counts`` it is a ``ValueError``)."""
+        if batched:
+            if sparse or pnorms_out is not None or randk_counts is not None:
+                raise ValueError("ShiftUplinkReducer: batched=True takes no sparse, pnorms_out or randk_counts "
+                                 "(TopK draws nothing and uses no norm)")
+            if self.comp.compressorType != CompressorType.TOPK_COMPRESSOR:
+                raise NotImplementedError("ShiftUplinkReducer: batched=True is the TOPK round (flc_topk_shift_reduce); "
+                                          f"this compressor is {self.comp.compressorType}")
         if sparse and pnorms_out is not None:
             raise ValueError("ShiftUplinkReducer: pnorms_out is not available with sparse=True (RandK uses no norm)")
         if randk_counts is not None and not sparse:
             raise ValueError("ShiftUplinkReducer: randk_counts is read by the sparse round only (sparse=True)")
         args = (a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx, uniforms,
-                lazy_u, pnorms_out, sparse, randk_counts)
+                lazy_u, pnorms_out, sparse, randk_counts, batched)
         if stream is not None:
             if stream.device != self.device:
                 raise ValueError(f"stream is on {stream.device}, the reducer runs on {self.device}")
@@ -288,7 +308,7 @@ class ShiftUplinkReducer:
         return self._run(*args)
 
     def _run(self, a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx,
-             uniforms, lazy_u, pnorms_out, sparse=False, randk_counts=None):
+             uniforms, lazy_u, pnorms_out, sparse=False, randk_counts=None, batched=False):
         lib = _lib.load()
         if not hasattr(lib, "flc_encode_shift_reduce"):
             raise NotImplementedError("this library build has no flc_encode_shift_reduce")
@@ -296,6 +316,10 @@ class ShiftUplinkReducer:
             raise NotImplementedError("this library build has no flc_randk_shift_reduce")
         if sparse and alpha is not None and shift_out is None:
             raise NotImplementedError("ShiftUplinkReducer: sparse=True updates the shift in place (shift_out = shift = b)")
+        if batched and not hasattr(lib, "flc_topk_shift_reduce"):
+            raise NotImplementedError("this library build has no flc_topk_shift_reduce")
+        if batched and alpha is not None and shift_out is None:
+            raise NotImplementedError("ShiftUplinkReducer: batched=True updates the shift in place (shift_out = shift = b)")
         dev = self.device
         for name, v in (("a", a), ("b", b), ("base", base), ("msg_out", msg_out), ("shift", shift),
                         ("shift_out", shift_out), ("out", out)):
@@ -393,6 +417,13 @@ class ShiftUplinkReducer:
                                                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
                                                 ws.numel(), _lib.stream_ptr(dev))
             _lib.check(rc, "flc_randk_shift_reduce")          # (a refusal: NotImplementedError with the reason)
+        elif d > 0 and batched:
+            ws = _lib.WORKSPACE.get(dev, lib.flc_topk_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
+            with torch.cuda.device(dev):
+                rc = lib.flc_topk_shift_reduce(ctypes.byref(prm), ctypes.byref(sr), n, d, ctypes.c_void_p(w_ptr),
+                                               ctypes.c_float(total), ctypes.c_void_p(out.data_ptr()),
+                                               ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
+            _lib.check(rc, "flc_topk_shift_reduce")           # (a refusal: NotImplementedError with the reason)
         elif d > 0:
             ws = _lib.WORKSPACE.get(dev, lib.flc_encode_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
             with torch.cuda.device(dev):

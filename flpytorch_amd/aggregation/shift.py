@@ -44,7 +44,8 @@ def dianaUplink(compressor, G, H, alpha, *, seed=None, **kw):
     ``m_i = C_i(G_i - H_i); H_i += alpha * m_i`` in place, and the fold ``(sum_i w_i m_i) / sum(w)``
     is returned — the server's ``gs`` before it adds its own shift — without storing any m_i.  Same
     bits as N ``dianaStep(in_place=True)`` calls and ``reduce_rows`` of their messages.  ``kw``:
-    ``ShiftUplinkReducer.__call__``'s weights / divisor / client0 / patterns / out / stream / sparse.
+    ``ShiftUplinkReducer.__call__``'s weights / divisor / client0 / patterns / out / stream / sparse /
+    batched.
 
     ``sparse=True`` (RandK only; anything else raises ``NotImplementedError``) runs the round through
     ``flc_randk_shift_reduce``: only the K selected elements of each ``H_i`` are read and written, work
@@ -52,7 +53,12 @@ def dianaUplink(compressor, G, H, alpha, *, seed=None, **kw):
     index set keeps its stored bits (the general call stores ``h + 0`` there: the same bits unless
     ``h`` is -0, which it turns into +0); selected elements and the returned fold have the general
     call's bits whenever ``H`` holds no -0 at an unselected place — always the case for shifts that
-    started as +0 and were only updated by these steps."""
+    started as +0 and were only updated by these steps.
+
+    ``batched=True`` (TopK only; anything else raises ``NotImplementedError``) runs the round through
+    ``flc_topk_shift_reduce``: all N differences, ONE many-row selection, a sparse epilogue and a list
+    fold instead of N lone selections in series.  The same untouched-elements contract and the same
+    bits as stated above for ``sparse=True``."""
     out, _, _ = _uplink(compressor, G, seed)(G, H, alpha=alpha, shift=H, shift_out=H, **kw)
     return out
 
@@ -62,7 +68,9 @@ def ef21Uplink(compressor, G, G_prev, *, seed=None, **kw):
     ``ef21Step``) and the fold of the new estimators is returned.  ``sparse=True`` (RandK only): only
     the K selected elements of each ``G_prev_i`` are written, then the updated rows are folded densely;
     unselected elements keep their stored bits (``dianaUplink``'s contract; the fold can then differ
-    from the general call's only in the sign of a zero, and only if ``G_prev`` held a -0)."""
+    from the general call's only in the sign of a zero, and only if ``G_prev`` held a -0).
+    ``batched=True`` (TopK only, a contractive compressor: ``mult`` is 1): the same round through
+    ``flc_topk_shift_reduce`` under the same contract."""
     mult = 1.0
     if not compressor.isContractionCompressor():
         mult = 1.0 / (1.0 + compressor.getW())
@@ -73,6 +81,7 @@ def ef21Uplink(compressor, G, G_prev, *, seed=None, **kw):
 def marinaUplink(compressor, G_cur, G_prev_rows, g_prev, *, seed=None, **kw):
     """The MARINA / PP-MARINA compressed round: the fold of ``g_prev + C_i(G_cur_i - G_prev_rows_i)``
     with ONE shared ``g_prev`` [D] vector; no message is stored.  ``sparse=True`` (RandK only): no row is
-    read outside its index set; the fold is bit-identical to the general call's without condition."""
+    read outside its index set; the fold is bit-identical to the general call's without condition.
+    ``batched=True`` (TopK only): the round through ``flc_topk_shift_reduce``, bit-identical as well."""
     out, _, _ = _uplink(compressor, G_cur, seed)(G_cur, G_prev_rows, base=g_prev, **kw)
     return out

@@ -230,6 +230,39 @@ int randk_lists_fold(int64_t n, int64_t d, int64_t K, void* wsp, const float* w,
 size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n, int64_t d);
 int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
                     const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+// shape C's fold of base + t over lists in the RkLists layout (k_randk_shift_lfold)
+int randk_shift_lfold_launch(const float* base, int64_t n, int64_t d, RkLists lists, const float* w, float wt, float* out,
+                             hipStream_t st);
+// The accepted shape of a sparse shifted round (flcodec.h: A DIANA in place, B EF21 in place, C one
+// shared base, D the plain fold), recognised by pointer and leading dimension, or -1 with the reason
+// set under the entry's name `me`.  sr: api.hip's normalised copy.
+enum { RKS_D = 0, RKS_A = 1, RKS_C = 2, RKS_B = 3 };
+int rks_shape(const flc_shift_rows& sr, const char* me);
+// The many-row TopK selection by itself (select.hip): after topk_lists_build row r's entries of chunk
+// c are ent_idx / ent_val[r * cap + tab[c * n + r].x + t], t < tab[c * n + r].y, and an entry is
+// admitted iff (mag_key(val), idx ^ txm) >= (T, cut) with T, cut taken from thr / flags / tiecut as
+// k_chunk_accum's load_meta takes them (flag TK_F_EXACT: every entry; TK_F_TIES: the tie cut).  A
+// caller may rewrite the entries and the admission state before topk_lists_fold (k_chunk_accum).
+// wsp: sel_workspace(prm, n, d) bytes, the carve of flc_encode_reduce.
+constexpr uint32_t TK_F_TIES = 4u, TK_F_EXACT = 8u;
+struct TkLists {
+    const uint2* tab;
+    uint32_t* ent_idx;
+    float* ent_val;
+    int64_t cap;
+    uint32_t* thr;
+    uint32_t* flags;
+    const uint32_t* tiecut;
+    uint32_t tie_hi;
+};
+int topk_lists_build(const flc_codec_params* prm, RowSrc rows, bool vec, int64_t n, int64_t d, void* wsp, size_t ws_bytes,
+                     TkLists* lists, hipStream_t st);
+int topk_lists_fold(const flc_codec_params* prm, int64_t n, int64_t d, void* wsp, const float* w, float wt, float* out,
+                    hipStream_t st);
+// the batched TopK shifted round (flc_topk_shift_reduce, topk_shift.hip)
+size_t topk_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
+int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt,
+                   float* out, void* ws, size_t ws_bytes, hipStream_t st);
 int randk_dense(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, float* out, void* ws,
                 size_t ws_bytes,
                 hipStream_t st);

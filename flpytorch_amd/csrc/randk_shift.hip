@@ -30,8 +30,6 @@
 
 namespace flc {
 
-enum { RKS_D = 0, RKS_A = 1, RKS_C = 2, RKS_B = 3 };
-
 struct RksArgs {
     const float* a; int64_t lda;
     float* b;       int64_t ldb;      // written at the members in shapes A (h') and B (m)
@@ -310,9 +308,9 @@ static int64_t rks_chunks(int64_t d) { return (d + CHUNK - 1) / CHUNK; }
 static int rks_blocks(int64_t items, int64_t cap) { return (int)std::max<int64_t>(1, std::min<int64_t>(items, cap)); }
 
 // The accepted shape of a round (flcodec.h), or -1 with the reason set.  sr: api.hip's normalised copy
-// (no shift_in without a shift_out, leading dimensions of absent operands zeroed).
-static int rks_shape(const flc_shift_rows& sr) {
-    const char* me = "flc_randk_shift_reduce";
+// (no shift_in without a shift_out, leading dimensions of absent operands zeroed).  Shared with the
+// batched TopK round (topk_shift.hip), whose entry accepts the same four shapes.
+int rks_shape(const flc_shift_rows& sr, const char* me) {
     if (!(std::isfinite(sr.msg_scale) && sr.msg_scale > 0.f)) {
         set_error("%s: msg_scale must be finite and > 0 (got %g)", me, (double)sr.msg_scale);
         return -1;
@@ -343,6 +341,15 @@ static int rks_shape(const flc_shift_rows& sr) {
     return RKS_D;
 }
 
+int randk_shift_lfold_launch(const float* base, int64_t n, int64_t d, RkLists L, const float* w, float wt, float* out,
+                             hipStream_t st) {
+    ProfScope _ps("k_randk_shift_lfold", st);
+    const int ab = rks_blocks((rks_chunks(d) * (CHUNK / RKS_CTS) + 3) / 4, 16384);
+    hipLaunchKernelGGL(k_randk_shift_lfold<RKS_CTS>, dim3(ab), dim3(256), 0, st, base, n, d, L, w, wt, out);
+    FLC_CHECK_LAUNCH("k_randk_shift_lfold");
+    return FLC_OK;
+}
+
 size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n, int64_t d) {
     if (n <= 0 || d <= 0) return 0;
     if (compat) return randk_lists_workspace(n, d, std::max<int64_t>(1, prm->k));
@@ -352,7 +359,7 @@ size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n
 int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
                     const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
     const char* me = "flc_randk_shift_reduce";
-    const int shape = rks_shape(sr);
+    const int shape = rks_shape(sr, me);
     if (shape < 0) return FLC_ERR_UNSUPPORTED;
     const bool compat = pat && pat->d_randk_idx;
     const int64_t K = prm->k;
@@ -393,11 +400,7 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
             FLC_CHECK_LAUNCH("k_randk_shift_lists");
         }
         if (shape != RKS_C) return randk_lists_fold(n, d, K, ws, w, wt, out, st);
-        ProfScope _ps("k_randk_shift_lfold", st);
-        const int ab = rks_blocks((C * (CHUNK / RKS_CTS) + 3) / 4, 16384);
-        hipLaunchKernelGGL(k_randk_shift_lfold<RKS_CTS>, dim3(ab), dim3(256), 0, st, sr.d_base, n, d, L, w, wt, out);
-        FLC_CHECK_LAUNCH("k_randk_shift_lfold");
-        return FLC_OK;
+        return randk_shift_lfold_launch(sr.d_base, n, d, L, w, wt, out, st);
     }
     const uint32_t* cnt = nullptr;
     const uint64_t* ckey = nullptr;

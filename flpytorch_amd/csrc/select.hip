@@ -4058,8 +4058,11 @@ int randk_lists_fold(int64_t n, int64_t d, int64_t K, void* wsp, const float* w,
     return launch_chunk_accum(n, d, carve_sel(wsp, FLC_RANDK, n, d, K, nullptr), false, w, wt, out, st);
 }
 
-int sel_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bool vec, int64_t n, int64_t d,
-            bool assign, const float* w, float wt, float* out, void* wsp, size_t ws_bytes, hipStream_t st) {
+// lists_only (topk_lists_build, TopK): everything up to the rows' final lists and admission state — no
+// lone-row path (assign false), no row-group folds, no final fold; the side stream is joined back to st
+static int sel_run_impl(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bool vec, int64_t n, int64_t d,
+                        bool assign, const float* w, float wt, float* out, void* wsp, size_t ws_bytes, hipStream_t st,
+                        bool lists_only) {
     const int codec = prm->codec;
     const int64_t K = prm->k;
     if (d == 0) return FLC_OK;
@@ -4151,7 +4154,7 @@ int sel_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bo
             const int TG = few ? 1 : tk_tail_groups(prm, n);
             // many rows: each group's select does its own exact fallback and its rows are folded
             // right after it (tiles carried in ws.part), under the next group's filter
-            gfold = FLC_TK_GFOLD && !few && !assign && !dense_k;
+            gfold = FLC_TK_GFOLD && !few && !assign && !dense_k && !lists_only;
             hipStream_t sside = st;
             TkCtx* cx = nullptr;
             std::unique_lock<std::mutex> lk;
@@ -4300,6 +4303,7 @@ if (vec) hipLaunchKernelGGL((k_topk_filter<true, true>), dim3(gb), dim3(256), 0,
     }
     // Every row's list now holds exactly its admitted entries plus, on the fast path, candidates
     // below the exact threshold; k_chunk_accum admits key >= thr.
+    if (lists_only) return FLC_OK;
     if (lone_assign) {
         // output zeros written by the filter; exact fallback (if the row failed) + scatter
         ProfScope _ps("k_assign_finish", st);
@@ -4317,6 +4321,39 @@ if (vec) hipLaunchKernelGGL((k_topk_filter<true, true>), dim3(gb), dim3(256), 0,
         return FLC_OK;
     }
     return launch_chunk_accum(n, d, ws, assign, w, wt, out, st);
+}
+
+int sel_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bool vec, int64_t n, int64_t d,
+            bool assign, const float* w, float wt, float* out, void* wsp, size_t ws_bytes, hipStream_t st) {
+    return sel_run_impl(prm, pat, rows, vec, n, d, assign, w, wt, out, wsp, ws_bytes, st, false);
+}
+
+// The many-row TopK selection on its own (topk_shift.hip: the batched shifted round turns the admitted
+// entries into messages between the selection and the fold).  build: sel_run's TopK branch over `rows`
+// up to the final lists, whichever regime (few rows, 2- / 4-chunk filter, dense K, exact fallback);
+// fold: k_chunk_accum over the lists and admission state as they then stand.
+int topk_lists_build(const flc_codec_params* prm, RowSrc rows, bool vec, int64_t n, int64_t d, void* wsp, size_t ws_bytes,
+                     TkLists* lists, hipStream_t st) {
+    if (prm->codec != FLC_TOPK) { set_error("topk_lists_build: TopK only"); return FLC_ERR_ARG; }
+    if (int rc = sel_run_impl(prm, nullptr, rows, vec, n, d, /*assign=*/false, nullptr, 1.f, nullptr, wsp, ws_bytes, st, true))
+        return rc;
+    const SelWs ws = carve_sel(wsp, FLC_TOPK, n, d, prm->k, nullptr);
+    lists->tab = ws.tab;
+    lists->ent_idx = ws.ent_idx;
+    lists->ent_val = ws.ent_val;
+    lists->cap = ws.cap;
+    lists->thr = ws.thr;
+    lists->flags = ws.flags;
+    lists->tiecut = ws.tiecut;
+    lists->tie_hi = prm->tie == FLC_TIE_HIGHEST ? 1u : 0u;
+    return FLC_OK;
+}
+
+int topk_lists_fold(const flc_codec_params* prm, int64_t n, int64_t d, void* wsp, const float* w, float wt, float* out,
+                    hipStream_t st) {
+    SelWs ws = carve_sel(wsp, FLC_TOPK, n, d, prm->k, nullptr);
+    ws.tie_hi = prm->tie == FLC_TIE_HIGHEST ? 1u : 0u;
+    return launch_chunk_accum(n, d, ws, false, w, wt, out, st);
 }
 
 // flc_select_row_flags: the rows' state words the last TopK sel_run left in the workspace

@@ -104,8 +104,9 @@ int shift_run(const flc_codec_params* prm, const flc_pattern* pat, const float* 
 // a message row (the workspace's, or the caller's d_msg row i), each followed by one fold step
 // into d_out — acc = first ? w m : acc + w m, divided after the last row.  Correct and bounded in
 // workspace, not a fast path (n selections, 2 n small launches).  RandK's in-place and store-free
-// rounds have their sparse entry (flc_randk_shift_reduce, randk_shift.hip: work ~ n K); a list-based
-// fold for TopK and Rank-K is future work.
+// rounds have their sparse entry (flc_randk_shift_reduce, randk_shift.hip: work ~ n K) and TopK's a
+// batched one over the many-row selection's lists (flc_topk_shift_reduce, topk_shift.hip); a
+// list-based fold for Rank-K is future work.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_shift_fold(const float* __restrict__ m, int64_t d, const float* __restrict__ w,
                                                     int64_t i, int last, float wt, float* __restrict__ acc) {

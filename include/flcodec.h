@@ -249,7 +249,8 @@ int flc_encode_shift(const flc_codec_params* prm, const flc_pattern* pat, const 
  * flc_encode_shift's path into a workspace row (or d_msg row i), each followed by a fold step into
  * d_out.  Correct and bounded in workspace (one message row + flc_encode_shift's own), NOT a fast
  * path: n selection passes and 2 n small launches.  d_randk_counts is ignored there.  RandK rounds
- * that store nothing or update in place have a sparse entry: flc_randk_shift_reduce below.
+ * that store nothing or update in place have a sparse entry, flc_randk_shift_reduce below, and TopK
+ * rounds of the same shapes a batched one, flc_topk_shift_reduce.
  *
  * Checked before any launch — FLC_ERR_ARG: null rows / d_a / d_b / d_out with n * d > 0,
  * n > FLC_MAX_ROWS, d_shift_out without d_shift_in, an output operand whose rows overlap
@@ -330,6 +331,69 @@ size_t flc_randk_shift_reduce_workspace_size(const flc_codec_params* prm, const 
 int flc_randk_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
                            int64_t n, int64_t d, const float* d_w, float w_total, float* d_out,
                            void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * Batched TopK shifted round (additive: flc_version() stays 104, detect the entry by its symbol).
+ * flc_encode_shift_reduce runs FLC_TOPK row by row: n lone selections, each with a dense encoded
+ * row, an epilogue and a fold step (about 48 n d bytes and 6 n launches in series).  This entry
+ * computes the same round for all n rows in a constant number of launches: the n differences are
+ * formed once into a workspace matrix (k_shift_sub_rows), the many-row TopK selection of
+ * flc_encode_reduce runs over that matrix, a sparse epilogue (k_topk_shift_lists) turns every
+ * selected entry into its message and in-place update, and the lists are folded: about
+ * 16 n d + 4 d bytes for an in-place DIANA round.  No flc_pattern: TopK draws nothing.
+ * Arithmetic, each operation rounded separately, in this order:
+ *     v = a_i[j] - b_i[j]
+ *     S_i = the K indices of largest |v| (key = the bits of |v|, NaN above inf), ties at the K-th
+ *           magnitude by prm->tie: exactly the set flc_encode_shift selects for that row
+ *     for j in S_i:  e = v;  t = e * msg_scale;  m = base ? base[j] + t : t;
+ *                    h' = shift_in[j] + shift_alpha * e
+ * d_out is folded in row order, the first term assigned, d_w == NULL meaning no multiply, one
+ * division by w_total at the end.
+ *
+ * Accepted shapes, recognised by pointer and leading dimension (those of flc_randk_shift_reduce):
+ *   A  DIANA / FRECON / COFIG in place: no base, no d_msg, d_shift_in == d_shift_out == d_b with
+ *      equal leading dimensions.  Only row i's K selected elements of h_i are written; d_out is the
+ *      fold of the sparse messages.
+ *   B  EF21 in place: d_base == d_msg == d_b with equal leading dimensions, no shift.  Only the K
+ *      selected elements of g_prev_i are written (the K-sparse scatter); d_out is then the dense fold
+ *      of the updated rows (flc_reduce_matrix's pass on the same stream: 4 n d bytes read).
+ *   C  MARINA: ONE shared [d] base (ldbase == 0), no d_msg, no shift.  d_out is the fold of
+ *      base + t_i; a row that did not select column j contributes exactly
+ *      w_i * (base[j] + 0.0f * msg_scale) (evaluated, not skipped).
+ *   D  the plain fold of C_i(a_i - b_i) * msg_scale: no base, no d_msg, no shift.
+ *
+ * THE CONTRACT that makes this an entry of its own: elements of an in-place operand (h_i in A,
+ * g_prev_i in B) OUTSIDE row i's index set are NOT WRITTEN.  flc_encode_shift_reduce stores
+ * x + (+0) there, which is x for every float except -0, which becomes +0.  Therefore
+ *   - every element of h_i' / g_next_i that row i selected has exactly flc_encode_shift's bits;
+ *   - every other element keeps its stored bits;
+ *   - if the in-place operand holds no -0 at an unselected place, the rows and d_out are
+ *     bit-identical to flc_encode_shift_reduce's.  That is the case whenever the operand started
+ *     as +0 and was only ever updated by these steps (a sum is -0 only when both operands are);
+ *   - if it does hold one, the row differs from the dense step only in that zero's sign, and in
+ *     shape B d_out can differ only in the sign of a zero;
+ *   - shapes C and D have no in-place operand: bit-identical to flc_encode_shift_reduce without
+ *     condition, the -0 columns of the fold included.
+ *
+ * FLC_ERR_UNSUPPORTED before any launch (the caller then uses flc_encode_shift_reduce): a codec
+ * other than FLC_TOPK (the size query then returns 0); any other operand shape (a dense output
+ * matrix, a per-row base that is not d_msg == d_b, a shift not in place over d_b); msg_scale, or
+ * shift_alpha with a shift, that is not finite and > 0 (a negative scale would turn the unselected
+ * +0 into -0).  FLC_ERR_ARG: null rows / d_a / d_b / d_out with n * d > 0, n > FLC_MAX_ROWS,
+ * negative n or d, K < 1 or K > d, d >= 0xFFFFFFFF, an unknown tie rule, in-place rows that overlap
+ * (|ldb| < d, n > 1).  FLC_ERR_WORKSPACE: ws_bytes below the size query.  n == 0 or d == 0: FLC_OK,
+ * the device is not touched.  A refused call writes nothing.
+ *
+ * Workspace, in this order: first the selection state exactly as flc_encode_reduce carves it for
+ * (FLC_TOPK, n, d, K) at the workspace base — flc_select_row_flags(prm, n, d, d_ws, ...) reports
+ * the rows' paths after this call as it does after the fused uplink (bits 1, 2 and 8; the
+ * epilogue consumes bit 4) — then the difference matrix [n][ldd], ldd = (d + 3) & ~3, 16-byte
+ * aligned.  Size <= flc_encode_reduce_workspace_size(prm, n, d) + 4 n ldd + 1 KiB.
+ * -------------------------------------------------------------------------------------- */
+size_t flc_topk_shift_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_topk_shift_reduce(const flc_codec_params* prm, const flc_shift_rows* rows, int64_t n, int64_t d,
+                          const float* d_w, float w_total, float* d_out,
+                          void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
  * Wire format: the message a client sends, and the server's decode +
@@ -462,7 +526,9 @@ int flc_selftest_division(const float* d_divisors, int n, unsigned long long* d_
  * Names: k_topk_filter, k_topk_sample, k_radix_hist, k_chunk_accum, k_ew_accum_vec,
  * k_norm_partials, k_reduce_vec, k_randk_scatter, k_ew_shift (flc_encode_shift's elementwise pass),
  * k_ew_shift_accum (flc_encode_shift_reduce's: one record per call), k_randk_shift (flc_randk_shift_reduce
- * with device draws: one record per call) and k_randk_shift_lists (its compat epilogue, one per call);
+ * with device draws: one record per call), k_randk_shift_lists (its compat epilogue, one per call),
+ * k_shift_sub_rows and k_topk_shift_lists (flc_topk_shift_reduce's difference pass and sparse epilogue:
+ * one record each per call);
  * the TopK filter's variant is recorded too
  * (k_topk_filter_g4: 4-chunk work items, the many-row path of large launches; k_topk_filter_g2:
  * 2-chunk items), so a test can assert which one ran.

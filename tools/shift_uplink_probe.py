@@ -32,6 +32,15 @@ interleaved in one process on one allocation; after every repeat the two outputs
 matrices must agree bit for bit (Gaussian shifts hold no -0).  The summary carries the 128-B line
 floor of the sparse round: the expected number of lines a row's K members touch, (D / 32) *
 (1 - (1 - K / D)^32), times 128 B, for a, for b and for the write-back, N rows.
+
+--topk (TopK specs, e.g. --specs topk:1%): the in-place DIANA round and the in-place EF21 round, each
+  batched    ShiftUplinkReducer(..., batched=True)                          flc_topk_shift_reduce
+  general    ShiftUplinkReducer(...) on its own copy of the in-place operand flc_encode_shift_reduce
+  yardstick  UplinkReducer's read-only TopK fold of the G rows alone (for scale)
+interleaved in one process on one allocation; after every repeat the two outputs and the two in-place
+matrices are compared as int32.  Byte model: batched 16 N D + 4 D (+ 4 N D for EF21's dense fold)
+against ~48 N D for the general entry's row loop.  Writes <out-dir>/<spec>_<shape>.jsonl
+(default out-dir with --topk: profiles/r11/topk_shift).
 """
 import argparse
 import json
@@ -149,6 +158,114 @@ def main_sparse(a):
         print("wrote", path, flush=True)
 
 
+def main_topk(a):
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d = a.n, a.d
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev).manual_seed(1000)
+
+    def filled():
+        t = torch.empty((n, d), dtype=torch.float32, device=dev)
+        for i in range(0, n, 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    G, H0 = filled(), filled()
+    Hb, Hg = torch.empty_like(H0), torch.empty_like(H0)
+    variants = ("batched", "general", "yardstick")
+    outs = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    kernels = ("k_shift_sub_rows", "k_topk_sample", "k_topk_filter", "k_cand_select", "k_topk_exact_rows",
+               "k_topk_shift_lists", "k_chunk_accum", "k_reduce_vec", "k_lone_resident")
+    for spec in a.specs.split(","):
+        if not spec.startswith("topk"):
+            raise SystemExit("--topk times TopK specs only")
+        for shape in a.shapes.split(","):
+            if shape not in ("diana", "ef21"):
+                raise SystemExit("--shapes: diana, ef21")
+            comp_b, comp_g, comp_y = (ag.initCompressor(spec, d) for _ in range(3))
+            k = comp_b.K
+            red_b = ag.ShiftUplinkReducer(comp_b, device=dev)
+            red_g = ag.ShiftUplinkReducer(comp_g, device=dev)
+            yard = ag.UplinkReducer(comp_y, device=dev)
+            Hb.copy_(H0)
+            Hg.copy_(H0)
+            if shape == "diana":
+                runs = {"batched": lambda: red_b(G, Hb, alpha=0.5, shift=Hb, shift_out=Hb, out=outs["batched"], batched=True),
+                        "general": lambda: red_g(G, Hg, alpha=0.5, shift=Hg, shift_out=Hg, out=outs["general"])}
+            else:
+                runs = {"batched": lambda: red_b(G, Hb, base=Hb, msg_out=Hb, out=outs["batched"], batched=True),
+                        "general": lambda: red_g(G, Hg, base=Hg, msg_out=Hg, out=outs["general"])}
+            runs["yardstick"] = lambda: yard(G, out=outs["yardstick"])
+            model = {"batched": (16 if shape == "diana" else 20) * n * d + 4 * d,
+                     "general": 48 * n * d,                # sub 12, select 8, epilogue 16, fold step 12
+                     "yardstick": 4 * n * d + 4 * d}
+            for f in runs.values():                        # warm: code objects, workspaces
+                f()
+            torch.cuda.synchronize()
+
+            def agree():
+                return (torch.equal(outs["batched"].view(torch.int32), outs["general"].view(torch.int32))
+                        and torch.equal(Hb.view(torch.int32), Hg.view(torch.int32)))
+            if not agree():
+                raise SystemExit(f"{spec} {shape}: the batched and the general round differ after the warm-up round")
+            ms = {v: [] for v in runs}
+            tag = spec.replace(":", "_").replace(".", "_").replace("%", "pct") + "_" + shape
+            path = os.path.join(a.out_dir, tag + ".jsonl")
+            with open(path, "w") as fh:
+                def emit(rec):
+                    line = json.dumps(rec)
+                    fh.write(line + "\n")
+                    fh.flush()
+                    print(line, flush=True)
+                for r in range(a.repeats):
+                    for v, f in runs.items():
+                        e0.record()
+                        for _ in range(a.steps):
+                            f()
+                        e1.record()
+                        e1.synchronize()
+                        t = e0.elapsed_time(e1) / a.steps
+                        ms[v].append(t)
+                        emit({"spec": spec, "shape": shape, "n": n, "d": d, "k": k, "repeat": r, "variant": v,
+                              "ms_per_call": round(t, 4), "model_bytes": model[v], "GBps": round(model[v] / t / 1e6, 1)})
+                    if not agree():
+                        raise SystemExit(f"{spec} {shape}: the batched and the general round differ after repeat {r}")
+                kms = {}
+                for v in variants:                         # the kernels' own times, one call each, outside the timed repeats
+                    _lib.profile_enable(True)
+                    for kn in kernels:
+                        _lib.profile_collect(kn)
+                    runs[v]()
+                    torch.cuda.synchronize()
+                    _lib.profile_enable(False)
+                    kms[v] = {kn: [round(t, 4), c] for kn in kernels for t, c in [_lib.profile_collect(kn)] if c}
+                if not agree():
+                    raise SystemExit(f"{spec} {shape}: the batched and the general round differ after the timer pass")
+                flags = ag.select_row_flags(comp_b, n, d)
+                med = {v: statistics.median(ms[v]) for v in runs}
+                emit({"spec": spec, "shape": shape, "n": n, "d": d, "k": k, "summary": True, "repeats": a.repeats,
+                      "steps": a.steps,
+                      "median_ms": {v: round(med[v], 4) for v in runs},
+                      "min_ms": {v: round(min(ms[v]), 4) for v in runs},
+                      "max_ms": {v: round(max(ms[v]), 4) for v in runs},
+                      "model_bytes": model,
+                      "GBps_of_model_at_median": {v: round(model[v] / med[v] / 1e6, 1) for v in runs},
+                      "general_over_batched": round(med["general"] / med["batched"], 3),
+                      "byte_model_general_over_batched": round(model["general"] / model["batched"], 3),
+                      "batched_over_yardstick": round(med["batched"] / med["yardstick"], 3),
+                      "batched_faster_beyond_spread": max(ms["batched"]) < min(ms["general"]),
+                      "bits_equal_every_repeat": True,
+                      "rows_on_exact_path_last_batched_call": int(((flags & 8) != 0).sum()),
+                      "kernel_ms_and_records_one_call": kms})
+            print("wrote", path, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--specs", default="natural,qsgd:127")
@@ -159,11 +276,17 @@ def main():
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles", "r09", "shift_uplink"))
     ap.add_argument("--fused-libs", default="")
     ap.add_argument("--sparse", action="store_true", help="RandK specs: flc_randk_shift_reduce against the general entry")
+    ap.add_argument("--topk", action="store_true", help="TopK specs: flc_topk_shift_reduce against the general entry")
+    ap.add_argument("--shapes", default="diana,ef21", help="--topk: the in-place rounds to time")
     a = ap.parse_args()
+    if a.topk and a.out_dir == ap.get_default("out_dir"):
+        a.out_dir = os.path.join(ROOT, "profiles", "r11", "topk_shift")
     if a.repeats < 1 or a.steps < 1 or a.n < 1 or a.d < 1:
         ap.error("--repeats, --steps, --n and --d are positive")
     if a.sparse:
         return main_sparse(a)
+    if a.topk:
+        return main_topk(a)
     import torch
 
     from flpytorch_amd import _lib
