@@ -42,6 +42,7 @@ EXPORTS = [
     "flc_encode_shift_reduce_workspace_size", "flc_encode_shift_reduce",
     "flc_randk_shift_reduce_workspace_size", "flc_randk_shift_reduce",
     "flc_topk_shift_reduce_workspace_size", "flc_topk_shift_reduce",
+    "flc_dither_shift_reduce_workspace_size", "flc_dither_shift_reduce", "flc_dither_row_flags",
     "flc_payload_bytes", "flc_payload_format", "flc_payload_validate", "flc_pack_workspace_size", "flc_pack", "flc_unpack",
     "flc_unpack_reduce_workspace_size", "flc_unpack_reduce",
     "flc_combine_workspace_size", "flc_combine_partials",
@@ -188,6 +189,12 @@ def _bind(lib):
         lib.flc_topk_shift_reduce_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
         lib.flc_topk_shift_reduce_workspace_size.restype = sz
         lib.flc_topk_shift_reduce.argtypes = [P(FlcCodecParams), P(FlcShiftRows), i64, i64, vp, f32, vp, vp, sz, vp]
+    if hasattr(lib, "flc_dither_shift_reduce"):     # (absent from A/B builds of older revisions)
+        lib.flc_dither_shift_reduce_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_dither_shift_reduce_workspace_size.restype = sz
+        lib.flc_dither_shift_reduce.argtypes = [P(FlcCodecParams), P(FlcPattern), P(FlcShiftRows), i64, i64, vp, f32,
+                                                vp, vp, vp, sz, vp]
+        lib.flc_dither_row_flags.argtypes = [i64, i64, vp, sz, vp, vp]
     lib.flc_payload_bytes.argtypes = [P(FlcCodecParams), i64]
     lib.flc_payload_bytes.restype = i64
     lib.flc_payload_format.argtypes = [P(FlcCodecParams)]
@@ -237,7 +244,8 @@ def _bind(lib):
                         "flc_encode_workspace_size", "flc_encode_reduce_workspace_size",
                         "flc_encode_reduce_ex_workspace_size", "flc_encode_shift_workspace_size",
                         "flc_encode_shift_reduce_workspace_size", "flc_randk_shift_reduce_workspace_size",
-                        "flc_topk_shift_reduce_workspace_size", "flc_payload_bytes", "flc_pack_workspace_size",
+                        "flc_topk_shift_reduce_workspace_size", "flc_dither_shift_reduce_workspace_size",
+                        "flc_payload_bytes", "flc_pack_workspace_size",
                         "flc_unpack_reduce_workspace_size", "flc_combine_workspace_size",
                         "flc_combine_blocks_workspace_size", "flc_device_randk_counts_workspace_size",
                         "flc_norm2_torch_cpu_workspace_size"):

@@ -256,10 +256,13 @@ class ShiftUplinkReducer:
             prm.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
         return prm, keep
 
-    def workspace_bytes(self, n, d, sparse=False, compat=False, batched=False):
+    def workspace_bytes(self, n, d, sparse=False, compat=False, batched=False, one_read=False):
         """``sparse``: flc_randk_shift_reduce's workspace (``compat``: with numpy-stream index rows);
-        ``batched``: flc_topk_shift_reduce's (the selection state, then the [n, d] difference matrix)."""
+        ``batched``: flc_topk_shift_reduce's (the selection state, then the [n, d] difference matrix);
+        ``one_read``: flc_dither_shift_reduce's (the sparse QSGD pipeline's state, no [n, d] matrix)."""
         prm, _ = self.params()
+        if one_read:
+            return _lib.load().flc_dither_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
         if batched:
             return _lib.load().flc_topk_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
         if sparse:
@@ -270,7 +273,7 @@ class ShiftUplinkReducer:
 
     def __call__(self, a, b, *, scale=1.0, base=None, msg_out=None, alpha=None, shift=None, shift_out=None, out=None,
                  weights=None, divisor=None, client0=0, randk_idx=None, uniforms=None, lazy_u=None, pnorms_out=None,
-                 stream=None, sparse=False, randk_counts=None, batched=False):
+                 stream=None, sparse=False, randk_counts=None, batched=False, one_read=False):
         """a, b: [N, D] fp32 row-contiguous device matrices (local gradients; shifts / previous
         estimators / previous gradients).  ``base``: None, [N, D], or ONE [D] vector for every row
         (MARINA's g_prev).  ``msg_out``: None (the messages are not stored) or [N, D]; it may be ``b``
@@ -286,7 +289,24 @@ class ShiftUplinkReducer:
         counts from ``UplinkReducer.randk_counts(n, d, client0)`` with the same seed, as in ``UplinkReducer``.
         ``batched=True``: the class docstring's TopK round (``NotImplementedError`` for another
         compressor, before any operand is looked at, or when the library refuses the shape — no silent
-        fallback; together with ``sparse``, ``pnorms_out`` or ``randk_counts`` it is a ``ValueError``)."""
+        fallback; together with ``sparse``, ``pnorms_out`` or ``randk_counts`` it is a ``ValueError``).
+        ``one_read=True``: the QSGD round (standard dithering with p = 2, device draws) through
+        ``flc_dither_shift_reduce``: a and b read once by the sparse QSGD pipeline over a - b, the
+        in-place operand written at the nonzero elements of C(a - b) only.  It takes the in-place DIANA
+        shape (``scale`` 1), the in-place EF21 shape and the plain fold (``scale`` 1) under the
+        untouched-elements contract of ``sparse=True`` with "selected" read as "encoded value nonzero";
+        ``pnorms_out`` is supported.  ``NotImplementedError`` for another compressor, before any operand
+        is looked at, or when the library refuses the call (MARINA's shared base, a dense path hint, a
+        candidate share past the staging capacity) — no silent fallback; together with ``sparse``,
+        ``batched``, ``uniforms`` or ``randk_counts`` it is a ``ValueError``."""
+        if one_read:
+            if sparse or batched or uniforms is not None or randk_counts is not None:
+                raise ValueError("ShiftUplinkReducer: one_read=True takes no sparse, batched, uniforms or randk_counts "
+                                 "(the QSGD round with device draws)")
+            if self.comp.compressorType != CompressorType.STANDARD_DITHERING_FP32 or getattr(self.comp, "p", None) != 2:
+                raise NotImplementedError("ShiftUplinkReducer: one_read=True is the QSGD round (standard dithering with "
+                                          f"p = 2, flc_dither_shift_reduce); this compressor is {self.comp.compressorType}"
+                                          f"{' with p = %s' % self.comp.p if hasattr(self.comp, 'p') else ''}")
         if batched:
             if sparse or pnorms_out is not None or randk_counts is not None:
                 raise ValueError("ShiftUplinkReducer: batched=True takes no sparse, pnorms_out or randk_counts "
@@ -299,7 +319,7 @@ class ShiftUplinkReducer:
         if randk_counts is not None and not sparse:
             raise ValueError("ShiftUplinkReducer: randk_counts is read by the sparse round only (sparse=True)")
         args = (a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx, uniforms,
-                lazy_u, pnorms_out, sparse, randk_counts, batched)
+                lazy_u, pnorms_out, sparse, randk_counts, batched, one_read)
         if stream is not None:
             if stream.device != self.device:
                 raise ValueError(f"stream is on {stream.device}, the reducer runs on {self.device}")
@@ -308,10 +328,14 @@ class ShiftUplinkReducer:
         return self._run(*args)
 
     def _run(self, a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx,
-             uniforms, lazy_u, pnorms_out, sparse=False, randk_counts=None, batched=False):
+             uniforms, lazy_u, pnorms_out, sparse=False, randk_counts=None, batched=False, one_read=False):
         lib = _lib.load()
         if not hasattr(lib, "flc_encode_shift_reduce"):
             raise NotImplementedError("this library build has no flc_encode_shift_reduce")
+        if one_read and not hasattr(lib, "flc_dither_shift_reduce"):
+            raise NotImplementedError("this library build has no flc_dither_shift_reduce")
+        if one_read and alpha is not None and shift_out is None:
+            raise NotImplementedError("ShiftUplinkReducer: one_read=True updates the shift in place (shift_out = shift = b)")
         if sparse and not hasattr(lib, "flc_randk_shift_reduce"):
             raise NotImplementedError("this library build has no flc_randk_shift_reduce")
         if sparse and alpha is not None and shift_out is None:
@@ -424,6 +448,15 @@ class ShiftUplinkReducer:
                                                ctypes.c_float(total), ctypes.c_void_p(out.data_ptr()),
                                                ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
             _lib.check(rc, "flc_topk_shift_reduce")           # (a refusal: NotImplementedError with the reason)
+        elif d > 0 and one_read:
+            ws = _lib.WORKSPACE.get(dev, lib.flc_dither_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
+            with torch.cuda.device(dev):
+                rc = lib.flc_dither_shift_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.byref(sr), n, d,
+                                                 ctypes.c_void_p(w_ptr), ctypes.c_float(total),
+                                                 ctypes.c_void_p(pnorms_out.data_ptr() if pnorms_out is not None else None),
+                                                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                                 ws.numel(), _lib.stream_ptr(dev))
+            _lib.check(rc, "flc_dither_shift_reduce")         # (a refusal: NotImplementedError with the reason)
         elif d > 0:
             ws = _lib.WORKSPACE.get(dev, lib.flc_encode_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
             with torch.cuda.device(dev):

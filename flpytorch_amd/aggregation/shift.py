@@ -58,7 +58,13 @@ def dianaUplink(compressor, G, H, alpha, *, seed=None, **kw):
     ``batched=True`` (TopK only; anything else raises ``NotImplementedError``) runs the round through
     ``flc_topk_shift_reduce``: all N differences, ONE many-row selection, a sparse epilogue and a list
     fold instead of N lone selections in series.  The same untouched-elements contract and the same
-    bits as stated above for ``sparse=True``."""
+    bits as stated above for ``sparse=True``.
+
+    ``one_read=True`` (QSGD, i.e. standard dithering with p = 2, device draws; anything else raises
+    ``NotImplementedError``) runs the round through ``flc_dither_shift_reduce``: ``G`` and ``H`` are read
+    once by the sparse QSGD pipeline over ``G_i - H_i`` and ``H_i`` is written only where
+    ``C_i(G_i - H_i)`` is nonzero.  The same contract with "selected" read as "encoded value nonzero";
+    ``ef21Uplink`` takes it too."""
     out, _, _ = _uplink(compressor, G, seed)(G, H, alpha=alpha, shift=H, shift_out=H, **kw)
     return out
 
@@ -82,6 +88,10 @@ def marinaUplink(compressor, G_cur, G_prev_rows, g_prev, *, seed=None, **kw):
     """The MARINA / PP-MARINA compressed round: the fold of ``g_prev + C_i(G_cur_i - G_prev_rows_i)``
     with ONE shared ``g_prev`` [D] vector; no message is stored.  ``sparse=True`` (RandK only): no row is
     read outside its index set; the fold is bit-identical to the general call's without condition.
-    ``batched=True`` (TopK only): the round through ``flc_topk_shift_reduce``, bit-identical as well."""
+    ``batched=True`` (TopK only): the round through ``flc_topk_shift_reduce``, bit-identical as well.
+    ``one_read=True`` raises ``NotImplementedError``: the one-read QSGD round does not take a shared base yet."""
+    if kw.get("one_read"):
+        raise NotImplementedError("marinaUplink: one_read=True (flc_dither_shift_reduce) does not take MARINA's shared "
+                                  "base yet; use the general round")
     out, _, _ = _uplink(compressor, G_cur, seed)(G_cur, G_prev_rows, base=g_prev, **kw)
     return out

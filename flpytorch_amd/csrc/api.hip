@@ -371,6 +371,40 @@ extern "C" int flc_topk_shift_reduce(const flc_codec_params* prm, const flc_shif
     return topk_shift_run(prm, sr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+extern "C" size_t flc_dither_shift_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (!prm || n < 0 || d < 0) return 0;
+    return dither_shift_workspace(prm, n, d);
+}
+
+extern "C" int flc_dither_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
+                                       int64_t n, int64_t d, const float* d_w, float w_total, float* d_pnorms_out,
+                                       float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_dither_shift_reduce";
+    if (!prm || prm->codec != FLC_STD_DITHERING || prm->norm != FLC_NORM_L2) {
+        set_error("%s: only FLC_STD_DITHERING with FLC_NORM_L2 (QSGD) has a one-read shifted round (use flc_encode_shift_reduce)", me);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) {
+        set_error("%s: n=%lld rows, at most %d per call (fold larger rounds as partials)", me, (long long)n, FLC_MAX_ROWS);
+        return FLC_ERR_ARG;
+    }
+    if (n == 0 || d == 0) return FLC_OK;
+    if (!rows || !rows->d_a || !rows->d_b || !d_out) { set_error("%s: need rows, a, b and out", me); return FLC_ERR_ARG; }
+    flc_shift_rows sr = *rows;
+    if (sr.d_shift_out && !sr.d_shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
+    if (!sr.d_shift_out) { sr.d_shift_in = nullptr; sr.ldin = sr.ldout = 0; }   // a shift nobody stores is not read
+    if (!sr.d_base) sr.ldbase = 0;
+    if (!sr.d_msg) sr.ldmsg = 0;
+    return dither_shift_run(prm, pat, sr, n, d, d_w, w_total, d_pnorms_out, d_out, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int flc_dither_row_flags(int64_t n, int64_t d, const void* d_ws, size_t ws_bytes, uint32_t* d_flags, void* stream) {
+    if (n < 0 || d < 0) { set_error("flc_dither_row_flags: n=%lld d=%lld", (long long)n, (long long)d); return FLC_ERR_ARG; }
+    if (n > 0 && d > 0 && (!d_ws || !d_flags)) { set_error("flc_dither_row_flags: null argument"); return FLC_ERR_ARG; }
+    return dither_row_flags(n, d, d_ws, ws_bytes, d_flags, (hipStream_t)stream);
+}
+
 extern "C" int64_t flc_payload_bytes(const flc_codec_params* prm, int64_t d) {
     if (!prm || !known(prm->codec) || d < 0) return 0;
     return payload_bytes(prm, d);

@@ -263,6 +263,18 @@ int topk_lists_fold(const flc_codec_params* prm, int64_t n, int64_t d, void* wsp
 size_t topk_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt,
                    float* out, void* ws, size_t ws_bytes, hipStream_t st);
+// the one-read QSGD shifted round (flc_dither_shift_reduce): dither_shift.hip decides on the host,
+// before any launch, whether the call is taken (else the refusal with its reason) and runs it;
+// dither_sparse.hip's ds_shift_run is the sparse pipeline over a - b with the in-place epilogues
+// (shape: RKS_A / RKS_B / RKS_D), ds_flags_at the DsWs.flags of a workspace
+size_t dither_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
+int dither_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
+                     const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+int dither_row_flags(int64_t n, int64_t d, const void* ws, size_t ws_bytes, uint32_t* flags, hipStream_t st);
+int ds_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int shape, int64_t n,
+                 int64_t d, const float* w, float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes,
+                 hipStream_t st);
+const uint32_t* ds_flags_at(const void* wsp, int64_t n, int64_t d);
 int randk_dense(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, float* out, void* ws,
                 size_t ws_bytes,
                 hipStream_t st);

@@ -162,17 +162,40 @@ __device__ inline uint32_t ds_hi8(uint32_t j, uint32_t rk) { return (grouphash(j
 __device__ inline float f32_up(double v) { float f = (float)v; return (double)f < v ? nextafterf(f, __builtin_huge_valf()) : f; }
 __device__ inline float f32_down(double v) { float f = (float)v; return (double)f > v ? nextafterf(f, 0.f) : f; }
 
+// The two-operand row source of the one-read shifted round (flc_dither_shift_reduce, DESIGN.md
+// §8.04): row i is the fp32 difference a_i - b_i, formed wherever the one-operand kernels use x.
+// k_ds_sample, k_ds_filter and k_ds_accum are templates on the source; everything after the filter
+// (k_ds_final, k_ds_resolve) works on entries, which carry the value's bits: v's here.
+struct DiffSrc {
+    RowSrc a, b;
+};
+struct RowRef {
+    const float* p;
+    __device__ inline float operator[](int64_t i) const { return p[i]; }
+};
+struct DiffRef {
+    const float* a;
+    const float* b;
+    __device__ inline float operator[](int64_t i) const { return a[i] - b[i]; }
+};
+__device__ inline RowRef row_ref(const RowSrc& s, int64_t i) { return RowRef{s.row(i)}; }
+__device__ inline DiffRef row_ref(const DiffSrc& s, int64_t i) { return DiffRef{s.a.row(i), s.b.row(i)}; }
+// the (first) operand's row through the scalar cache (RowSrc::row_s)
+__device__ inline const float* row_a(const RowSrc& s, int64_t i) { return s.row_s(i); }
+__device__ inline const float* row_a(const DiffSrc& s, int64_t i) { return s.a.row_s(i); }
+
 // ------------------------------------------------------------------------------------------
 // Sample: one workgroup per row.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(DS_SNT) void k_ds_sample(RowSrc rows, int64_t n, int64_t d, const float* __restrict__ levels,
+template <class SRC>
+__global__ __launch_bounds__(DS_SNT) void k_ds_sample(SRC rows, int64_t n, int64_t d, const float* __restrict__ levels,
                                                       int s, uint64_t seed, int64_t client0, DsWs ws, int64_t r_off, int wide) {
     constexpr int NW = DS_SNT / 64;
     __shared__ double r2[NW], r4[NW];
     const int64_t row = r_off + blockIdx.x;                               // (a launch may take a row range)
     if (row == 0) load_table(levels, s, ws.gtab);
     if (row >= n) return;
-    const float* r = rows.row(row);
+    const auto r = row_ref(rows, row);
     double a2 = 0.0, a4 = 0.0;
     int64_t S;
     if (d <= DS_SMAX) {
@@ -301,9 +324,27 @@ __device__ inline __amdgpu_buffer_rsrc_t chunk_ursrc(const double* u, int64_t j0
 // exact norm, not needed there) the float64 sums PER TORCH LANE go to tsum[row][item][8] — element
 // j of a row belongs to lane j % 8, i.e. lane 4 (t & 1) + q for thread t's q-th element of a
 // device-RNG step (4 t + 256 L + q) and 2 (t & 3) + (q & 1) for the compat filter's.
-template <int RING, int GCAP, int PROBE = 0, bool COMPAT = false, bool TNS = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FLC_DS_WPEC : FLC_DS_WPE))) void k_ds_filter(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_t rb, int64_t d, DsWs ws, UniformSrc us) {
+//
+// DIFF (SRC = DiffSrc, the one-read shifted round): the elements are v = a - b.  A ring slot holds
+// both operands' float4 of a step, so the ring is 8 pairs deep where the one-operand ring holds 16
+// float4 — the same 64 VGPRs and the same bytes in flight per wave — and the subtraction happens
+// at consumption.  b's chunk descriptors are range-checked like a's (both return 0 past the row
+// end: v = 0, dropped), and the item's fixed store sequence is unchanged.  Device draws and the
+// exact norm only.
+struct DSlot {
+    float4 a, b;
+};
+__device__ inline DSlot load_d(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb, int lane, int L) {
+    DSlot s;
+    s.a = load_q(ra, lane, L);
+    s.b = load_q(rb, lane, L);
+    return s;
+}
+template <int RING, int GCAP, int PROBE = 0, bool COMPAT = false, bool TNS = false, class SRC = RowSrc>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FLC_DS_WPEC : FLC_DS_WPE))) void k_ds_filter(SRC rows, int64_t n, int64_t r0, int64_t rn, int64_t rb, int64_t d, DsWs ws, UniformSrc us) {
     constexpr int FGS = DS_FGS, NH = DS_NH;
+    constexpr bool DIFF = std::is_same<SRC, DiffSrc>::value;
+    static_assert(!DIFF || (!COMPAT && !TNS && PROBE == 0 && !FLC_DS_PL), "two-operand source: the device-RNG, exact-norm filter only");
     static_assert(16 % RING == 0, "ring must divide the 16 loads of a chunk");
     static_assert(GCAP % 512 == 0 && (GCAP & (GCAP - 1)) == 0, "copy-out in whole 16-B wave slots; wrap mask");
     static_assert(!COMPAT || PROBE == 0, "probes: device-RNG filter only");
@@ -333,7 +374,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
     float* sgf = stagef[wv];
     // LDS byte address of the wave's staging buffer (wave-uniform)
     const uint32_t sla = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) uint2*)sg);
-    typedef typename std::conditional<COMPAT, CSlot, float4>::type Slot;
+    typedef typename std::conditional<COMPAT, CSlot, typename std::conditional<DIFF, DSlot, float4>::type>::type Slot;
     Slot ring[RING];
     // item order: blocks of rb rows (the last one shorter), and inside a block (gi, row) with the
     // row fastest: the waves in flight at any time read the same item of the block's rows, spread
@@ -348,13 +389,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
     int64_t row, gi0;
     item_at(it, row, gi0);
     int64_t c = gi0 * FGS;
-    auto rs = chunk_rsrc(rows.row_s(row), c * CHUNK, d);
+    auto rs = chunk_rsrc(row_a(rows, row), c * CHUNK, d);
     auto urow = [&](int64_t r) { return us.u + r * us.uld; };
-    auto ru = rs;
+    auto ru = rs;                                            // the second operand: compat u, DIFF b
     if constexpr (COMPAT) ru = chunk_ursrc(urow(row), c * CHUNK, d);
+    if constexpr (DIFF) ru = chunk_rsrc(rows.b.row_s(row), c * CHUNK, d);
 #pragma unroll
     for (int L = 0; L < RING - 1; ++L) {
         if constexpr (COMPAT) ring[L] = load_c(rs, ru, lane, L);
+        else if constexpr (DIFF) ring[L] = load_d(rs, ru, lane, L);
         else ring[L] = load_q(rs, lane, L);
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -383,17 +426,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
             const int64_t j0 = c * CHUNK;
             __amdgpu_buffer_rsrc_t rsn, run = ru;
             if (sub + 1 < FGS) {
-                rsn = chunk_rsrc(rows.row_s(row), j0 + CHUNK, d);
+                rsn = chunk_rsrc(row_a(rows, row), j0 + CHUNK, d);
                 if constexpr (COMPAT) run = chunk_ursrc(urow(row), j0 + CHUNK, d);
+                if constexpr (DIFF) run = chunk_rsrc(rows.b.row_s(row), j0 + CHUNK, d);
             } else if (nit < items) {
                 int64_t ngi;
                 item_at(nit, nrow, ngi);
                 nc = ngi * FGS;
-                rsn = chunk_rsrc(rows.row_s(nrow), nc * CHUNK, d);
+                rsn = chunk_rsrc(row_a(rows, nrow), nc * CHUNK, d);
                 if constexpr (COMPAT) run = chunk_ursrc(urow(nrow), nc * CHUNK, d);
+                if constexpr (DIFF) run = chunk_rsrc(rows.b.row_s(nrow), nc * CHUNK, d);
             } else {
-                    rsn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rows.row_s(row)), (short)0, 0, 0x00020000);
+                    rsn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(row_a(rows, row)), (short)0, 0, 0x00020000);
                     if constexpr (COMPAT) run = chunk_ursrc(urow(row), 0, 0);
+                    if constexpr (DIFF) run = chunk_rsrc(rows.b.row_s(row), 0, 0);   // no records: every load returns 0
                 }
                 if constexpr (COMPAT) {
                     // item-local index of (L, q): 4096 sub + 2 lane + 256 L + {0, 1, 128, 129}[q]
@@ -438,8 +484,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
 #pragma unroll
                 for (int L = 0; L < 16; ++L) {
                     const int P = L + RING - 1;
-                    ring[P % RING] = P < 16 ? load_q(rs, lane, P) : load_q(rsn, lane, P - 16);
-                    const float4 x = ring[L % RING];
+                    float4 x;
+                    if constexpr (DIFF) {
+                        // both operands of step P go out; step L's pair is subtracted here
+                        ring[P % RING] = P < 16 ? load_d(rs, ru, lane, P) : load_d(rsn, run, lane, P - 16);
+                        const DSlot sl = ring[L % RING];
+                        x = make_float4(sl.a.x - sl.b.x, sl.a.y - sl.b.y, sl.a.z - sl.b.z, sl.a.w - sl.b.w);
+                    } else {
+                        ring[P % RING] = P < 16 ? load_q(rs, lane, P) : load_q(rsn, lane, P - 16);
+                        x = ring[L % RING];
+                    }
                     uint32_t hg;
                     if (PROBE == 4) { hg = gb + (uint32_t)(L * 64) * 0x9E3779B1u; hg ^= hg >> 15; }   // cost probe only
                     else hg = gmix(gb + (uint32_t)(L * 64) * 0x9E3779B1u);
@@ -560,7 +614,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
 #pragma unroll 1
                     for (int e = 0; e < FGS * 64; ++e) {
                         const int sub = e >> 6, L = (e >> 2) & 15, q = e & 3;
-                        const auto rso = chunk_rsrc(rows.row_s(row), (cg + sub) * CHUNK, d);
+                        const auto rso = chunk_rsrc(row_a(rows, row), (cg + sub) * CHUNK, d);
                         const float x = ovl ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rso, lane * 16 + q * 4, L * 1024, 0)) : 0.f;
                         const uint32_t hg = gmix(lphi + (uint32_t)((cg + sub) * 1024 + L * 64) * 0x9E3779B1u + rk);
                         const float hi = (float)((hg >> (8 * q)) & 0xFFu);
@@ -1303,8 +1357,10 @@ constexpr int DS_AW = FLC_DS_AW;
 // waves per CU for this latency-bound walk (a 4-wave block with the table in LDS fit 3 per CU).
 // The row walk is a ring of AP rows' first 64 entries: row q's slot is refilled with row q + AP
 // as soon as q is folded, so a list load has AP - 1 rows of work in front of it.
-template <bool W, int AP, bool COMPAT>
-__global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int first, int last,
+// SRC = DiffSrc (the one-read shifted round): every place that reads a row — a dense row's
+// re-encode (in either ring form) and the sign-of-zero pass over the -0 columns — reads a - b.
+template <bool W, int AP, bool COMPAT, class SRC = RowSrc>
+__global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC rows, int64_t n, int64_t r0, int64_t rn, int first, int last,
                                                   int64_t d, DsWs ws, const float* __restrict__ levels, int s,
                                                   const float* __restrict__ w, float wt, float* __restrict__ part,
                                                   float* __restrict__ out, UniformSrc us) {
@@ -1527,13 +1583,14 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(RowSr
                 const uint32_t rk = ws.rk[row];
                 rr.rk2 = rk ^ 0x27D4EB2Fu;
                 rr.fast = (mode & DS_FAST) != 0u;
-                const float* rp = rows.row(row) + hbase;
+                const auto rp = row_ref(rows, row);
                 for (int k = 0; k < HCHUNK / 64; ++k) {
                     const uint32_t e = (uint32_t)(k * 64 + lane);
                     if (e < (uint32_t)len) {
                         const uint32_t j = hbase + e;
-                        const float ev = COMPAT ? ds_encode<true>(rp[e], j, 0u, us.u[row * us.uld + j], rr, tab, s, sf)
-                                                : ds_encode<false>(rp[e], j, ds_hi8(j, rk), 0.0, rr, tab, s, sf);
+                        const float xv = rp[(int64_t)hbase + e];
+                        const float ev = COMPAT ? ds_encode<true>(xv, j, 0u, us.u[row * us.uld + j], rr, tab, s, sf)
+                                                : ds_encode<false>(xv, j, ds_hi8(j, rk), 0.0, rr, tab, s, sf);
                         add(e, W ? wi * ev : ev);
                     }
                 }
@@ -1592,13 +1649,14 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(RowSr
                             const uint32_t rk = __builtin_amdgcn_readlane(cur.rk, q);
                             rr.rk2 = rk ^ 0x27D4EB2Fu;
                             rr.fast = (mode & DS_FAST) != 0u;
-                            const float* rp = rows.row(row) + hbase;
+                            const auto rp = row_ref(rows, row);
                             for (int k = 0; k < HCHUNK / 64; ++k) {
                                 const uint32_t e = (uint32_t)(k * 64 + lane);
                                 if (e < (uint32_t)len) {
                                     const uint32_t j = hbase + e;
-                                    const float ev = COMPAT ? ds_encode<true>(rp[e], j, 0u, us.u[row * us.uld + j], rr, tab, s, sf)
-                                                            : ds_encode<false>(rp[e], j, ds_hi8(j, rk), 0.0, rr, tab, s, sf);
+                                    const float xv = rp[(int64_t)hbase + e];
+                                    const float ev = COMPAT ? ds_encode<true>(xv, j, 0u, us.u[row * us.uld + j], rr, tab, s, sf)
+                                                            : ds_encode<false>(xv, j, ds_hi8(j, rk), 0.0, rr, tab, s, sf);
                                     add(e, W ? wi * ev : ev);
                                 }
                             }
@@ -1643,7 +1701,7 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(RowSr
             const bool mine = neg;
             for (int64_t i = 0; i < n && __ballot(neg) != 0ull; ++i) {
                 if (neg) {
-                    const float xv = rows.row(i)[hbase + e];
+                    const float xv = row_ref(rows, i)[hbase + e];
                     const bool zs = (xv != 0.f) && (__float_as_uint(xv) >> 31);
                     const bool ws_ = W && (__float_as_uint(w[i]) >> 31);
                     neg = zs != ws_;
@@ -1800,9 +1858,17 @@ static int ds_groups(const flc_codec_params* prm, int64_t n) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(g ? g : (n >= 128 ? 2 : 1), n));
 }
 
-int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d, const float* w,
-           float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes, hipStream_t st, const float* pnorm_in,
-           int norm_mode) {
+// The pipeline in two parts, as topk_lists_build / topk_lists_fold split the TopK one: the lists
+// (sample, filter, norm, resolve) and the fold (k_ds_accum).  The row-group pipeline interleaves the
+// two — group g's fold runs under group g + 1's filter — so they are one function with the fold
+// switched: fold == false issues every launch but k_ds_accum's and still joins the side stream back
+// into `st`, after which the lists, norms and flags in the workspace are final.  ds_run is
+// <RowSrc, fold>: its launches are what they were.  SRC = DiffSrc: device draws, the exact norm.
+template <class SRC>
+static int ds_run_t(const flc_codec_params* prm, const flc_pattern* pat, SRC rows, int64_t n, int64_t d, const float* w,
+                    float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes, hipStream_t st, const float* pnorm_in,
+                    int norm_mode, bool fold) {
+    constexpr bool DIFF = std::is_same<SRC, DiffSrc>::value;
     const DsVariant& v = ds_variant();
     // the rows' norms: the filter's partials (exact), the caller's, or torch's CPU order (tn)
     const bool tn = norm_mode == FLC_NORMMODE_TORCH_CPU && !pnorm_in;
@@ -1823,13 +1889,19 @@ int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int
     auto filter = [&](int64_t r0, int64_t rn, hipStream_t s2 = nullptr, bool beside = false) -> int {
         // s2: the row group's norm / resolve go to this stream (after an event on st), under the
         // next group's filter
-        auto kern = tns ? (!compat ? k_ds_filter<16, DS_GCAP, 0, false, true>
-                                   : v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true, true>)
-                  : compat ? (v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true>)
-                  : v.probe == 1 ? k_ds_filter<16, DS_GCAP, 1> : v.probe == 2 ? k_ds_filter<16, DS_GCAP, 2>
-                  : v.probe == 3 ? k_ds_filter<16, DS_GCAP, 3> : v.probe == 4 ? k_ds_filter<16, DS_GCAP, 4>
-                  : v.probe == 5 ? k_ds_filter<16, DS_GCAP, 5> : v.probe == 6 ? k_ds_filter<16, DS_GCAP, 6>
-                  : FLC_DS_V2 ? k_ds_filter2<16, FLC_DS2_CAP> : k_ds_filter<16, DS_GCAP>;
+        auto kern = [&] {
+            if constexpr (DIFF) {
+                return k_ds_filter<8, DS_GCAP, 0, false, false, DiffSrc>;      // 8 pairs: the 16-float4 ring's bytes
+            } else {
+                return tns ? (!compat ? k_ds_filter<16, DS_GCAP, 0, false, true>
+                                      : v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true, true>)
+                     : compat ? (v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true>)
+                     : v.probe == 1 ? k_ds_filter<16, DS_GCAP, 1> : v.probe == 2 ? k_ds_filter<16, DS_GCAP, 2>
+                     : v.probe == 3 ? k_ds_filter<16, DS_GCAP, 3> : v.probe == 4 ? k_ds_filter<16, DS_GCAP, 4>
+                     : v.probe == 5 ? k_ds_filter<16, DS_GCAP, 5> : v.probe == 6 ? k_ds_filter<16, DS_GCAP, 6>
+                     : FLC_DS_V2 ? k_ds_filter2<16, FLC_DS2_CAP> : k_ds_filter<16, DS_GCAP>;
+            }
+        }();
         int gw = (int)std::max<int64_t>(1, std::min<int64_t>((rn * ws.G + 3) / 4, 32768));
         // row groups (s2: the group's tail runs beside the next group's filter): the filter's
         // blocks reserve FLC_DS_LDSPAD more bytes of LDS, so one block fewer fits a CU and the
@@ -1859,14 +1931,16 @@ int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int
             // the group's norms in torch's order (k_tn_maps: the one extra read of its rows; with
             // k_tn_sums, the three-read composition, two), where the exact mode's k_ds_final
             // runs: under the next group's filter when there is one
-            if (int rc = tn_run(rows, n, r0, rn, d, ws.pn, tnws, tns ? ws.tsum : nullptr, ws.G, sr)) return rc;
+            if constexpr (!DIFF)
+                if (int rc = tn_run(rows, n, r0, rn, d, ws.pn, tnws, tns ? ws.tsum : nullptr, ws.G, sr)) return rc;
         }
+        { ProfScope _ps("k_ds_final", sr);
         if (tn || pnorm_in)
             hipLaunchKernelGGL(k_ds_final<true>, dim3((unsigned)((rn + 3) / 4)), dim3(256), 0, sr, r0, rn, ws, w, pnorm_out,
                                tn ? ws.pn : pnorm_in);
         else
             hipLaunchKernelGGL(k_ds_final<false>, dim3((unsigned)((rn + 3) / 4)), dim3(256), 0, sr, r0, rn, ws, w, pnorm_out,
-                               (const float*)nullptr);
+                               (const float*)nullptr); }
         FLC_CHECK_LAUNCH("k_ds_final");
         int rb = (int)std::max<int64_t>(1, std::min<int64_t>(((rn + 63) / 64 * ws.G + 3) / 4, 8192));
         // beside the next group's filter: a bounded grid (grid-stride), so the side kernel holds a
@@ -1881,10 +1955,17 @@ int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int
     };
     auto accum = [&](int64_t r0, int64_t rn, int first, int last, hipStream_t s2, bool beside = false) -> int {
         int ab = (int)std::max<int64_t>(1, std::min<int64_t>((H + DS_AW - 1) / DS_AW, 32768));
+        if (!fold) return FLC_OK;                            // the lists only: the caller folds (or does not)
         if (beside && FLC_DS_SIDE_FOLD_WG > 0) ab = std::min(ab, FLC_DS_SIDE_FOLD_WG);
         ProfScope _ps("k_ds_accum", s2);
-        auto kern = w ? (compat ? k_ds_accum<true, DS_AP, true> : k_ds_accum<true, DS_AP, false>)
-                      : (compat ? k_ds_accum<false, DS_AP, true> : k_ds_accum<false, DS_AP, false>);
+        auto kern = [&] {
+            if constexpr (DIFF) {
+                return w ? k_ds_accum<true, DS_AP, false, DiffSrc> : k_ds_accum<false, DS_AP, false, DiffSrc>;
+            } else {
+                return w ? (compat ? k_ds_accum<true, DS_AP, true> : k_ds_accum<true, DS_AP, false>)
+                         : (compat ? k_ds_accum<false, DS_AP, true> : k_ds_accum<false, DS_AP, false>);
+            }
+        }();
         hipLaunchKernelGGL(kern, dim3(ab), dim3(64 * DS_AW), 0, s2, rows, n, r0, rn, first, last, d, ws, prm->d_levels, prm->s, w,
                            wt, ws.part, out, us);
         FLC_CHECK_LAUNCH("k_ds_accum");
@@ -1894,7 +1975,7 @@ int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int
     auto sample = [&](int64_t a, int64_t b, hipStream_t sx) -> int {
         if (b <= a) return FLC_OK;
         ProfScope _ps("k_ds_sample", sx);
-        hipLaunchKernelGGL(k_ds_sample, dim3((unsigned)(b - a)), dim3(DS_SNT), 0, sx, rows, n, d, prm->d_levels, prm->s, prm->seed,
+        hipLaunchKernelGGL(k_ds_sample<SRC>, dim3((unsigned)(b - a)), dim3(DS_SNT), 0, sx, rows, n, d, prm->d_levels, prm->s, prm->seed,
                            client0, ws, a, (tn || pnorm_in) ? 1 : 0);
         FLC_CHECK_LAUNCH("k_ds_sample");
         return FLC_OK;
@@ -1974,6 +2055,171 @@ int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int
     }
     FLC_CHECK_HIP(hipEventRecord(cx.ev[K], cx.side));
     FLC_CHECK_HIP(hipStreamWaitEvent(st, cx.ev[K], 0));
+    return FLC_OK;
+}
+
+int ds_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d, const float* w,
+           float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes, hipStream_t st, const float* pnorm_in,
+           int norm_mode) {
+    return ds_run_t<RowSrc>(prm, pat, rows, n, d, w, wt, pnorm_out, out, wsp, ws_bytes, st, pnorm_in, norm_mode, /*fold=*/true);
+}
+
+// ------------------------------------------------------------------------------------------
+// The one-read shifted round's epilogues (flc_dither_shift_reduce, dither_shift.hip; DESIGN.md
+// §8.04): after the lists of the differences v_i = a_i - b_i are final, the in-place operand is
+// updated at the elements whose encoded value e is nonzero, and nowhere else:
+//     shape A (DIANA)  b_i[j] = b_i[j] + alpha * e        shape B (EF21)  b_i[j] = b_i[j] + e * msg_scale
+// each operation rounded separately, e exactly the value k_ds_accum folds.
+// ------------------------------------------------------------------------------------------
+struct DsShift {
+    const float* a; int64_t lda;
+    float* b;       int64_t ldb;      // the in-place operand: h_i (A) or g_prev_i (B)
+    float ms;                         // msg_scale
+    float alpha;                      // shift_alpha
+};
+
+__device__ inline float ds_shift_upd(int mode, float bv, float e, const DsShift& g) {
+    return mode == RKS_A ? bv + g.alpha * e : bv + e * g.ms;
+}
+
+// Sparse rows.  One wave per (half chunk h, 64-row batch): per row its list ent16[h][row][0 .. sure +
+// resolved), U rows' entry windows, then their gathers of b, then their stores in flight together.
+// Rows flagged dense have count 0 here (ds_meta) and are k_ds_shift_dense_rows'.  A row's entries
+// name distinct columns and every (h, row) list belongs to one wave, so the thread that gathered an
+// element stores it; a column at or past d is never stored to.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_ds_shift_lists(DsShift g, int64_t n, int64_t d, DsWs ws,
+                                                        const float* __restrict__ levels, int s) {
+    constexpr int U = 8;
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    __shared__ float lvl[DS_MAXLEV + 1];
+    if (threadIdx.x <= (unsigned)DS_MAXLEV) lvl[threadIdx.x] = (int)threadIdx.x <= s ? levels[threadIdx.x] : 0.f;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t H = nhalves(d), nb = (n + 63) / 64;
+    auto value = [&](uint32_t e, float pn) {                // k_ds_accum's: copysign(levels[lev], sign) * pnorm
+        const float lv = lvl[(e >> 12) & 15u];
+        return __uint_as_float(__float_as_uint(lv) | ((e & 0x800u) << 20)) * pn;
+    };
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wv; t < H * nb; t += (int64_t)gridDim.x * 4) {
+        const int64_t h = t / nb, r0 = (t - h * nb) * 64;
+        const int64_t hbase = h * HCHUNK;
+        const DsMeta m = ds_meta(ws, h, n, n, r0 + lane, nullptr);   // cnt: 0 for dense rows and past n
+        const uint64_t any = __ballot(m.cnt != 0u);
+        if (any == 0ull) continue;
+#pragma unroll 1
+        for (int q0 = 0; q0 < 64; q0 += U) {
+            if (((any >> q0) & ((1ull << U) - 1ull)) == 0ull) continue;
+            uint32_t en[U];
+            float bv[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t cnt = __builtin_amdgcn_readlane(m.cnt, q0 + u);
+                const int64_t row = min(r0 + q0 + u, n - 1);
+                en[u] = NONE;
+                if ((uint32_t)lane < cnt) en[u] = ws.ent16[(h * n + row) * DS_HCAP + lane];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t row = min(r0 + q0 + u, n - 1);
+                const int64_t j = hbase + (int64_t)(en[u] & (HCHUNK - 1));
+                if (en[u] != NONE && j >= d) en[u] = NONE;
+                bv[u] = 0.f;
+                if (en[u] != NONE) bv[u] = g.b[row * g.ldb + j];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t row = min(r0 + q0 + u, n - 1);
+                const float pn = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(m.pn), q0 + u));
+                if (en[u] != NONE) {
+                    const float e = value(en[u], pn);
+                    const int64_t j = hbase + (int64_t)(en[u] & (HCHUNK - 1));
+                    if (!(e == 0.f)) g.b[row * g.ldb + j] = ds_shift_upd(MODE, bv[u], e, g);
+                }
+            }
+            // the rest of a list longer than one window (rare)
+            for (int u = 0; u < U; ++u) {
+                const uint32_t cnt = __builtin_amdgcn_readlane(m.cnt, q0 + u);
+                if (cnt <= 64u) continue;
+                const int64_t row = r0 + q0 + u;
+                const float pn = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(m.pn), q0 + u));
+                for (uint32_t k = 64u + (uint32_t)lane; k < cnt; k += 64u) {
+                    const uint32_t ek = ws.ent16[(h * n + row) * DS_HCAP + k];
+                    const int64_t j = hbase + (int64_t)(ek & (HCHUNK - 1));
+                    const float e = value(ek, pn);
+                    if (j < d && !(e == 0.f)) {
+                        float* p = g.b + row * g.ldb + j;
+                        *p = ds_shift_upd(MODE, *p, e, g);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Dense rows.  The flags live on the device, so this is one launch whose workgroups leave at once
+// for rows without DS_DENSE.  A flagged row is encoded element by element with its norm — ds_encode,
+// k_ds_accum's dense re-encode — and the in-place element is stored where e is nonzero (NaN
+// included): the same contract whichever path a row took.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_ds_shift_dense_rows(DsShift g, int64_t n, int64_t d, DsWs ws, int s) {
+    const int64_t row = blockIdx.y;
+    if (row >= n) return;
+    const uint32_t mode = ws.flags[row];
+    if (!(mode & DS_DENSE)) return;
+    DsRow rr;
+    rr.n = ws.pn[row];
+    rr.rn = ws.rpn[row];
+    const uint32_t rk = ws.rk[row];
+    rr.rk2 = rk ^ 0x27D4EB2Fu;
+    rr.fast = (mode & DS_FAST) != 0u;
+    const float4* tab = ws.gtab;
+    const float sf = (float)s;
+    const float* ap = g.a + row * g.lda;
+    float* bp = g.b + row * g.ldb;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < d; j += (int64_t)gridDim.x * 256) {
+        const float bv = bp[j];
+        const float v = ap[j] - bv;
+        const float e = ds_encode<false>(v, (uint32_t)j, ds_hi8((uint32_t)j, rk), 0.0, rr, tab, s, sf);
+        if (!(e == 0.f)) bp[j] = ds_shift_upd(MODE, bv, e, g);
+    }
+}
+
+const uint32_t* ds_flags_at(const void* wsp, int64_t n, int64_t d) { return carve_ds(const_cast<void*>(wsp), n, d, nullptr).flags; }
+
+int ds_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int shape, int64_t n, int64_t d,
+                 const float* w, float wt, float* pnorm_out, float* out, void* wsp, size_t ws_bytes, hipStream_t st) {
+    const DiffSrc rows{RowSrc{sr.d_a, sr.lda, nullptr}, RowSrc{sr.d_b, sr.ldb, nullptr}};
+    // A and D: the fold of the messages (k_ds_accum over a - b) completes before either epilogue writes
+    // b — it re-reads a and b for dense rows and -0 columns — and ds_run_t returns with the row-group
+    // pipeline joined into st.  B folds the updated rows afterwards instead.
+    if (int rc = ds_run_t<DiffSrc>(prm, pat, rows, n, d, w, wt, pnorm_out, out, wsp, ws_bytes, st, nullptr, FLC_NORMMODE_EXACT,
+                                   /*fold=*/shape != RKS_B))
+        return rc;
+    if (shape != RKS_A && shape != RKS_B) return FLC_OK;
+    const DsWs ws = carve_ds(wsp, n, d, nullptr);
+    const DsShift g{sr.d_a, sr.lda, const_cast<float*>(sr.d_b), sr.ldb, sr.msg_scale, sr.shift_alpha};
+    {
+        ProfScope _ps("k_ds_shift_lists", st);
+        const int64_t waves = nhalves(d) * ((n + 63) / 64);
+        const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 65536)));
+        if (shape == RKS_A) hipLaunchKernelGGL(k_ds_shift_lists<RKS_A>, grid, dim3(256), 0, st, g, n, d, ws, prm->d_levels, prm->s);
+        else hipLaunchKernelGGL(k_ds_shift_lists<RKS_B>, grid, dim3(256), 0, st, g, n, d, ws, prm->d_levels, prm->s);
+        FLC_CHECK_LAUNCH("k_ds_shift_lists");
+    }
+    {
+        ProfScope _ps("k_ds_shift_dense_rows", st);
+        const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((d + 2047) / 2048, 256)), (unsigned)n);
+        if (shape == RKS_A) hipLaunchKernelGGL(k_ds_shift_dense_rows<RKS_A>, grid, dim3(256), 0, st, g, n, d, ws, prm->s);
+        else hipLaunchKernelGGL(k_ds_shift_dense_rows<RKS_B>, grid, dim3(256), 0, st, g, n, d, ws, prm->s);
+        FLC_CHECK_LAUNCH("k_ds_shift_dense_rows");
+    }
+    if (shape == RKS_B) {                                     // the dense fold of the updated rows
+        const bool vec = (((uintptr_t)sr.d_b & 15u) == 0) && (sr.ldb % 4 == 0);
+        const RowSrc brows{sr.d_b, sr.ldb, nullptr};
+        return reduce_impl(brows, vec, n, d, nullptr, w, wt, FLC_REDUCE_PLAIN, out, st);
+    }
     return FLC_OK;
 }
 

@@ -396,6 +396,63 @@ int flc_topk_shift_reduce(const flc_codec_params* prm, const flc_shift_rows* row
                           void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * One-read QSGD shifted round (additive: flc_version() stays 104, detect the entry by its symbol).
+ * flc_encode_shift_reduce runs FLC_STD_DITHERING in two full reads: the norms of the n differences
+ * (8 n d bytes), then the encode, which also stores every element of an in-place operand (12 n d
+ * bytes for DIANA in place).  This entry runs the round through the sparse QSGD pipeline of
+ * flc_encode_reduce with the difference a_i - b_i as its row: a and b are read once (norm and
+ * candidates in the same pass), and because C(v) is sparse the in-place operand is gathered and
+ * written at the nonzero elements only: 8 n d + 4 d bytes algorithmically for DIANA in place.
+ * Semantics are flc_encode_shift_reduce's for FLC_STD_DITHERING, FLC_NORM_L2, device draws, each
+ * operation rounded separately, in this order:
+ *     v = a_i[j] - b_i[j];  e = C_i(v);  t = e * msg_scale;  m = base ? base[j] + t : t;
+ *     h' = shift_in[j] + shift_alpha * e
+ * with the draws and row key of (prm->seed, pat->client0 + i) and the exactly rounded norm (the
+ * float64 sum of squares of v in a fixed order, rounded once; d_pnorms_out[n] receives it when not
+ * NULL).  d_out is folded in row order, the first term assigned, d_w == NULL meaning no multiply,
+ * one division by w_total at the end.
+ *
+ * Accepted shapes, recognised by pointer and leading dimension as flc_randk_shift_reduce does:
+ *   A  DIANA / FRECON / COFIG in place: no base, no d_msg, d_shift_in == d_shift_out == d_b with
+ *      equal leading dimensions, msg_scale == 1.0f.  d_out is the fold of the messages.
+ *   B  EF21 in place: d_base == d_msg == d_b with equal leading dimensions, no shift, any finite
+ *      msg_scale > 0.  g_prev_i[j] += e * msg_scale at the nonzero elements; d_out is then the dense
+ *      fold of the updated rows (flc_reduce_matrix's pass on the same stream).
+ *   D  the plain fold of C_i(a_i - b_i): no base, no d_msg, no shift, msg_scale == 1.0f.
+ *   (C, MARINA's one shared base, is refused: its fold needs the (index, value) list form.)
+ *
+ * THE CONTRACT is flc_randk_shift_reduce's with "selected" read as "e is nonzero": an element of
+ * the in-place operand whose encoded value is +-0 is NOT WRITTEN (flc_encode_shift_reduce stores
+ * x + 0 there: x for every float except -0); every written element has exactly flc_encode_shift's
+ * bits; if the operand holds no -0 where e is zero, the rows and d_out are bit-identical to
+ * flc_encode_shift_reduce's; shape D is identical without condition.
+ *
+ * FLC_ERR_UNSUPPORTED, decided on the host before any launch (the call writes nothing; the caller
+ * uses flc_encode_shift_reduce): a codec other than FLC_STD_DITHERING or a norm other than
+ * FLC_NORM_L2 (the size query then returns 0); pat->d_uniforms given (compat draws); the sparse
+ * path not taken for (prm, n, d) — FLC_PATH_DENSE, or no path hint and a candidate share
+ * 1.1 s / sqrt(d) + 0.003 past the staging capacity (FLC_PATH_SPARSE forces the path); shape C or
+ * any other operand shape; msg_scale != 1 in A or D; msg_scale, or shift_alpha with a shift, that
+ * is not finite and > 0.  FLC_ERR_ARG: null rows / d_a / d_b / d_out with n * d > 0, negative n or
+ * d, n > FLC_MAX_ROWS, d >= 0x7FFFFFFF, d_shift_out without d_shift_in, in-place rows that overlap
+ * (|ldb| < d, n > 1).  FLC_ERR_WORKSPACE: ws_bytes below the size query.  n == 0 or d == 0: FLC_OK,
+ * the device is not touched.
+ *
+ * Workspace: the sparse pipeline's state exactly as flc_encode_reduce carves it for (n, d), at the
+ * workspace base; no [n][d] matrix and no [d] message row.  A row whose norm falls outside its
+ * sampled bounds, or whose candidates overflow an item's staging, is flagged dense and takes the
+ * dense forms of the fold and of the epilogue: same bits, same contract.
+ * flc_dither_row_flags (test hook, no compute) copies the per-row flag words this entry left in
+ * d_ws — called with the same n and d — into d_flags[n] (device, on `stream`): bit 1 the row was
+ * folded dense, bit 4 its norm lies in the fast-division window.
+ * -------------------------------------------------------------------------------------- */
+size_t flc_dither_shift_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_dither_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
+                            int64_t n, int64_t d, const float* d_w, float w_total, float* d_pnorms_out,
+                            float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+int flc_dither_row_flags(int64_t n, int64_t d, const void* d_ws, size_t ws_bytes, uint32_t* d_flags, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * Wire format: the message a client sends, and the server's decode +
  * reduce straight from the N messages.  The reference counts these bits
  * (last_need_to_send_advance, compressors.py:223-224, 367-368) but moves the dense decoded
@@ -528,7 +585,9 @@ int flc_selftest_division(const float* d_divisors, int n, unsigned long long* d_
  * k_ew_shift_accum (flc_encode_shift_reduce's: one record per call), k_randk_shift (flc_randk_shift_reduce
  * with device draws: one record per call), k_randk_shift_lists (its compat epilogue, one per call),
  * k_shift_sub_rows and k_topk_shift_lists (flc_topk_shift_reduce's difference pass and sparse epilogue:
- * one record each per call);
+ * one record each per call), k_ds_sample / k_ds_filter / k_ds_final / k_ds_resolve / k_ds_accum (the sparse QSGD
+ * pipeline, one record per launch), k_ds_shift_lists and k_ds_shift_dense_rows (flc_dither_shift_reduce's
+ * sparse and dense-row epilogues: one record each per call in shapes A and B);
  * the TopK filter's variant is recorded too
  * (k_topk_filter_g4: 4-chunk work items, the many-row path of large launches; k_topk_filter_g2:
  * 2-chunk items), so a test can assert which one ran.

@@ -41,6 +41,14 @@ interleaved in one process on one allocation; after every repeat the two outputs
 matrices are compared as int32.  Byte model: batched 16 N D + 4 D (+ 4 N D for EF21's dense fold)
 against ~48 N D for the general entry's row loop.  Writes <out-dir>/<spec>_<shape>.jsonl
 (default out-dir with --topk: profiles/r11/topk_shift).
+
+--one-read (QSGD specs, default qsgd:127): the in-place DIANA round and the in-place EF21 round, each
+  one_read   ShiftUplinkReducer(..., one_read=True)                         flc_dither_shift_reduce
+  general    ShiftUplinkReducer(...) on its own copy of the in-place operand flc_encode_shift_reduce
+interleaved in one process on one allocation, device draws; after every repeat the two outputs and the
+two in-place matrices are compared as int32.  Byte model: one_read 8 N D + 4 D (+ 4 N D for EF21's dense
+fold) against 20 N D + 4 D; the summary carries the kernels' own times and the number of rows the
+one-read call folded dense.  Writes <out-dir>/<spec>_<shape>.jsonl (default profiles/r12/dither_shift).
 """
 import argparse
 import json
@@ -266,6 +274,120 @@ def main_topk(a):
             print("wrote", path, flush=True)
 
 
+def main_one_read(a):
+    import ctypes
+
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d = a.n, a.d
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev).manual_seed(1000)
+
+    def filled():
+        t = torch.empty((n, d), dtype=torch.float32, device=dev)
+        for i in range(0, n, 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    G, H0 = filled(), filled()
+    Ho, Hg = torch.empty_like(H0), torch.empty_like(H0)
+    variants = ("one_read", "general")
+    outs = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    kernels = ("k_ds_sample", "k_ds_filter", "k_ds_final", "k_ds_resolve", "k_ds_accum", "k_ds_shift_lists",
+               "k_ds_shift_dense_rows", "k_reduce_vec", "k_norm_partials", "k_ew_shift_accum")
+    for spec in a.specs.split(","):
+        if not spec.startswith("qsgd"):
+            raise SystemExit("--one-read times QSGD specs only")
+        for shape in a.shapes.split(","):
+            if shape not in ("diana", "ef21"):
+                raise SystemExit("--shapes: diana, ef21")
+            comp_o, comp_g = (ag.initCompressor(spec, d) for _ in range(2))
+            mult = 1.0 if comp_o.isContractionCompressor() else 1.0 / (1.0 + comp_o.getW())
+            red_o = ag.ShiftUplinkReducer(comp_o, device=dev, seed=SEED)
+            red_g = ag.ShiftUplinkReducer(comp_g, device=dev, seed=SEED)
+            Ho.copy_(H0)
+            Hg.copy_(H0)
+            if shape == "diana":
+                runs = {"one_read": lambda: red_o(G, Ho, alpha=0.5, shift=Ho, shift_out=Ho, out=outs["one_read"], one_read=True),
+                        "general": lambda: red_g(G, Hg, alpha=0.5, shift=Hg, shift_out=Hg, out=outs["general"])}
+            else:
+                runs = {"one_read": lambda: red_o(G, Ho, scale=mult, base=Ho, msg_out=Ho, out=outs["one_read"], one_read=True),
+                        "general": lambda: red_g(G, Hg, scale=mult, base=Hg, msg_out=Hg, out=outs["general"])}
+            # algorithmic bytes: a and b once (+ EF21's dense fold of the updated rows) against two reads and a full store
+            model = {"one_read": (8 if shape == "diana" else 12) * n * d + 4 * d, "general": 20 * n * d + 4 * d}
+            for f in runs.values():                        # warm: code objects, workspaces
+                f()
+            torch.cuda.synchronize()
+
+            def agree():
+                return (torch.equal(outs["one_read"].view(torch.int32), outs["general"].view(torch.int32))
+                        and torch.equal(Ho.view(torch.int32), Hg.view(torch.int32)))
+            if not agree():
+                raise SystemExit(f"{spec} {shape}: the one-read and the general round differ after the warm-up round")
+            ms = {v: [] for v in runs}
+            tag = spec.replace(":", "_").replace(".", "_") + "_" + shape
+            path = os.path.join(a.out_dir, tag + ".jsonl")
+            with open(path, "w") as fh:
+                def emit(rec):
+                    line = json.dumps(rec)
+                    fh.write(line + "\n")
+                    fh.flush()
+                    print(line, flush=True)
+                for r in range(a.repeats):
+                    for v, f in runs.items():
+                        e0.record()
+                        for _ in range(a.steps):
+                            f()
+                        e1.record()
+                        e1.synchronize()
+                        t = e0.elapsed_time(e1) / a.steps
+                        ms[v].append(t)
+                        emit({"spec": spec, "shape": shape, "n": n, "d": d, "repeat": r, "variant": v,
+                              "ms_per_call": round(t, 4), "model_bytes": model[v], "GBps": round(model[v] / t / 1e6, 1)})
+                    if not agree():
+                        raise SystemExit(f"{spec} {shape}: the one-read and the general round differ after repeat {r}")
+                kms = {}
+                for v in variants:                         # the kernels' own times, one call each, outside the timed repeats
+                    _lib.profile_enable(True)
+                    for kn in kernels:
+                        _lib.profile_collect(kn)
+                    runs[v]()
+                    torch.cuda.synchronize()
+                    _lib.profile_enable(False)
+                    kms[v] = {kn: [round(t, 4), c] for kn in kernels for t, c in [_lib.profile_collect(kn)] if c}
+                # the rows a one-read call folds dense: read from the stream's workspace before the next call reuses it
+                runs["one_read"]()
+                ws = _lib.WORKSPACE.get(dev, 0)
+                fl = torch.zeros(n, dtype=torch.int32, device=dev)
+                _lib.check(_lib.load().flc_dither_row_flags(n, d, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                                            ctypes.c_void_p(fl.data_ptr()), _lib.stream_ptr(dev)),
+                           "flc_dither_row_flags")
+                runs["general"]()                          # (keeps the two operands in step)
+                torch.cuda.synchronize()
+                if not agree():
+                    raise SystemExit(f"{spec} {shape}: the one-read and the general round differ after the timer pass")
+                med = {v: statistics.median(ms[v]) for v in runs}
+                emit({"spec": spec, "shape": shape, "n": n, "d": d, "summary": True, "repeats": a.repeats, "steps": a.steps,
+                      "median_ms": {v: round(med[v], 4) for v in runs},
+                      "min_ms": {v: round(min(ms[v]), 4) for v in runs},
+                      "max_ms": {v: round(max(ms[v]), 4) for v in runs},
+                      "model_bytes": model,
+                      "GBps_of_model_at_median": {v: round(model[v] / med[v] / 1e6, 1) for v in runs},
+                      "general_over_one_read": round(med["general"] / med["one_read"], 3),
+                      "byte_model_general_over_one_read": round(model["general"] / model["one_read"], 3),
+                      "line_granularity_model_general_over_one_read": 1.9 if shape == "diana" else None,
+                      "one_read_median_below_general_min": med["one_read"] < min(ms["general"]),
+                      "bits_equal_every_repeat": True,
+                      "dense_flagged_rows": int(((fl & 1) != 0).sum()),
+                      "kernel_ms_and_records_one_call": kms})
+            print("wrote", path, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--specs", default="natural,qsgd:127")
@@ -277,16 +399,23 @@ def main():
     ap.add_argument("--fused-libs", default="")
     ap.add_argument("--sparse", action="store_true", help="RandK specs: flc_randk_shift_reduce against the general entry")
     ap.add_argument("--topk", action="store_true", help="TopK specs: flc_topk_shift_reduce against the general entry")
-    ap.add_argument("--shapes", default="diana,ef21", help="--topk: the in-place rounds to time")
+    ap.add_argument("--one-read", action="store_true", help="QSGD specs: flc_dither_shift_reduce against the general entry")
+    ap.add_argument("--shapes", default="diana,ef21", help="--topk / --one-read: the in-place rounds to time")
     a = ap.parse_args()
     if a.topk and a.out_dir == ap.get_default("out_dir"):
         a.out_dir = os.path.join(ROOT, "profiles", "r11", "topk_shift")
+    if a.one_read and a.out_dir == ap.get_default("out_dir"):
+        a.out_dir = os.path.join(ROOT, "profiles", "r12", "dither_shift")
+    if a.one_read and a.specs == ap.get_default("specs"):
+        a.specs = "qsgd:127"
     if a.repeats < 1 or a.steps < 1 or a.n < 1 or a.d < 1:
         ap.error("--repeats, --steps, --n and --d are positive")
     if a.sparse:
         return main_sparse(a)
     if a.topk:
         return main_topk(a)
+    if a.one_read:
+        return main_one_read(a)
     import torch
 
     from flpytorch_amd import _lib
