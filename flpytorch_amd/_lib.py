@@ -45,6 +45,8 @@ EXPORTS = [
     "flc_dither_shift_reduce_workspace_size", "flc_dither_shift_reduce", "flc_dither_row_flags",
     "flc_payload_bytes", "flc_payload_format", "flc_payload_validate", "flc_pack_workspace_size", "flc_pack", "flc_unpack",
     "flc_unpack_reduce_workspace_size", "flc_unpack_reduce",
+    "flc_pack_shift_workspace_size", "flc_pack_shift",
+    "flc_unpack_shift_reduce_workspace_size", "flc_unpack_shift_reduce",
     "flc_combine_workspace_size", "flc_combine_partials",
     "flc_combine_blocks_workspace_size", "flc_combine_blocks",
     "flc_mt_choice", "flc_mt_rand", "flc_mt_randint31",
@@ -94,6 +96,18 @@ class FlcShiftRows(ctypes.Structure):
         ("shift_alpha", ctypes.c_float),
         ("d_shift_in", ctypes.c_void_p), ("ldin", ctypes.c_int64),
         ("d_shift_out", ctypes.c_void_p), ("ldout", ctypes.c_int64),
+    ]
+
+
+class FlcPayloadRows(ctypes.Structure):
+    """flc_payload_rows: the operands of flc_unpack_shift_reduce (payload i at d_payloads + i * ld_bytes
+    or d_payload_ptrs[i]; base / msg row i at ptr + i * ld, ldbase == 0: one shared [d] base)."""
+    _fields_ = [
+        ("d_payloads", ctypes.c_void_p), ("ld_bytes", ctypes.c_int64),
+        ("d_payload_ptrs", ctypes.c_void_p),
+        ("msg_scale", ctypes.c_float),
+        ("d_base", ctypes.c_void_p), ("ldbase", ctypes.c_int64),
+        ("d_msg", ctypes.c_void_p), ("ldmsg", ctypes.c_int64),
     ]
 
 
@@ -206,6 +220,14 @@ def _bind(lib):
     lib.flc_unpack_reduce_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
     lib.flc_unpack_reduce_workspace_size.restype = sz
     lib.flc_unpack_reduce.argtypes = [P(FlcCodecParams), vp, i64, vp, i64, i64, vp, f32, vp, vp, sz, vp]
+    if hasattr(lib, "flc_pack_shift"):              # (absent from A/B builds of older revisions)
+        lib.flc_pack_shift_workspace_size.argtypes = [P(FlcCodecParams), i64]
+        lib.flc_pack_shift_workspace_size.restype = sz
+        lib.flc_pack_shift.argtypes = [P(FlcCodecParams), P(FlcPattern), vp, vp, i64, f32, vp, vp, f32, vp, vp, vp,
+                                       vp, sz, vp]
+        lib.flc_unpack_shift_reduce_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_unpack_shift_reduce_workspace_size.restype = sz
+        lib.flc_unpack_shift_reduce.argtypes = [P(FlcCodecParams), P(FlcPayloadRows), i64, i64, vp, f32, vp, vp, sz, vp]
     lib.flc_combine_workspace_size.argtypes = [vp, i64, i32]
     lib.flc_combine_workspace_size.restype = sz
     lib.flc_combine_partials.argtypes = [vp, vp, i64, f32, i32, vp, sz, vp]
@@ -246,6 +268,7 @@ def _bind(lib):
                         "flc_encode_shift_reduce_workspace_size", "flc_randk_shift_reduce_workspace_size",
                         "flc_topk_shift_reduce_workspace_size", "flc_dither_shift_reduce_workspace_size",
                         "flc_payload_bytes", "flc_pack_workspace_size",
+                        "flc_pack_shift_workspace_size", "flc_unpack_shift_reduce_workspace_size",
                         "flc_unpack_reduce_workspace_size", "flc_combine_workspace_size",
                         "flc_combine_blocks_workspace_size", "flc_device_randk_counts_workspace_size",
                         "flc_norm2_torch_cpu_workspace_size"):

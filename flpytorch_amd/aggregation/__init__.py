@@ -7,9 +7,11 @@ classes whose reduction is the shared sequential fold (algorithms.py:1753-1768),
 """
 from .compressors import (Compressor, CompressorType, initCompressor, stream_choice, stream_rand,  # noqa: F401
                           stream_random, stream_randint31)
-from .fused import PayloadReducer, ShiftUplinkReducer, UplinkReducer, select_row_flags  # noqa: F401
+from .fused import (PayloadReducer, ShiftPayloadReducer, ShiftUplinkReducer, UplinkReducer,  # noqa: F401
+                    select_row_flags)
 from .mixed import MixedUplink  # noqa: F401
-from .shift import dianaStep, dianaUplink, ef21Step, ef21Uplink, marinaStep, marinaUplink  # noqa: F401
+from .shift import (dianaStep, dianaStepWire, dianaUplink, ef21Step, ef21StepWire, ef21Uplink, marinaStep,  # noqa: F401
+                    marinaStepWire, marinaUplink)
 from .reduce import (make_server_gradient_frecon, reduce_client_models, reduce_rows,  # noqa: F401
                      serverGradientCOFIG, serverGradientDIANA, serverGradientGradSkip, serverGradientMaster,
                      serverGradientPlain)

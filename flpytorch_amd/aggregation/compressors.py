@@ -522,16 +522,36 @@ class Compressor:
         (``msg`` None when ``message`` is False, ``shift_out`` None without ``alpha``).  ``out`` /
         ``shift_out`` may be any of the inputs (in-place update).  Updates the wire statistics
         like ``compressVector``.  Device tensors only (the client state lives on the GPU)."""
+        msg, hout, _ = self._shift("compressShift", a, b, scale, base, out, alpha, shift, shift_out, message, pnorm_out)
+        return msg, hout
+
+    def compressShiftPayload(self, a, b, *, scale=1.0, base=None, out=None, alpha=None, shift=None, shift_out=None,
+                             message=False, payload_out=None):
+        """``compressShift`` that also emits the message this client sends (flc_pack_shift): the payload
+        of ``compressVector(a - b)`` — byte for byte ``compressPayload(a - b)`` under the same pattern,
+        so ``decompressPayload(payload)`` is the compressed difference — written in the pass that
+        forms ``base + C(a - b) * scale`` and ``shift + alpha * C(a - b)``.  Both of those are optional
+        here (``message`` defaults to False; MARINA's client needs the payload only).  ``payload_out``:
+        a 16-byte aligned uint8 device tensor of ``payloadBytes()`` bytes that overlaps no operand.
+        Returns ``(payload, msg, shift_out)``; statistics advance like ``compressShift``."""
+        if not hasattr(_lib.load(), "flc_pack_shift"):
+            raise NotImplementedError("this library build has no flc_pack_shift")
+        msg, hout, payload = self._shift("compressShiftPayload", a, b, scale, base, out, alpha, shift, shift_out,
+                                         message or out is not None, None, True, payload_out)
+        return payload, msg, hout
+
+    def _shift(self, who, a, b, scale, base, out, alpha, shift, shift_out, message, pnorm_out, pack=False,
+               payload_out=None):
         for name, v in (("a", a), ("b", b), ("base", base), ("shift", shift), ("out", out),
                         ("shift_out", shift_out)):
             if v is not None and (v.dtype != torch.float32 or not v.is_cuda):
-                raise TypeError(f"compressShift: {name} must be an fp32 device tensor")
+                raise TypeError(f"{who}: {name} must be an fp32 device tensor")
         dev = _gpu_device(a)
         d = a.numel()
         if b.numel() != d or (base is not None and base.numel() != d) or (shift is not None and shift.numel() != d):
-            raise ValueError("compressShift: a, b, base and shift must have the same number of elements")
+            raise ValueError(f"{who}: a, b, base and shift must have the same number of elements")
         if alpha is not None and shift is None:
-            raise ValueError("compressShift: alpha given without a shift tensor")
+            raise ValueError(f"{who}: alpha given without a shift tensor")
         keep = []
 
         def flat(v):
@@ -547,24 +567,50 @@ class Compressor:
         if message:
             msg = out if out is not None else torch.empty_like(af)
             if not msg.is_contiguous():
-                raise ValueError("compressShift: out must be contiguous")
+                raise ValueError(f"{who}: out must be contiguous")
         hout = None
         if alpha is not None:
             hout = shift_out if shift_out is not None else torch.empty_like(hf)
             if not hout.is_contiguous():
-                raise ValueError("compressShift: shift_out must be contiguous")
-        if msg is None and hout is None:
-            raise ValueError("compressShift: nothing to compute (message=False and no alpha)")
+                raise ValueError(f"{who}: shift_out must be contiguous")
+        if msg is None and hout is None and not pack:
+            raise ValueError(f"{who}: nothing to compute (message=False and no alpha)")
+        if pack and msg is None and basef is not None:
+            raise ValueError(f"{who}: base given without a message (message=True or out)")
         lib = _lib.load()
         prm, k2 = self.codec_params(dev)
         keep.extend(k2)
         pat = self._pattern(dev, keep)
-        ws_bytes = lib.flc_encode_shift_workspace_size(ctypes.byref(prm), d)
-        ws = _lib.WORKSPACE.get(dev, ws_bytes)
         vp = ctypes.c_void_p
+        payload = None
+        if pack:
+            nbytes = int(lib.flc_payload_bytes(ctypes.byref(prm), d))
+            if payload_out is None:
+                payload = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            elif (payload_out.numel() < nbytes or payload_out.dtype != torch.uint8 or not payload_out.is_cuda
+                  or not payload_out.is_contiguous() or payload_out.data_ptr() % 16):
+                raise ValueError(f"{who}: payload_out must be a contiguous 16-byte aligned uint8 device tensor of "
+                                 "payloadBytes()")
+            else:
+                payload = payload_out
+            ws_bytes = lib.flc_pack_shift_workspace_size(ctypes.byref(prm), d)
+        else:
+            ws_bytes = lib.flc_encode_shift_workspace_size(ctypes.byref(prm), d)
+        ws = _lib.WORKSPACE.get(dev, ws_bytes)
 
         def ptr(v):
             return vp(v.data_ptr() if v is not None else None)
+        if pack:
+            with torch.cuda.device(dev):
+                rc = lib.flc_pack_shift(ctypes.byref(prm), ctypes.byref(pat), ptr(af), ptr(bf), d,
+                                        ctypes.c_float(float(np.float32(scale))), ptr(basef), ptr(msg),
+                                        ctypes.c_float(float(np.float32(alpha if alpha is not None else 0.0))),
+                                        ptr(hf if hout is not None else None), ptr(hout), ptr(payload),
+                                        vp(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
+            _lib.check(rc, "flc_pack_shift")
+            self._account(d)
+            return (msg.view(a.shape) if msg is not None else None,
+                    hout.view(shift.shape) if hout is not None else None, payload)
         with torch.cuda.device(dev):
             rc = lib.flc_encode_shift(ctypes.byref(prm), ctypes.byref(pat), ptr(af), ptr(bf), d,
                                       ctypes.c_float(float(np.float32(scale))), ptr(basef), ptr(msg),
@@ -577,7 +623,32 @@ class Compressor:
             msg = msg.view(a.shape)
         if hout is not None:
             hout = hout.view(shift.shape)
-        return msg, hout
+        return msg, hout, None
+
+    def decompressShiftPayload(self, payload, d=None, *, scale=1.0, base=None, out=None):
+        """The one-row server step of a shifted message: ``base + decompressPayload(payload) * scale``
+        (``decompressPayload(payload) * scale`` without a base), fp32 op for op — the n = 1 fold of
+        flc_unpack_shift_reduce with divisor 1.  ``out`` may be ``base`` (EF21's mirror in place).  A
+        host payload (off the network) crosses to the device first, as in ``decompressPayload``."""
+        from .fused import ShiftPayloadReducer
+        dev = _gpu_device(payload)
+        d = self._dim(d)
+        if payload.dtype != torch.uint8:
+            raise TypeError(f"decompressShiftPayload: payload must be uint8 (got {payload.dtype})")
+        nbytes = self.payloadBytes(d)
+        if payload.numel() < nbytes:
+            raise ValueError(f"decompressShiftPayload: {payload.numel()} bytes, the payload of d={d} is {nbytes}")
+        payload = payload.reshape(-1)[:nbytes].to(device=dev)
+        if not payload.is_contiguous() or payload.data_ptr() % 16:
+            payload = payload.clone()
+        for name, v in (("base", base), ("out", out)):
+            if v is not None and (v.dtype != torch.float32 or not v.is_cuda or v.numel() != d or not v.is_contiguous()):
+                raise ValueError(f"decompressShiftPayload: {name} must be a contiguous fp32 device tensor of {d} elements")
+        res = torch.empty(d, dtype=torch.float32, device=dev) if out is None else out.view(-1)
+        # the fold of one row with divisor 1 is the row: (m) / 1 == m, -0 included
+        ShiftPayloadReducer(self, device=dev)([payload], d, scale=scale, base=None if base is None else base.view(-1),
+                                              out=res, divisor=1.0)
+        return res if out is None else out
 
 
 def initCompressor(compressorCmdLine, D):

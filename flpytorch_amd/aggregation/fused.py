@@ -526,3 +526,105 @@ class PayloadReducer:
                                        ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
         _lib.check(rc, "flc_unpack_reduce")
         return out
+
+
+class ShiftPayloadReducer:
+    """Server side of a shifted round on the wire (flc_unpack_shift_reduce):
+
+        msg_i = base_i + decode(payload_i) * scale;   out = (sum_i w_i * msg_i) / sum(w)
+
+    folded in client order straight from the messages.  For payloads made by
+    ``Compressor.compressShiftPayload`` it leaves the ``out`` and the ``msg_out`` rows of
+    ``ShiftUplinkReducer`` (flc_encode_shift_reduce) over the rows they were packed from, bit for
+    bit.  Dense formats run one tile-owner pass (k_unpack_shift_accum); RandK / TopK payloads go row
+    by row through a dense workspace row (the dense round's bits, not a fast path).  Rank-K raises
+    ``NotImplementedError``."""
+
+    def __init__(self, compressor: Compressor, device=None):
+        _lib.require_gpu()
+        self.comp = compressor
+        self.device = _device(device)
+
+    def __call__(self, payloads, d=None, *, scale=1.0, base=None, msg_out=None, out=None, weights=None, divisor=None):
+        """payloads: [N, ld] uint8 device tensor (rows 16-byte aligned, ld % 16 == 0) or a list of N
+        16-byte aligned uint8 device tensors.  ``base``: None, [N, D], or ONE [D] vector for every row
+        (MARINA's g_prev).  ``msg_out``: None or [N, D]; it may be ``base`` (EF21's server mirror in
+        place).  ``weights`` / ``divisor`` as in ``PayloadReducer``.  Returns ``out``."""
+        lib = _lib.load()
+        if not hasattr(lib, "flc_unpack_shift_reduce"):
+            raise NotImplementedError("this library build has no flc_unpack_shift_reduce")
+        dev = self.device
+        d = self.comp._dim(d)
+        prm, keep = self.comp.codec_params(dev)
+        pr = _lib.FlcPayloadRows()
+        if torch.is_tensor(payloads) and payloads.dim() == 2:
+            n = payloads.shape[0]
+            if payloads.dtype != torch.uint8 or not payloads.is_cuda:
+                raise TypeError("ShiftPayloadReducer: payloads must be a uint8 device tensor")
+            if payloads.stride(1) != 1 or payloads.stride(0) % 16 or payloads.data_ptr() % 16:
+                raise ValueError("payload rows must be contiguous and 16-byte aligned")
+            pr.d_payloads, pr.ld_bytes = payloads.data_ptr(), payloads.stride(0)
+        else:
+            payloads = list(payloads)
+            n = len(payloads)
+            nbytes = int(lib.flc_payload_bytes(ctypes.byref(prm), d))
+            for p in payloads:
+                if not torch.is_tensor(p) or p.dtype != torch.uint8 or not p.is_cuda:
+                    raise TypeError("ShiftPayloadReducer: payloads must be uint8 device tensors")
+                if p.data_ptr() % 16 or not p.is_contiguous() or p.numel() < nbytes:
+                    raise ValueError(f"payloads must be contiguous, 16-byte aligned and hold {nbytes} bytes")
+            if n:
+                host_pt = torch.tensor([p.data_ptr() for p in payloads], dtype=torch.int64).pin_memory()
+                pt = host_pt.to(dev, non_blocking=True)
+                keep.extend(payloads)
+                keep.append(pt)
+                pr.d_payload_ptrs = pt.data_ptr()
+
+        def rows(name, v):
+            if v.dtype != torch.float32 or not v.is_cuda:
+                raise TypeError(f"ShiftPayloadReducer: {name} must be an fp32 device tensor")
+            if tuple(v.shape) != (n, d):
+                raise ValueError(f"ShiftPayloadReducer: {name} must be [{n}, {d}] (got {tuple(v.shape)})")
+            if d > 1 and v.stride(1) != 1:
+                raise ValueError(f"ShiftPayloadReducer: {name} must be row-contiguous")
+            return v.data_ptr(), v.stride(0)
+        if base is not None:
+            if base.dim() == 1:
+                if base.dtype != torch.float32 or not base.is_cuda:
+                    raise TypeError("ShiftPayloadReducer: base must be an fp32 device tensor")
+                if base.numel() != d or (d > 1 and base.stride(0) != 1):
+                    raise ValueError(f"ShiftPayloadReducer: a shared base must be a contiguous [{d}] vector")
+                pr.d_base, pr.ldbase = base.data_ptr(), 0
+            else:
+                pr.d_base, pr.ldbase = rows("base", base)
+                if n > 1 and pr.ldbase == 0:
+                    raise ValueError("ShiftPayloadReducer: pass a shared base as a [D] vector")
+        if msg_out is not None:
+            pr.d_msg, pr.ldmsg = rows("msg_out", msg_out)
+        pr.msg_scale = float(np.float32(scale))
+        if out is None:
+            out = torch.empty(d, dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or not out.is_cuda or out.numel() != d or not out.is_contiguous():
+            raise ValueError(f"ShiftPayloadReducer: out must be a contiguous fp32 device [{d}] vector")
+        w_ptr, total = None, float(n)
+        if weights is not None:
+            weights = [float(w) for w in weights]
+            if len(weights) != n:
+                raise ValueError(f"weights must hold {n} values")
+            if n:
+                total = weights[0]
+                for w in weights[1:]:
+                    total += w
+                wt = torch.tensor(weights, dtype=torch.float32, device=dev)
+                keep.append(wt)
+                w_ptr = wt.data_ptr()
+        if divisor is not None:
+            total = float(divisor)
+        ws_bytes = lib.flc_unpack_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
+        ws = _lib.WORKSPACE.get(dev, ws_bytes)
+        with torch.cuda.device(dev):
+            rc = lib.flc_unpack_shift_reduce(ctypes.byref(prm), ctypes.byref(pr), n, d, ctypes.c_void_p(w_ptr),
+                                             ctypes.c_float(total), ctypes.c_void_p(out.data_ptr()),
+                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, "flc_unpack_shift_reduce")
+        return out

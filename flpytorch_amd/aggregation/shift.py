@@ -31,6 +31,33 @@ def marinaStep(compressor, grad_cur, grad_prev, g_prev):
     return msg
 
 
+# -- the same steps emitting the message the client sends (flc_pack_shift) -------------------------
+def dianaStepWire(compressor, grad_cur, h, alpha, in_place=False):
+    """``dianaStep`` on the wire: returns ``(payload, h_new)`` — the payload decodes to ``m_i``
+    (``decompressShiftPayload(payload)``), written in the pass that updates the shift."""
+    payload, _, h_new = compressor.compressShiftPayload(grad_cur, h, alpha=alpha, shift=h,
+                                                        shift_out=h if in_place else None)
+    return payload, h_new
+
+
+def ef21StepWire(compressor, grad_cur, g_prev, in_place=False):
+    """``ef21Step`` on the wire: returns ``(payload, g_next)``; the server mirror applies
+    ``decompressShiftPayload(payload, scale=mult, base=g_prev)`` with the same ``mult``."""
+    mult = 1.0
+    if not compressor.isContractionCompressor():
+        mult = 1.0 / (1.0 + compressor.getW())
+    payload, msg, _ = compressor.compressShiftPayload(grad_cur, g_prev, scale=mult, base=g_prev,
+                                                      out=g_prev if in_place else None, message=True)
+    return payload, msg
+
+
+def marinaStepWire(compressor, grad_cur, grad_prev):
+    """MARINA's client on the wire: the payload of ``C(grad_cur - grad_prev)`` and nothing else (the
+    server adds it to its ``g_prev``: ``decompressShiftPayload(payload, base=g_prev)``)."""
+    payload, _, _ = compressor.compressShiftPayload(grad_cur, grad_prev)
+    return payload
+
+
 # -- a whole round of N resident clients in one call (flc_encode_shift_reduce) --------------------
 def _uplink(compressor, like, seed):
     from .fused import ShiftUplinkReducer

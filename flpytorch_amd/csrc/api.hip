@@ -460,6 +460,80 @@ extern "C" int flc_unpack_reduce(const flc_codec_params* prm, const void* d_payl
                              w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- shifted steps on the wire (wire_shift.hip) ----------------------------------------------------
+extern "C" size_t flc_pack_shift_workspace_size(const flc_codec_params* prm, int64_t d) {
+    if (!prm || !known(prm->codec) || prm->codec == FLC_RANK_K || d < 0) return 0;
+    return pack_shift_workspace(prm, d);
+}
+
+extern "C" int flc_pack_shift(const flc_codec_params* prm, const flc_pattern* pat, const float* d_a, const float* d_b,
+                              int64_t d, float msg_scale, const float* d_base, float* d_msg, float shift_alpha,
+                              const float* d_shift_in, float* d_shift_out, void* d_payload, void* d_ws, size_t ws_bytes,
+                              void* stream) {
+    const char* me = "flc_pack_shift";
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (prm->codec == FLC_RANK_K) { set_error("%s: Rank-K payloads are not carried by shifted steps", me); return FLC_ERR_UNSUPPORTED; }
+    if (int rc = bad_params(prm, me)) return rc;
+    if (d < 0) { set_error("%s: d < 0", me); return FLC_ERR_ARG; }
+    if (!d_payload) { set_error("%s: need a payload", me); return FLC_ERR_ARG; }
+    if ((uintptr_t)d_payload & 15u) { set_error("%s: payload must be 16-byte aligned", me); return FLC_ERR_ARG; }
+    if (d > 0 && (!d_a || !d_b)) { set_error("%s: need a and b", me); return FLC_ERR_ARG; }
+    if (d_shift_out && !d_shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
+    if (d_base && !d_msg) { set_error("%s: base without msg", me); return FLC_ERR_ARG; }
+    ShiftArgs sh{d_b, msg_scale, d_base, d_msg, shift_alpha, d_shift_out ? d_shift_in : nullptr, d_shift_out};
+    return pack_shift_run(prm, pat, d_a, d, sh, (char*)d_payload, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t flc_unpack_shift_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (!prm || !known(prm->codec) || prm->codec == FLC_RANK_K || n < 0 || d < 0) return 0;
+    return unpack_shift_reduce_workspace(prm, n, d);
+}
+
+extern "C" int flc_unpack_shift_reduce(const flc_codec_params* prm, const flc_payload_rows* rows, int64_t n, int64_t d,
+                                       const float* d_w, float w_total, float* d_out, void* d_ws, size_t ws_bytes,
+                                       void* stream) {
+    const char* me = "flc_unpack_shift_reduce";
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (prm->codec == FLC_RANK_K) { set_error("%s: Rank-K payloads are not carried by shifted steps", me); return FLC_ERR_UNSUPPORTED; }
+    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) {
+        set_error("%s: n=%lld payloads, at most %d per call (fold larger rounds as partials)", me, (long long)n, FLC_MAX_ROWS);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    if (d == 0) return FLC_OK;
+    if (!d_out) { set_error("%s: need out", me); return FLC_ERR_ARG; }
+    flc_payload_rows pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.msg_scale = 1.f;
+    if (n > 0) {
+        if (!rows || (!rows->d_payloads && !rows->d_payload_ptrs)) { set_error("%s: no payloads", me); return FLC_ERR_ARG; }
+        pr = *rows;
+        if (pr.d_payloads) {
+            pr.d_payload_ptrs = nullptr;
+            if ((uintptr_t)pr.d_payloads & 15u) { set_error("%s: payload rows must be 16-byte aligned", me); return FLC_ERR_ARG; }
+            if (pr.ld_bytes < payload_bytes(prm, d) || (pr.ld_bytes & 15)) {
+                set_error("%s: ld_bytes=%lld, at least the payload's %lld bytes and a multiple of 16", me,
+                          (long long)pr.ld_bytes, (long long)payload_bytes(prm, d));
+                return FLC_ERR_ARG;
+            }
+        }
+        if (!pr.d_base) pr.ldbase = 0;
+        if (!pr.d_msg) pr.ldmsg = 0;
+        if (pr.d_msg && n > 1 && (pr.ldmsg < 0 ? -pr.ldmsg : pr.ldmsg) < d) {
+            set_error("%s: the d_msg rows overlap (|ldmsg| < d)", me);
+            return FLC_ERR_ARG;
+        }
+        if (pr.d_base && pr.ldbase == 0 && n > 1 && pr.d_msg) {
+            // one base vector for every row: a message row over it would change it under the later rows
+            const uintptr_t b0 = (uintptr_t)pr.d_base, b1 = (uintptr_t)(pr.d_base + d);
+            uintptr_t lo, hi;
+            row_span(pr.d_msg, pr.ldmsg, n, d, &lo, &hi);
+            if (lo < b1 && b0 < hi) { set_error("%s: d_msg overlaps the shared base", me); return FLC_ERR_ARG; }
+        }
+    }
+    return unpack_shift_reduce_run(prm, pr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
 namespace flc {
 // the torch-order mode restates p = 2 of the dithering codecs; p = inf: a maximum, exact in any order
 static bool dithering(int codec) { return codec == FLC_STD_DITHERING || codec == FLC_NAT_DITHERING; }

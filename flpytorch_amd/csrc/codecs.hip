@@ -454,6 +454,83 @@ __global__ __launch_bounds__(256) void k_ew_shift(const float* __restrict__ a, i
 }
 
 // ------------------------------------------------------------------------------------------
+// The shifted step that emits its message (flc_pack_shift, dense formats): the union of k_ew_shift
+// and k_ew_code.  a and b (and base / h_in when given) are read once, e = C(a - b) is formed as
+// k_ew_shift forms it, turned into its wire code in registers as k_ew_code does (the F32 format
+// stores e itself) and applied to msg / h_out — QSGD with in-place DIANA: 8 d read, 4 d + 1 d
+// written after the norm pass.  The header's `bad` word is zeroed by the caller before the launch.
+// The payload overlaps no operand (the caller's contract); msg / h_out may alias a, b, base, h_in
+// as in k_ew_shift: every element is read and written by one thread, loads before stores.
+// ------------------------------------------------------------------------------------------
+template <class Op, bool VEC>
+__global__ __launch_bounds__(256) void k_ew_shift_code(const float* a, int64_t d, Op op,
+                                                       const float* __restrict__ levels, int s, ShiftArgs sh,
+                                                       CodeArgs ca) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem_tab[];
+    if (Op::TABLE) op.set_table_ok(load_table(levels, s, smem_tab));
+    op.setup(0);
+    PayloadHeader* h = reinterpret_cast<PayloadHeader*>(ca.payload);
+    char* body = ca.payload + 16;
+    const float norm = ca.pn ? *ca.pn : 0.f;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        h->fmt = (uint32_t)ca.fmt;
+        h->count = (uint32_t)d;
+        h->norm = norm;
+    }
+    const uint32_t sbit = ca.fmt == FMT_Q8 ? 0x80u : 0x8000u;
+    auto code = [&](float v) -> uint32_t {
+        return ca.fmt == FMT_NAT16 ? nat_code(v) : lev_code(v, ca.lv, ca.s, norm, sbit, &h->bad);
+    };
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t j0 = VEC ? (d / 4) * 4 : 0;
+    if (VEC) {
+        for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < d / 4; g += stride) {
+            uint32_t cs[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) cs[q] = op.col(g * 4 + q);
+            const float4 x = reinterpret_cast<const float4*>(a)[g];
+            const float4 y = reinterpret_cast<const float4*>(sh.b)[g];
+            float4 bs = make_float4(0.f, 0.f, 0.f, 0.f), hv = bs;
+            if (sh.msg && sh.base) bs = reinterpret_cast<const float4*>(sh.base)[g];
+            if (sh.hout) hv = reinterpret_cast<const float4*>(sh.hin)[g];
+            const float4 v = make_float4(x.x - y.x, x.y - y.y, x.z - y.z, x.w - y.w);
+            const float4 e = op.row_fast() ? apply4<true>(op, v, g * 4, cs, smem_tab)
+                                           : apply4<false>(op, v, g * 4, cs, smem_tab);
+            if (ca.fmt == FMT_F32) {
+                reinterpret_cast<float4*>(body)[g] = e;
+            } else {
+                const uint32_t c0 = code(e.x), c1 = code(e.y), c2 = code(e.z), c3 = code(e.w);
+                if (ca.fmt == FMT_Q8)
+                    reinterpret_cast<uint32_t*>(body)[g] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+                else
+                    reinterpret_cast<uint2*>(body)[g] = make_uint2(c0 | (c1 << 16), c2 | (c3 << 16));
+            }
+            if (sh.msg) {
+                const float4 t = make_float4(e.x * sh.scale, e.y * sh.scale, e.z * sh.scale, e.w * sh.scale);
+                reinterpret_cast<float4*>(sh.msg)[g] =
+                    sh.base ? make_float4(bs.x + t.x, bs.y + t.y, bs.z + t.z, bs.w + t.w) : t;
+            }
+            if (sh.hout)
+                reinterpret_cast<float4*>(sh.hout)[g] =
+                    make_float4(hv.x + sh.alpha * e.x, hv.y + sh.alpha * e.y, hv.z + sh.alpha * e.z, hv.w + sh.alpha * e.w);
+        }
+    }
+    for (int64_t j = j0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < d; j += stride) {
+        const float bs = (sh.msg && sh.base) ? sh.base[j] : 0.f;
+        const float hv = sh.hout ? sh.hin[j] : 0.f;
+        const float e = op.template apply<false>(a[j] - sh.b[j], j, op.col(j), smem_tab);
+        if (ca.fmt == FMT_F32) reinterpret_cast<float*>(body)[j] = e;
+        else if (ca.fmt == FMT_Q8) reinterpret_cast<uint8_t*>(body)[j] = (uint8_t)code(e);
+        else reinterpret_cast<uint16_t*>(body)[j] = (uint16_t)code(e);
+        if (sh.msg) {
+            const float t = e * sh.scale;
+            sh.msg[j] = sh.base ? bs + t : t;
+        }
+        if (sh.hout) sh.hout[j] = hv + sh.alpha * e;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Fused encode + reduce over N rows.  Tile owner: a thread owns COLS float4 column groups for
 // the whole launch and folds rows 0..N-1 into registers in order; PF rows are in flight
 // (a register ring with static indices), so each lane keeps PF*COLS*16 B of loads outstanding.
@@ -737,6 +814,24 @@ static int launch_shift(const float* a, int64_t d, Op op, const float* levels, i
     return FLC_OK;
 }
 
+// flc_pack_shift's pass: the vector kernel needs every operand in use 16-byte aligned (the payload
+// always is); one profile record per call
+template <class Op>
+static int launch_shift_code(const float* a, int64_t d, Op op, const float* levels, int s, const ShiftArgs& sh,
+                             const CodeArgs& ca, hipStream_t st) {
+    if (d == 0) return FLC_OK;
+    const uintptr_t al = (uintptr_t)a | (uintptr_t)sh.b | (uintptr_t)sh.base | (uintptr_t)sh.msg |
+                         (uintptr_t)sh.hin | (uintptr_t)sh.hout;
+    const bool vec = (al & 15u) == 0;
+    const size_t lds = Op::TABLE ? (size_t)s * sizeof(float4) : 0;
+    const int grid = grid_cap(vec ? (d + 3) / 4 : d, 256, 4096);
+    ProfScope _ps("k_ew_shift_code", st);
+    if (vec) hipLaunchKernelGGL((k_ew_shift_code<Op, true>), dim3(grid), dim3(256), lds, st, a, d, op, levels, s, sh, ca);
+    else hipLaunchKernelGGL((k_ew_shift_code<Op, false>), dim3(grid), dim3(256), lds, st, a, d, op, levels, s, sh, ca);
+    FLC_CHECK_LAUNCH("k_ew_shift_code");
+    return FLC_OK;
+}
+
 // tile shape of the accumulate kernel: COLS float4 columns per thread, PF rows in flight;
 // FLC_EW_TILE=<cols>x<pf> overrides (tuning runs only).
 static int ew_tile_variant() {
@@ -888,7 +983,7 @@ size_t ew_workspace(const flc_codec_params* prm, int64_t n, int64_t d, bool norm
     return b;
 }
 
-static int check_dither(const flc_codec_params* prm) {
+int check_dither(const flc_codec_params* prm) {
     if (prm->s < 1 || !prm->d_levels) { set_error("dithering: need s >= 1 and levels"); return FLC_ERR_ARG; }
     if (prm->s > 8192) { set_error("dithering: s=%d above the LDS level table (8192)", prm->s); return FLC_ERR_UNSUPPORTED; }
     if (prm->norm != FLC_NORM_L1 && prm->norm != FLC_NORM_L2 && prm->norm != FLC_NORM_LINF) {
@@ -955,6 +1050,7 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
     UniformSrc us{compat ? pat->d_uniforms : nullptr, (pat && pat->uniforms_ld) ? pat->uniforms_ld : d};
     auto go = [&](auto op, const float* levels, int s) -> int {
         if (sr) return launch_shift_accum(*sr, n, d, op, levels, s, w, wt, out, st);
+        if (sh && ca) return launch_shift_code(src.base, d, op, levels, s, *sh, *ca, st);
         if (sh) return launch_shift(src.base, d, op, levels, s, *sh, st);
         if (ca) return launch_code(src.base, d, op, levels, s, *ca, st);
         if (dense) return launch_dense(src.base, d, op, levels, s, out, st);

@@ -128,7 +128,8 @@ struct ShiftArgs {
     const float* hin;
     float* hout;
 };
-// flc_pack's fused encode -> code form (Q8 / Q16 / NAT16): payload header + body written directly
+// flc_pack's fused encode -> code form (Q8 / Q16 / NAT16): payload header + body written directly.
+// Together with ShiftArgs (flc_pack_shift, k_ew_shift_code) the F32 format is taken too: e itself.
 struct CodeArgs {
     int fmt;
     char* payload;
@@ -140,6 +141,8 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt, void* ws,
            size_t ws_bytes, hipStream_t st, const ShiftArgs* sh = nullptr, const CodeArgs* ca = nullptr,
            int norm_mode = FLC_NORMMODE_EXACT, const flc_shift_rows* sr = nullptr);
+// the dithering codecs' parameter check (s, levels, p-norm), before any launch
+int check_dither(const flc_codec_params* prm);
 size_t ew_shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 size_t shift_workspace(const flc_codec_params* prm, int64_t d);
 // the shifted fold over n rows (flc_encode_shift_reduce): the elementwise codecs in one tile-owner
@@ -175,6 +178,24 @@ int unpack_reduce_run(const flc_codec_params* prm, const char* base, int64_t ld,
                       int64_t d, const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
 int shift_run(const flc_codec_params* prm, const flc_pattern* pat, const float* a, int64_t d, const ShiftArgs& sh,
               float* pnorm_out, void* ws, size_t ws_bytes, hipStream_t st);
+// RandK / TopK / Rank-K: the dense row e = C(a - b) formed in the workspace (shift_workspace bytes),
+// the first half of shift_run; then its epilogue over a stored e and one step of the row-order fold
+int shift_encode_dense(const flc_codec_params* prm, const flc_pattern* pat, const float* a, const float* b, int64_t d,
+                       float** e_out, void* ws, size_t ws_bytes, hipStream_t st);
+int shift_epi_launch(const float* e, int64_t d, const ShiftArgs& sh, hipStream_t st);
+int shift_fold_launch(const float* m, int64_t d, const float* w, int64_t i, bool last, float wt, float* acc,
+                      hipStream_t st);
+// the SPARSE payload of a dense row (wire.hip k_pack_count / scan / write): bc holds pack_blocks(d)
+// counters, the payload is zeroed by the caller
+int64_t pack_blocks(int64_t d);
+int pack_sparse_launch(const float* dense, int64_t d, int64_t cap, uint32_t* bc, char* payload, hipStream_t st);
+// shifted steps on the wire (wire_shift.hip): flc_pack_shift / flc_unpack_shift_reduce
+size_t pack_shift_workspace(const flc_codec_params* prm, int64_t d);
+int pack_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const float* a, int64_t d, const ShiftArgs& sh,
+                   char* payload, void* ws, size_t ws_bytes, hipStream_t st);
+size_t unpack_shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
+int unpack_shift_reduce_run(const flc_codec_params* prm, const flc_payload_rows& pr, int64_t n, int64_t d,
+                            const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
 // Row g's boundary of G row groups whose last group is `lastpct` % of the others' size (the last
 // group's tail is the exposed one): rows [group_row(n, G, g), group_row(n, G, g + 1)).
 // lastpct is clamped to [1, 100]: 0 or less would leave the last group (the one whose fold writes

@@ -70,16 +70,24 @@ int shift_run(const flc_codec_params* prm, const flc_pattern* pat, const float* 
         return ew_run(prm, pat, s, vec, 1, d, nullptr, pnorm_out, /*dense=*/true, nullptr, nullptr, 1.f, ws, ws_bytes,
                       st, &sh);
     }
+    float* e = nullptr;
+    if (int rc = shift_encode_dense(prm, pat, a, sh.b, d, &e, ws, ws_bytes, st)) return rc;
+    return shift_epi_launch(e, d, sh, st);
+}
+
+int shift_encode_dense(const flc_codec_params* prm, const flc_pattern* pat, const float* a, const float* b, int64_t d,
+                       float** e_out, void* ws, size_t ws_bytes, hipStream_t st) {
+    (void)ws_bytes;
     Carver c(ws);
     float* diff = c.take<float>((size_t)d);
     float* e = c.take<float>((size_t)d);
     const size_t inner = inner_workspace(prm, d);
     void* iws = c.take<char>(inner);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((d + 1023) / 1024, 4096));
-    if ((((uintptr_t)a | (uintptr_t)sh.b) & 15u) == 0)
-        hipLaunchKernelGGL(k_shift_sub, dim3(grid), dim3(256), 0, st, a, sh.b, d, diff);
+    if ((((uintptr_t)a | (uintptr_t)b) & 15u) == 0)
+        hipLaunchKernelGGL(k_shift_sub, dim3(grid), dim3(256), 0, st, a, b, d, diff);
     else
-        hipLaunchKernelGGL(k_shift_sub_scalar, dim3(grid), dim3(256), 0, st, a, sh.b, d, diff);
+        hipLaunchKernelGGL(k_shift_sub_scalar, dim3(grid), dim3(256), 0, st, a, b, d, diff);
     FLC_CHECK_LAUNCH("k_shift_sub");
     int rc = FLC_OK;
     RowSrc r{diff, d, nullptr};
@@ -92,6 +100,11 @@ int shift_run(const flc_codec_params* prm, const flc_pattern* pat, const float* 
         rc = rk_run(prm, r, 1, d, /*reduce=*/false, nullptr, 1.f, e, iws, inner, st);
     }
     if (rc) return rc;
+    *e_out = e;
+    return FLC_OK;
+}
+
+int shift_epi_launch(const float* e, int64_t d, const ShiftArgs& sh, hipStream_t st) {
     const int g2 = (int)std::max<int64_t>(1, std::min<int64_t>((d + 255) / 256, 8192));
     hipLaunchKernelGGL(k_shift_epi, dim3(g2), dim3(256), 0, st, e, d, sh);
     FLC_CHECK_LAUNCH("k_shift_epi");
@@ -119,6 +132,14 @@ __global__ __launch_bounds__(256) void k_shift_fold(const float* __restrict__ m,
     }
 }
 
+int shift_fold_launch(const float* m, int64_t d, const float* w, int64_t i, bool last, float wt, float* acc,
+                      hipStream_t st) {
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((d + 255) / 256, 8192));
+    hipLaunchKernelGGL(k_shift_fold, dim3(grid), dim3(256), 0, st, m, d, w, i, last ? 1 : 0, wt, acc);
+    FLC_CHECK_LAUNCH("k_shift_fold");
+    return FLC_OK;
+}
+
 size_t shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
     if (shift_elementwise(prm->codec)) return ew_shift_reduce_workspace(prm, n, d);
     Carver c(nullptr);
@@ -142,7 +163,6 @@ int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const 
     float* mrow = c.take<float>((size_t)d);
     const size_t inner = shift_workspace(prm, d);
     void* iws = c.take<char>(inner);
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((d + 255) / 256, 8192));
     for (int64_t i = 0; i < n; ++i) {
         flc_pattern pi;
         memset(&pi, 0, sizeof(pi));
@@ -158,8 +178,7 @@ int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const 
         ShiftArgs sh{sr.d_b + i * sr.ldb, sr.msg_scale, sr.d_base ? sr.d_base + i * sr.ldbase : nullptr, m, sr.shift_alpha,
                      sr.d_shift_out ? sr.d_shift_in + i * sr.ldin : nullptr, sr.d_shift_out ? sr.d_shift_out + i * sr.ldout : nullptr};
         if (int rc = shift_run(prm, &pi, sr.d_a + i * sr.lda, d, sh, nullptr, iws, inner, st)) return rc;
-        hipLaunchKernelGGL(k_shift_fold, dim3(grid), dim3(256), 0, st, m, d, w, i, i == n - 1 ? 1 : 0, wt, out);
-        FLC_CHECK_LAUNCH("k_shift_fold");
+        if (int rc = shift_fold_launch(m, d, w, i, i == n - 1, wt, out, st)) return rc;
     }
     return FLC_OK;
 }

@@ -190,34 +190,6 @@ __global__ __launch_bounds__(256) void k_unpack_sparse(const char* __restrict__ 
 // NAT16 codes, 4 floats) for the whole fold, rows in order, PF rows' slices in flight (a register
 // ring), so the fp32 sum is the sequential one: acc = t_0; acc = acc + t_i; out = acc / wt with
 // t_i = w_i * dec_i.  Q8 level tables (<= 128 levels) sit in LDS.
-template <int FMT>
-struct WireFmt {
-    static constexpr int E = FMT == FMT_Q8 ? 16 : (FMT == FMT_F32 ? 4 : 8);
-    static constexpr int BYTES = 16 / E;
-};
-
-template <int FMT>
-__device__ inline float dec1(uint32_t c, const float* lv, int s, float norm) {
-    if (FMT == FMT_Q8) return lev_decode(c, lv, s, norm, 0x80u);
-    if (FMT == FMT_Q16) return lev_decode(c, lv, s, norm, 0x8000u);
-    if (FMT == FMT_NAT16) return nat_decode(c);
-    return __uint_as_float(c);
-}
-
-template <int FMT>
-__device__ inline void dec16(uint4 v, const float* lv, int s, float norm, float* e) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    constexpr int E = WireFmt<FMT>::E;
-#pragma unroll
-    for (int q = 0; q < E; ++q) {
-        uint32_t c;
-        if (FMT == FMT_Q8) c = (w[q >> 2] >> (8 * (q & 3))) & 0xFFu;
-        else if (FMT == FMT_F32) c = w[q];
-        else c = (w[q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
-        e[q] = dec1<FMT>(c, lv, s, norm);
-    }
-}
-
 template <int FMT, bool W, int PF>
 __global__ __launch_bounds__(256) void k_unpack_accum(const char* __restrict__ base, int64_t ld,
                                                       const char* const* __restrict__ ptrs, int64_t n, int64_t d,
@@ -321,6 +293,20 @@ size_t pack_workspace(const flc_codec_params* prm, int64_t d) {
 
 static bool natbug(const flc_codec_params* prm) { return prm->codec == FLC_NAT_DITHERING; }
 
+int64_t pack_blocks(int64_t d) { return std::max<int64_t>((d + PK_BLK - 1) / PK_BLK, 1); }
+
+// the SPARSE payload of a dense row (d > 0): its elements whose bits are not +0, ascending
+int pack_sparse_launch(const float* dense, int64_t d, int64_t cap, uint32_t* bc, char* payload, hipStream_t st) {
+    const int64_t nb = (d + PK_BLK - 1) / PK_BLK;
+    hipLaunchKernelGGL(k_pack_count, dim3((unsigned)nb), dim3(256), 0, st, dense, d, bc);
+    FLC_CHECK_LAUNCH("k_pack_count");
+    hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, st, bc, nb, payload, cap);
+    FLC_CHECK_LAUNCH("k_pack_scan");
+    hipLaunchKernelGGL(k_pack_write, dim3((unsigned)nb), dim3(256), 0, st, dense, d, bc, payload, cap);
+    FLC_CHECK_LAUNCH("k_pack_write");
+    return FLC_OK;
+}
+
 int pack_run(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, char* payload, void* ws,
              size_t ws_bytes, hipStream_t st) {
     if (ws_bytes < pack_workspace(prm, d)) { set_error("flc_pack: workspace too small"); return FLC_ERR_WORKSPACE; }
@@ -370,16 +356,8 @@ int pack_run(const flc_codec_params* prm, const flc_pattern* pat, const float* x
     int rc = encode_row(prm, pat, x, d, nullptr, dither ? w.pnorm : nullptr, w.dense, w.inner, w.inner_bytes, st);
     if (rc) return rc;
     (void)natbug;
-    if (fmt == FMT_SPARSE) {
-        const int64_t nb = (d + PK_BLK - 1) / PK_BLK, cap = std::max<int64_t>(1, std::min(prm->k, d));
-        hipLaunchKernelGGL(k_pack_count, dim3((unsigned)nb), dim3(256), 0, st, w.dense, d, w.bc);
-        FLC_CHECK_LAUNCH("k_pack_count");
-        hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, st, w.bc, nb, payload, cap);
-        FLC_CHECK_LAUNCH("k_pack_scan");
-        hipLaunchKernelGGL(k_pack_write, dim3((unsigned)nb), dim3(256), 0, st, w.dense, d, w.bc, payload, cap);
-        FLC_CHECK_LAUNCH("k_pack_write");
-        return FLC_OK;
-    }
+    if (fmt == FMT_SPARSE)
+        return pack_sparse_launch(w.dense, d, std::max<int64_t>(1, std::min(prm->k, d)), w.bc, payload, st);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((d + 255) / 256, 8192));
     hipLaunchKernelGGL(k_pack_dense, dim3(grid), dim3(256), 0, st, w.dense, d, fmt, prm->d_levels, prm->s,
                        dither ? w.pnorm : nullptr, payload);

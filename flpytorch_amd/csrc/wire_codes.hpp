@@ -70,4 +70,33 @@ __device__ inline float nat_decode(uint32_t c) {
     return copysignf(ldexpf(1.f, (int)m - 16384), sg);
 }
 
+// ---- one 16-B body slice of a dense format (the tile owners of wire.hip and wire_shift.hip) ----
+template <int FMT>
+struct WireFmt {
+    static constexpr int E = FMT == FMT_Q8 ? 16 : (FMT == FMT_F32 ? 4 : 8);
+    static constexpr int BYTES = 16 / E;
+};
+
+template <int FMT>
+__device__ inline float dec1(uint32_t c, const float* lv, int s, float norm) {
+    if (FMT == FMT_Q8) return lev_decode(c, lv, s, norm, 0x80u);
+    if (FMT == FMT_Q16) return lev_decode(c, lv, s, norm, 0x8000u);
+    if (FMT == FMT_NAT16) return nat_decode(c);
+    return __uint_as_float(c);
+}
+
+template <int FMT>
+__device__ inline void dec16(uint4 v, const float* lv, int s, float norm, float* e) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    constexpr int E = WireFmt<FMT>::E;
+#pragma unroll
+    for (int q = 0; q < E; ++q) {
+        uint32_t c;
+        if (FMT == FMT_Q8) c = (w[q >> 2] >> (8 * (q & 3))) & 0xFFu;
+        else if (FMT == FMT_F32) c = w[q];
+        else c = (w[q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
+        e[q] = dec1<FMT>(c, lv, s, norm);
+    }
+}
+
 }  // namespace flc

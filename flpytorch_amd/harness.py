@@ -202,10 +202,16 @@ class Simulation:
     def __init__(self, algorithm, client_compressor, model, x0, num_clients, clients_per_round, rounds,
                  local_lr, global_lr, local_iters=1, runtime_seed=0, device="cuda", sampling="uniform",
                  poisson_p=None, init_compressor=None, server_gradient=None, record_iterates=False, wire=False,
-                 initialize_shifts_policy="zero", diana_step=None, ef21_step=None, marina_step=None):
+                 initialize_shifts_policy="zero", diana_step=None, ef21_step=None, marina_step=None, shift_wire=False):
         algorithm = algorithm.lower()
         if algorithm not in ALGORITHMS:
             raise ValueError(f"harness drives {', '.join(ALGORITHMS)}, not {algorithm!r}")  # algorithms.py:1954 style
+        if shift_wire not in (False, True, "socket"):
+            raise ValueError(f"shift_wire must be False, True or 'socket' (got {shift_wire!r})")
+        if shift_wire and wire:
+            raise ValueError("wire and shift_wire are separate modes: pass one of them")
+        if shift_wire and algorithm not in ("diana", "ef21", "marina"):
+            raise ValueError("shift_wire drives the shifted steps' messages (diana, ef21, marina) only")
         if wire and algorithm != "dcgd":
             raise ValueError("wire mode drives DCGD's compressVector messages only")
         if initialize_shifts_policy not in ("zero", "full_gradient_at_start"):
@@ -229,7 +235,14 @@ class Simulation:
         if wire not in (False, True, "socket"):
             raise ValueError(f"wire must be False, True or 'socket' (got {wire!r})")
         self.wire = wire
-        self.link = transport.socket_pair() if wire == "socket" else None
+        # shift_wire=True (DIANA / EF21 / MARINA): every compressed client step ships its message
+        # C(a - b) as the wire payload, written by the pass that updates the client's state
+        # (Compressor.compressShiftPayload, flc_pack_shift), and the server side rebuilds the vector
+        # the local step applies from it (decompressShiftPayload: m_i; g_prev + dec * mult; g_prev +
+        # dec).  Uncompressed steps (EF21's first, MARINA's ck == 1) ship no payload, as without it.
+        # shift_wire="socket": the payload crosses the socket pair and is validated on arrival.
+        self.shift_wire = shift_wire
+        self.link = transport.socket_pair() if "socket" in (wire, shift_wire) else None
         self.iterates = []                                                       # x after each round (opt-in)
         self.init_compressor = init_compressor or ag.initCompressor
         self.diana_step = diana_step or _on_gpu(ag.dianaStep)
@@ -308,6 +321,8 @@ class Simulation:
                 c = comp.compressVector(g)
             cs["stats"]["send_scalars_to_master"] += comp.last_need_to_send_advance
             return c
+        if self.shift_wire:
+            return self.client_step_shift_wire(cs, comp, g)
         if self.algorithm == "diana":                                            # algorithms.py:1383-1392
             m, cs["hi"] = self.diana_step(comp, g, cs["hi"], self.H["alpha"])
             cs["stats"]["send_scalars_to_master"] += comp.last_need_to_send_advance
@@ -329,6 +344,46 @@ class Simulation:
         cs["stats"]["send_scalars_to_master"] += comp.last_need_to_send_advance
         cs["g_prev"] = g_next
         return g_next
+
+    def client_step_shift_wire(self, cs, comp, g):
+        """client_step's DIANA / EF21 / MARINA branches with the message on the wire: the client
+        half is one compressShiftPayload call, the server half one decompressShiftPayload call whose
+        result — bit for bit the plain step's — is what the local step applies."""
+        home, d = g.device, g.numel()
+
+        # the product's codec runs on the MI355X whatever device the client state lives on (like
+        # _on_gpu); another implementation of the protocol (a test's double) takes the tensors as they are
+        on_gpu = isinstance(comp, ag.Compressor)
+
+        def dev(t):
+            return t.cuda() if on_gpu and t.device.type != "cuda" else t
+
+        def ship(payload):
+            cs["stats"]["payload_bytes"] = cs["stats"].get("payload_bytes", 0) + payload.numel()
+            return self.transfer(comp, payload, d) if self.link is not None else payload
+        if self.algorithm == "diana":                                            # algorithms.py:1383-1392
+            h = dev(cs["hi"])
+            payload, _, h_new = comp.compressShiftPayload(dev(g), h, alpha=self.H["alpha"], shift=h)
+            cs["hi"] = h_new.to(home)
+            out = comp.decompressShiftPayload(ship(payload), d)
+        elif self.algorithm == "marina":                                         # algorithms.py:512-540
+            if cs["ck"] == 1:
+                cs["stats"]["send_scalars_to_master"] += d
+                return g
+            _, g_old = self.model.value_and_gradient(self.H["x_prev"], cs["client_id"])
+            payload, _, _ = comp.compressShiftPayload(dev(g), dev(g_old))
+            out = comp.decompressShiftPayload(ship(payload), d, base=dev(self.H["g_prev"].to(home)))
+        else:                                                                    # EF21, algorithms.py:1494-1518
+            if cs["g_prev"] is None:
+                cs["g_prev"] = g                                                 # (first step: not counted)
+                return g
+            mult = 1.0 if comp.isContractionCompressor() else 1.0 / (1.0 + comp.getW())
+            g_prev = dev(cs["g_prev"])
+            payload, g_next, _ = comp.compressShiftPayload(dev(g), g_prev, scale=mult, base=g_prev, message=True)
+            cs["g_prev"] = g_next.to(home)                                       # the client's own estimator
+            out = comp.decompressShiftPayload(ship(payload), d, scale=mult, base=g_prev)   # the server's mirror
+        cs["stats"]["send_scalars_to_master"] += comp.last_need_to_send_advance
+        return out.to(home)
 
     def transfer(self, comp, msg, d):
         """One message client -> server over the socket pair: the client end sends on a thread

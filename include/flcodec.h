@@ -497,6 +497,67 @@ int flc_unpack_reduce(const flc_codec_params* prm, const void* d_payloads, int64
                       float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Shifted steps on the wire (additive to ABI 1.04: detect by symbol): the shift codecs' client
+ * step e = C(a - b) that EMITS its message, and the server fold of n such messages with the
+ * shifted round's semantics.
+ *
+ * flc_pack_shift — one client row.  v = a - b and e = C(v) exactly as flc_encode_shift forms them
+ * (same pattern row, same draws, the exactly rounded norm of a - b for dithering).  d_payload
+ * receives exactly the bytes flc_pack writes for the fp32 row x = a - b under the same prm / pat
+ * (header with the norm and bad = 0, the codes or the ascending (idx, val) list, zeroed padding):
+ * flc_unpack(payload) == e bit for bit.  d_msg = d_base + e * msg_scale (e * msg_scale without a
+ * base) and d_shift_out = d_shift_in + shift_alpha * e, each op rounded separately, flc_encode_shift's
+ * bits; both are optional (MARINA's client needs the payload only).  d_msg / d_shift_out may alias
+ * a, b, base and shift_in as in flc_encode_shift; the payload (16-byte aligned, flc_payload_bytes)
+ * must not overlap any operand.  Dense formats (F32 / Q8 / Q16 / NAT16): one pass after the norm
+ * pass (k_ew_shift_code: a, b [, base, shift_in] read once; codes, msg, shift_out written once —
+ * QSGD with in-place DIANA moves 8 d + 8 d + 4 d + 1 d = 21 d bytes).  SPARSE (RandK / TopK): a - b
+ * and the dense e in the workspace, the compaction of flc_pack, then the epilogue — a constant
+ * number of launches, not a fast path.  d == 0 writes the empty header, as flc_pack.
+ *
+ * flc_unpack_shift_reduce — the server.  msg_i = base_i + dec(payload_i) * msg_scale (dec * msg_scale
+ * without a base), stored to d_msg row i when given; d_out = (sum_i w_i * msg_i) / w_total folded in
+ * row order (first term assigned, d_w == NULL: no multiply, one division at the end).  Row i of
+ * d_msg may be row i of d_base (same pointer and leading dimension: EF21's server mirror updated in
+ * place); ldbase == 0 is ONE shared [d] base (MARINA's g_prev).  Without base and d_msg and with
+ * msg_scale == 1 it is flc_unpack_reduce's fold.  Dense formats: one tile-owner pass
+ * (k_unpack_shift_accum; an in-place EF21 mirror with Q8 moves (1 + 4 + 4) n d + 4 d bytes); SPARSE:
+ * row by row through a dense workspace row, so the bits are the dense shifted round's.
+ *
+ * The identity: for any flc_shift_rows round in which nothing is written through a shift operand,
+ * flc_pack_shift of each row into payload i followed by flc_unpack_shift_reduce over the n payloads
+ * with the same base, msg_scale, d_msg and weights leaves the d_out and the d_msg rows of
+ * flc_encode_shift_reduce, bit for bit (compat and device draws, -0 columns included).
+ *
+ * Checked before any launch; a refused call writes nothing.  FLC_ERR_ARG: null a / b / payload /
+ * out with work to do, d < 0 or n < 0, a payload that is not 16-byte aligned, ld_bytes <
+ * flc_payload_bytes or ld_bytes % 16 != 0, d_shift_out without d_shift_in, d_base without d_msg
+ * (client entry), d_msg rows that overlap (|ldmsg| < d with n > 1), d_msg overlapping a shared base.
+ * FLC_ERR_UNSUPPORTED (reason in flc_last_error_string): an unknown codec, FLC_RANK_K (its factors
+ * are not carried by shifted steps), n > FLC_MAX_ROWS.  FLC_ERR_WORKSPACE: ws_bytes below the size
+ * query (0 for an unknown codec, a negative size or Rank-K).  Server: d == 0 returns FLC_OK without
+ * touching the device; n == 0 with d > 0 zero-fills d_out.
+ * -------------------------------------------------------------------------------------- */
+size_t flc_pack_shift_workspace_size(const flc_codec_params* prm, int64_t d);
+int flc_pack_shift(const flc_codec_params* prm, const flc_pattern* pat,
+                   const float* d_a, const float* d_b, int64_t d,
+                   float msg_scale, const float* d_base, float* d_msg,
+                   float shift_alpha, const float* d_shift_in, float* d_shift_out,
+                   void* d_payload, void* d_ws, size_t ws_bytes, void* stream);
+
+typedef struct {
+    const void* d_payloads; int64_t ld_bytes;   /* strided payload rows, or NULL with ...          */
+    const void* const* d_payload_ptrs;          /* ... a device array of n payload pointers         */
+    float msg_scale;
+    const float* d_base; int64_t ldbase;        /* NULL; [n] rows; or ldbase == 0: ONE shared [d]   */
+    float* d_msg;        int64_t ldmsg;         /* NULL, or [n] rows (may be the d_base rows)       */
+} flc_payload_rows;
+size_t flc_unpack_shift_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_unpack_shift_reduce(const flc_codec_params* prm, const flc_payload_rows* rows,
+                            int64_t n, int64_t d, const float* d_w, float w_total,
+                            float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * Multi-GPU combine on a caller-owned RCCL communicator (rccl_comm: an ncclComm_t, passed as
  * void* so no RCCL type crosses the boundary).  Each rank's d_partial holds the client-order
  * partial sum of its client block (flc_encode_reduce / flc_unpack_reduce with w_total = 1.0);
@@ -587,7 +648,9 @@ int flc_selftest_division(const float* d_divisors, int n, unsigned long long* d_
  * k_shift_sub_rows and k_topk_shift_lists (flc_topk_shift_reduce's difference pass and sparse epilogue:
  * one record each per call), k_ds_sample / k_ds_filter / k_ds_final / k_ds_resolve / k_ds_accum (the sparse QSGD
  * pipeline, one record per launch), k_ds_shift_lists and k_ds_shift_dense_rows (flc_dither_shift_reduce's
- * sparse and dense-row epilogues: one record each per call in shapes A and B);
+ * sparse and dense-row epilogues: one record each per call in shapes A and B), k_ew_shift_code
+ * (flc_pack_shift's one pass over a dense format: one record per call) and k_unpack_shift_accum
+ * (flc_unpack_shift_reduce's tile-owner pass over a dense format: one record per call);
  * the TopK filter's variant is recorded too
  * (k_topk_filter_g4: 4-chunk work items, the many-row path of large launches; k_topk_filter_g2:
  * 2-chunk items), so a test can assert which one ran.

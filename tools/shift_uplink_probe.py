@@ -49,6 +49,18 @@ interleaved in one process on one allocation, device draws; after every repeat t
 two in-place matrices are compared as int32.  Byte model: one_read 8 N D + 4 D (+ 4 N D for EF21's dense
 fold) against 20 N D + 4 D; the summary carries the kernels' own times and the number of rows the
 one-read call folded dense.  Writes <out-dir>/<spec>_<shape>.jsonl (default profiles/r12/dither_shift).
+
+--wire (dense-format specs, default qsgd:127,natural; device draws): the shifted steps on the wire,
+  client  fused        compressShiftPayload(g, h, alpha, shift = shift_out = h)   flc_pack_shift, DIANA in place
+          composition  torch (g - h) + compressPayload + compressShift(message=False): the only bit-equal
+                       way to the same payload and shift without flc_pack_shift
+  server  fused        ShiftPayloadReducer(P, base = msg_out = M, scale = mult)    flc_unpack_shift_reduce,
+                       the EF21 mirror in place over N payloads
+          composition  N x decompressPayload + the two torch expressions (dec * mult, M_i + t) + reduce_rows
+interleaved in one process on one allocation; after every repeat the payloads, the shifts, the mirrors
+and the folds are compared (bytes / int32).  Byte models: client 21 d (QSGD; natural 14 d: no norm pass,
+2-byte codes) against 41 d (30 d); server (c + 8) N d + 4 d against (c + 28) N d with c code bytes per
+element.  Writes <out-dir>/<spec>_client.jsonl and <spec>_server.jsonl (default profiles/r13/shift_wire).
 """
 import argparse
 import json
@@ -388,6 +400,136 @@ def main_one_read(a):
             print("wrote", path, flush=True)
 
 
+def main_wire(a):
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d = a.n, a.d
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev).manual_seed(1000)
+
+    def filled():
+        t = torch.empty((n, d), dtype=torch.float32, device=dev)
+        for i in range(0, n, 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    G, M0 = filled(), filled()
+    Mf, Mc = torch.empty_like(M0), torch.empty_like(M0)
+    diff, tmp = torch.empty(d, dtype=torch.float32, device=dev), torch.empty(d, dtype=torch.float32, device=dev)
+    outs = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in ("fused", "composition")}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    kernels = ("k_ew_shift_code", "k_unpack_shift_accum", "k_norm_partials", "k_ew_shift", "k_reduce_vec")
+
+    def timed(runs, agree, what, path, model, extra):
+        for _ in range(2):                             # warm: code objects, workspaces, the allocator's blocks
+            for f in runs.values():
+                f()
+        torch.cuda.synchronize()
+        if not agree():
+            raise SystemExit(f"{what}: fused and composition differ after the warm-up rounds")
+        ms = {v: [] for v in runs}
+        with open(path, "w") as fh:
+            def emit(rec):
+                line = json.dumps(rec)
+                fh.write(line + "\n")
+                fh.flush()
+                print(line, flush=True)
+            for r in range(a.repeats):
+                for v, f in runs.items():
+                    e0.record()
+                    for _ in range(a.steps):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    t = e0.elapsed_time(e1) / a.steps
+                    ms[v].append(t)
+                    emit(dict(extra, repeat=r, variant=v, ms_per_call=round(t, 4), model_bytes=model[v],
+                              GBps=round(model[v] / t / 1e6, 1)))
+                if not agree():
+                    raise SystemExit(f"{what}: fused and composition differ after repeat {r}")
+            kms = {}
+            for v, f in runs.items():                  # the kernels' own times, one call each
+                _lib.profile_enable(True)
+                for kn in kernels:
+                    _lib.profile_collect(kn)
+                f()
+                torch.cuda.synchronize()
+                _lib.profile_enable(False)
+                kms[v] = {kn: [round(t, 4), c] for kn in kernels for t, c in [_lib.profile_collect(kn)] if c}
+            if not agree():
+                raise SystemExit(f"{what}: fused and composition differ after the timer pass")
+            med = {v: statistics.median(ms[v]) for v in runs}
+            emit(dict(extra, summary=True, repeats=a.repeats, steps=a.steps,
+                      median_ms={v: round(med[v], 4) for v in runs}, min_ms={v: round(min(ms[v]), 4) for v in runs},
+                      max_ms={v: round(max(ms[v]), 4) for v in runs}, model_bytes=model,
+                      GBps_of_model_at_median={v: round(model[v] / med[v] / 1e6, 1) for v in runs},
+                      composition_over_fused=round(med["composition"] / med["fused"], 3),
+                      byte_model_composition_over_fused=round(model["composition"] / model["fused"], 3),
+                      fused_faster_beyond_spread=max(ms["fused"]) < min(ms["composition"]),
+                      bits_equal_every_repeat=True, kernel_ms_and_records_one_call=kms))
+        print("wrote", path, flush=True)
+
+    for spec in a.specs.split(","):
+        tag = spec.replace(":", "_").replace(".", "_")
+        comp_f, comp_c, comp_p = (ag.initCompressor(spec, d) for _ in range(3))
+        for c in (comp_f, comp_c, comp_p):
+            c.device_rng = (SEED, 0)
+        pb = comp_f.payloadBytes(d)
+        code = (pb - 16) / d                           # code bytes per element
+        norm = 8 if not spec.startswith("natural") else 0      # the norm pass reads a and b once more
+        alpha = 1.0 / (1.0 + comp_f.getW())
+        mult = 1.0 if comp_f.isContractionCompressor() else 1.0 / (1.0 + comp_f.getW())
+        # ---- client: one row, DIANA in place --------------------------------------------------
+        g, hf, hc = G[0], Mf[0], Mc[0]
+        hf.copy_(M0[0])
+        hc.copy_(M0[0])
+        pf = torch.empty(pb, dtype=torch.uint8, device=dev)
+        pc = torch.empty(pb, dtype=torch.uint8, device=dev)
+
+        def client_fused():
+            comp_f.compressShiftPayload(g, hf, alpha=alpha, shift=hf, shift_out=hf, payload_out=pf)
+
+        def client_composition():
+            torch.sub(g, hc, out=diff)
+            comp_c.compressPayload(diff, out=pc)
+            comp_c.compressShift(g, hc, alpha=alpha, shift=hc, shift_out=hc, message=False)
+        timed({"fused": client_fused, "composition": client_composition},
+              lambda: torch.equal(pf, pc) and torch.equal(hf.view(torch.int32), hc.view(torch.int32)),
+              f"{spec} client", os.path.join(a.out_dir, tag + "_client.jsonl"),
+              {"fused": int((norm + 8 + 4 + code) * d),
+               "composition": int((12 + norm // 2 + 4 + code + norm + 8 + 4) * d)},   # (the payload leg's norm pass reads the stored difference)
+              {"spec": spec, "side": "client", "d": d})
+        # ---- server: the EF21 mirror in place over n payloads ---------------------------------
+        P = torch.empty((n, pb), dtype=torch.uint8, device=dev)
+        for i in range(n):
+            comp_p.device_rng = (SEED, i)
+            comp_p.compressShiftPayload(G[i], M0[i], payload_out=P[i])
+        Mf.copy_(M0)
+        Mc.copy_(M0)
+        red = ag.ShiftPayloadReducer(comp_f, device=dev)
+
+        def server_fused():
+            red(P, d, scale=mult, base=Mf, msg_out=Mf, out=outs["fused"])
+
+        def server_composition():
+            for i in range(n):
+                dec = comp_c.decompressPayload(P[i], d)
+                torch.mul(dec, mult, out=tmp)
+                torch.add(Mc[i], tmp, out=Mc[i])
+            ag.reduce_rows(outs["composition"], Mc, relative=False, out=outs["composition"])
+        timed({"fused": server_fused, "composition": server_composition},
+              lambda: (torch.equal(outs["fused"].view(torch.int32), outs["composition"].view(torch.int32))
+                       and torch.equal(Mf.view(torch.int32), Mc.view(torch.int32))),
+              f"{spec} server", os.path.join(a.out_dir, tag + "_server.jsonl"),
+              {"fused": int((code + 8) * n * d + 4 * d), "composition": int((code + 28) * n * d + 4 * d)},
+              {"spec": spec, "side": "server", "n": n, "d": d})
+        del P
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--specs", default="natural,qsgd:127")
@@ -400,6 +542,7 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="RandK specs: flc_randk_shift_reduce against the general entry")
     ap.add_argument("--topk", action="store_true", help="TopK specs: flc_topk_shift_reduce against the general entry")
     ap.add_argument("--one-read", action="store_true", help="QSGD specs: flc_dither_shift_reduce against the general entry")
+    ap.add_argument("--wire", action="store_true", help="flc_pack_shift / flc_unpack_shift_reduce against their compositions")
     ap.add_argument("--shapes", default="diana,ef21", help="--topk / --one-read: the in-place rounds to time")
     a = ap.parse_args()
     if a.topk and a.out_dir == ap.get_default("out_dir"):
@@ -408,6 +551,10 @@ def main():
         a.out_dir = os.path.join(ROOT, "profiles", "r12", "dither_shift")
     if a.one_read and a.specs == ap.get_default("specs"):
         a.specs = "qsgd:127"
+    if a.wire and a.out_dir == ap.get_default("out_dir"):
+        a.out_dir = os.path.join(ROOT, "profiles", "r13", "shift_wire")
+    if a.wire and a.specs == ap.get_default("specs"):
+        a.specs = "qsgd:127,natural"
     if a.repeats < 1 or a.steps < 1 or a.n < 1 or a.d < 1:
         ap.error("--repeats, --steps, --n and --d are positive")
     if a.sparse:
@@ -416,6 +563,8 @@ def main():
         return main_topk(a)
     if a.one_read:
         return main_one_read(a)
+    if a.wire:
+        return main_wire(a)
     import torch
 
     from flpytorch_amd import _lib
