@@ -593,37 +593,22 @@ class Compressor:
                                  "payloadBytes()")
             else:
                 payload = payload_out
-            ws_bytes = lib.flc_pack_shift_workspace_size(ctypes.byref(prm), d)
-        else:
-            ws_bytes = lib.flc_encode_shift_workspace_size(ctypes.byref(prm), d)
-        ws = _lib.WORKSPACE.get(dev, ws_bytes)
+        # the two entries differ in one argument: the payload to write, or the norm to report
+        entry = "flc_pack_shift" if pack else "flc_encode_shift"
+        ws = _lib.WORKSPACE.get(dev, getattr(lib, entry + "_workspace_size")(ctypes.byref(prm), d))
 
         def ptr(v):
             return vp(v.data_ptr() if v is not None else None)
-        if pack:
-            with torch.cuda.device(dev):
-                rc = lib.flc_pack_shift(ctypes.byref(prm), ctypes.byref(pat), ptr(af), ptr(bf), d,
-                                        ctypes.c_float(float(np.float32(scale))), ptr(basef), ptr(msg),
-                                        ctypes.c_float(float(np.float32(alpha if alpha is not None else 0.0))),
-                                        ptr(hf if hout is not None else None), ptr(hout), ptr(payload),
-                                        vp(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
-            _lib.check(rc, "flc_pack_shift")
-            self._account(d)
-            return (msg.view(a.shape) if msg is not None else None,
-                    hout.view(shift.shape) if hout is not None else None, payload)
         with torch.cuda.device(dev):
-            rc = lib.flc_encode_shift(ctypes.byref(prm), ctypes.byref(pat), ptr(af), ptr(bf), d,
-                                      ctypes.c_float(float(np.float32(scale))), ptr(basef), ptr(msg),
-                                      ctypes.c_float(float(np.float32(alpha if alpha is not None else 0.0))),
-                                      ptr(hf if hout is not None else None), ptr(hout), ptr(pnorm_out),
-                                      vp(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_encode_shift")
+            rc = getattr(lib, entry)(ctypes.byref(prm), ctypes.byref(pat), ptr(af), ptr(bf), d,
+                                     ctypes.c_float(float(np.float32(scale))), ptr(basef), ptr(msg),
+                                     ctypes.c_float(float(np.float32(alpha if alpha is not None else 0.0))),
+                                     ptr(hf if hout is not None else None), ptr(hout), ptr(payload if pack else pnorm_out),
+                                     vp(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
+        _lib.check(rc, entry)
         self._account(d)
-        if msg is not None:
-            msg = msg.view(a.shape)
-        if hout is not None:
-            hout = hout.view(shift.shape)
-        return msg, hout, None
+        return (msg.view(a.shape) if msg is not None else None,
+                hout.view(shift.shape) if hout is not None else None, payload)
 
     def decompressShiftPayload(self, payload, d=None, *, scale=1.0, base=None, out=None):
         """The one-row server step of a shifted message: ``base + decompressPayload(payload) * scale``

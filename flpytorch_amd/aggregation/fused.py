@@ -32,6 +32,85 @@ def _device(device):
     return dev
 
 
+def _fold_weights(weights, n, dev, keep, divisor):
+    """``(w_ptr, total)`` of a weighted fold: the weights as an fp32 device tensor (None: every w_i = 1)
+    and the fp32 divisor — the weights summed in order as Python floats (n without weights),
+    ``divisor`` in its place when given."""
+    w_ptr, total = None, float(n)
+    if weights is not None:
+        weights = [float(w) for w in weights]
+        if len(weights) != n:
+            raise ValueError(f"weights must hold {n} values")
+        if n:
+            total = weights[0]
+            for w in weights[1:]:
+                total += w
+            wt = torch.tensor(weights, dtype=torch.float32, device=dev)
+            keep.append(wt)
+            w_ptr = wt.data_ptr()
+    if divisor is not None:
+        total = float(divisor)
+    return w_ptr, total
+
+
+def _pointer_table(tensors, dev, keep):
+    """Device array of the tensors' addresses.  Pinned staging + async copy: no host wait on the
+    work already queued on the stream."""
+    host_pt = torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64).pin_memory()
+    pt = host_pt.to(dev, non_blocking=True)
+    keep.extend(tensors)
+    keep.append(pt)
+    return pt.data_ptr()
+
+
+def _is_fp32_device(v):
+    return v.dtype == torch.float32 and v.is_cuda
+
+
+def _row_matrix(who, name, v, n, d, like=""):
+    """``(ptr, ld)`` of an [N, D] row-contiguous operand; ``who``: the class the messages name."""
+    if tuple(v.shape) != (n, d):
+        raise ValueError(f"{who}: {name} must be [{n}, {d}]{like} (got {tuple(v.shape)})")
+    if d > 1 and v.stride(1) != 1:
+        raise ValueError(f"{who}: {name} must be row-contiguous")
+    return v.data_ptr(), v.stride(0)
+
+
+def _base_rows(who, base, n, d, rows):
+    """``(ptr, ld)`` of a base: ONE [D] vector for every row (ld 0) or [N, D] rows through ``rows``."""
+    if base.dim() == 1:
+        if base.numel() != d or (d > 1 and base.stride(0) != 1):
+            raise ValueError(f"{who}: a shared base must be a contiguous [{d}] vector")
+        return base.data_ptr(), 0
+    ptr, ld = rows("base", base)
+    if n > 1 and ld == 0:
+        raise ValueError(f"{who}: pass a shared base as a [D] vector")
+    return ptr, ld
+
+
+def _pattern_draws(pat, t, randk_idx, uniforms, lazy_u):
+    """The compat draws of a call into ``pat``; returns whether the device RNG (a seed) is needed."""
+    if t == CompressorType.RANDK_COMPRESSOR and randk_idx is not None:
+        pat.d_randk_idx = randk_idx.data_ptr()
+        pat.idx_ld = randk_idx.stride(0)
+    if uniforms is not None:
+        pat.d_uniforms = uniforms.data_ptr()
+        pat.uniforms_ld = uniforms.stride(0)
+    if t == CompressorType.LAZY_COMPRESSOR:
+        if lazy_u is None:
+            raise ValueError("lazy codec needs lazy_u [N] draws")
+        pat.d_lazy_u = lazy_u.data_ptr()
+    return (t == CompressorType.RANDK_COMPRESSOR and randk_idx is None) or \
+           (t in (CompressorType.NATURAL_COMPRESSOR_FP32, CompressorType.STANDARD_DITHERING_FP32) and uniforms is None)
+
+
+def _pattern_counts(pat, randk_counts, n, d):
+    """RandK device draws: the chunk counts of ``UplinkReducer.randk_counts(n, d, client0)``."""
+    if tuple(randk_counts.shape) != ((d + 4095) // 4096, n) or not randk_counts.is_cuda:
+        raise ValueError("randk_counts must be a [ceil(d / 4096), n] device tensor")
+    pat.d_randk_counts = randk_counts.data_ptr()
+
+
 def select_row_flags(comp: Compressor, n, d, device=None):
     """Path report of the last TopK call on the current stream's workspace (flc_select_row_flags): a
     [n] int64 tensor of row state bits — 1 overflow, 2 short list, 4 ties cut on the fast path,
@@ -139,47 +218,17 @@ class UplinkReducer:
             d = rows[0].numel() if n else 0
             # the pointer-array entry reads rows with 16-byte vector loads: keep them aligned
             rows = [r if (r.is_contiguous() and r.data_ptr() % 16 == 0) else r.contiguous().clone() for r in rows]
-            keep.extend(rows)
-            # pinned staging + async copy: no host wait on the work already queued on the stream
-            host_pt = torch.tensor([r.data_ptr() for r in rows], dtype=torch.int64).pin_memory()
-            pt = host_pt.to(dev, non_blocking=True)
-            keep.append(pt)
-            base, ld, ptrs = None, 0, pt.data_ptr()
+            base, ld, ptrs = None, 0, _pointer_table(rows, dev, keep)
         if out is None:
             out = torch.empty(d, dtype=torch.float32, device=dev)
         if n == 0:
             return out.zero_()                                   # no clients (algorithms.py:2117-2118)
         t = self.comp.compressorType
-        if t == CompressorType.RANDK_COMPRESSOR and randk_idx is not None:
-            pat.d_randk_idx = randk_idx.data_ptr()
-            pat.idx_ld = randk_idx.stride(0)
         if randk_counts is not None and t == CompressorType.RANDK_COMPRESSOR and randk_idx is None:
-            if tuple(randk_counts.shape) != ((d + 4095) // 4096, n) or not randk_counts.is_cuda:
-                raise ValueError("randk_counts must be a [ceil(d / 4096), n] device tensor")
-            pat.d_randk_counts = randk_counts.data_ptr()
-        if uniforms is not None:
-            pat.d_uniforms = uniforms.data_ptr()
-            pat.uniforms_ld = uniforms.stride(0)
-        if t == CompressorType.LAZY_COMPRESSOR:
-            if lazy_u is None:
-                raise ValueError("lazy codec needs lazy_u [N] draws")
-            pat.d_lazy_u = lazy_u.data_ptr()
-        needs_seed = (t in (CompressorType.RANDK_COMPRESSOR,) and randk_idx is None) or \
-                     (t in (CompressorType.NATURAL_COMPRESSOR_FP32, CompressorType.STANDARD_DITHERING_FP32)
-                      and uniforms is None)
-        if needs_seed and self.seed is None:
+            _pattern_counts(pat, randk_counts, n, d)
+        if _pattern_draws(pat, t, randk_idx, uniforms, lazy_u) and self.seed is None:
             raise ValueError("no compat pattern given and no device-RNG seed set")
-        w_ptr, total = None, float(n)
-        if weights is not None:
-            weights = [float(w) for w in weights]
-            total = weights[0]
-            for w in weights[1:]:
-                total += w
-            wt = torch.tensor(weights, dtype=torch.float32, device=dev)
-            keep.append(wt)
-            w_ptr = wt.data_ptr()
-        if divisor is not None:
-            total = float(divisor)
+        w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
         pin_ptr = None
         if pnorms_in is not None:
             if (not torch.is_tensor(pnorms_in) or pnorms_in.dtype != torch.float32 or pnorms_in.device != dev
@@ -213,6 +262,26 @@ class UplinkReducer:
         return out
 
 
+# ShiftUplinkReducer's rounds by keyword (None: the general entry):
+#   ABI entry, it takes the pattern, its size query takes the pattern, it takes pnorms_out
+_SHIFT_MODES = {
+    None: ("flc_encode_shift_reduce", True, False, True),
+    "one_read": ("flc_dither_shift_reduce", True, False, True),
+    "batched": ("flc_topk_shift_reduce", False, False, False),
+    "sparse": ("flc_randk_shift_reduce", True, True, False),
+}
+
+
+def _shift_mode(sparse, batched, one_read):
+    return "one_read" if one_read else "batched" if batched else "sparse" if sparse else None
+
+
+def _shift_workspace_size(lib, mode, prm, pat, n, d):
+    entry, _, size_pat, _ = _SHIFT_MODES[mode]
+    args = (ctypes.byref(prm), ctypes.byref(pat), n, d) if size_pat else (ctypes.byref(prm), n, d)
+    return getattr(lib, entry + "_workspace_size")(*args)
+
+
 class ShiftUplinkReducer:
     """A DIANA / EF21 / MARINA / FRECON / COFIG round of N resident clients in one call
     (flc_encode_shift_reduce):
@@ -229,9 +298,9 @@ class ShiftUplinkReducer:
     ``norm_mode = "torch_cpu"`` does not apply to shifted steps.
 
     ``sparse=True`` (RandK only) runs the round through ``flc_randk_shift_reduce``: work
-    proportional to N K, not N D.  It takes the in-place DIANA shape (``shift is shift_out is b``,
-    no base / msg_out), the in-place EF21 shape (``base is msg_out is b``), MARINA's shared [D]
-    base, and the plain fold of C(a - b); anything else raises ``NotImplementedError``.  Elements
+    proportional to N K, not N D.  It takes shapes A - D of the table in ``include/flcodec.h``, in this
+    call's terms ``shift is shift_out is b`` (A), ``base is msg_out is b`` (B), a shared [D] ``base``
+    (C) and none of them (D); anything else raises ``NotImplementedError``.  Elements
     of the in-place operand OUTSIDE a row's index set are not written (the general entry stores
     ``x + 0`` there: the same bits except that a stored -0 becomes +0); selected elements and
     ``out`` carry the general entry's bits whenever the operand holds no -0 at an unselected
@@ -261,15 +330,9 @@ class ShiftUplinkReducer:
         ``batched``: flc_topk_shift_reduce's (the selection state, then the [n, d] difference matrix);
         ``one_read``: flc_dither_shift_reduce's (the sparse QSGD pipeline's state, no [n, d] matrix)."""
         prm, _ = self.params()
-        if one_read:
-            return _lib.load().flc_dither_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
-        if batched:
-            return _lib.load().flc_topk_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
-        if sparse:
-            pat = _lib.FlcPattern()
-            pat.d_randk_idx = 1 if compat else None             # (the size query only tells the modes apart)
-            return _lib.load().flc_randk_shift_reduce_workspace_size(ctypes.byref(prm), ctypes.byref(pat), n, d)
-        return _lib.load().flc_encode_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
+        pat = _lib.FlcPattern()
+        pat.d_randk_idx = 1 if compat else None                 # (the size query only tells the modes apart)
+        return _shift_workspace_size(_lib.load(), _shift_mode(sparse, batched, one_read), prm, pat, n, d)
 
     def __call__(self, a, b, *, scale=1.0, base=None, msg_out=None, alpha=None, shift=None, shift_out=None, out=None,
                  weights=None, divisor=None, client0=0, randk_idx=None, uniforms=None, lazy_u=None, pnorms_out=None,
@@ -330,47 +393,30 @@ class ShiftUplinkReducer:
     def _run(self, a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx,
              uniforms, lazy_u, pnorms_out, sparse=False, randk_counts=None, batched=False, one_read=False):
         lib = _lib.load()
-        if not hasattr(lib, "flc_encode_shift_reduce"):
-            raise NotImplementedError("this library build has no flc_encode_shift_reduce")
-        if one_read and not hasattr(lib, "flc_dither_shift_reduce"):
-            raise NotImplementedError("this library build has no flc_dither_shift_reduce")
-        if one_read and alpha is not None and shift_out is None:
-            raise NotImplementedError("ShiftUplinkReducer: one_read=True updates the shift in place (shift_out = shift = b)")
-        if sparse and not hasattr(lib, "flc_randk_shift_reduce"):
-            raise NotImplementedError("this library build has no flc_randk_shift_reduce")
-        if sparse and alpha is not None and shift_out is None:
-            raise NotImplementedError("ShiftUplinkReducer: sparse=True updates the shift in place (shift_out = shift = b)")
-        if batched and not hasattr(lib, "flc_topk_shift_reduce"):
-            raise NotImplementedError("this library build has no flc_topk_shift_reduce")
-        if batched and alpha is not None and shift_out is None:
-            raise NotImplementedError("ShiftUplinkReducer: batched=True updates the shift in place (shift_out = shift = b)")
+        who = "ShiftUplinkReducer"
+        mode = _shift_mode(sparse, batched, one_read)
+        entry, takes_pat, _, takes_pnorms = _SHIFT_MODES[mode]
+        for name in ("flc_encode_shift_reduce", entry):
+            if not hasattr(lib, name):
+                raise NotImplementedError(f"this library build has no {name}")
+        if mode and alpha is not None and shift_out is None:
+            raise NotImplementedError(f"{who}: {mode}=True updates the shift in place (shift_out = shift = b)")
         dev = self.device
         for name, v in (("a", a), ("b", b), ("base", base), ("msg_out", msg_out), ("shift", shift),
                         ("shift_out", shift_out), ("out", out)):
-            if v is not None and (not torch.is_tensor(v) or v.dtype != torch.float32 or not v.is_cuda):
-                raise TypeError(f"ShiftUplinkReducer: {name} must be an fp32 device tensor")
+            if v is not None and (not torch.is_tensor(v) or not _is_fp32_device(v)):
+                raise TypeError(f"{who}: {name} must be an fp32 device tensor")
         if a.dim() != 2:
-            raise ValueError("ShiftUplinkReducer: a must be an [N, D] matrix")
+            raise ValueError(f"{who}: a must be an [N, D] matrix")
         n, d = a.shape
 
         def rows(name, v):
-            if tuple(v.shape) != (n, d):
-                raise ValueError(f"ShiftUplinkReducer: {name} must be [{n}, {d}] like a (got {tuple(v.shape)})")
-            if d > 1 and v.stride(1) != 1:
-                raise ValueError(f"ShiftUplinkReducer: {name} must be row-contiguous")
-            return v.data_ptr(), v.stride(0)
+            return _row_matrix(who, name, v, n, d, like=" like a")
         sr = _lib.FlcShiftRows()
         sr.d_a, sr.lda = rows("a", a)
         sr.d_b, sr.ldb = rows("b", b)
         if base is not None:
-            if base.dim() == 1:
-                if base.numel() != d or (d > 1 and base.stride(0) != 1):
-                    raise ValueError(f"ShiftUplinkReducer: a shared base must be a contiguous [{d}] vector")
-                sr.d_base, sr.ldbase = base.data_ptr(), 0
-            else:
-                sr.d_base, sr.ldbase = rows("base", base)
-                if n > 1 and sr.ldbase == 0:
-                    raise ValueError("ShiftUplinkReducer: pass a shared base as a [D] vector")
+            sr.d_base, sr.ldbase = _base_rows(who, base, n, d, rows)
         if alpha is not None and shift is None:
             raise ValueError("ShiftUplinkReducer: alpha given without a shift matrix")
         if alpha is None and shift_out is not None:
@@ -394,78 +440,29 @@ class ShiftUplinkReducer:
         pat = _lib.FlcPattern()
         pat.client0 = int(client0)
         t = self.comp.compressorType
-        if t == CompressorType.RANDK_COMPRESSOR and randk_idx is not None:
-            pat.d_randk_idx = randk_idx.data_ptr()
-            pat.idx_ld = randk_idx.stride(0)
-        if uniforms is not None:
-            pat.d_uniforms = uniforms.data_ptr()
-            pat.uniforms_ld = uniforms.stride(0)
         lazy_host = None
-        if t == CompressorType.LAZY_COMPRESSOR:
-            if lazy_u is None:
-                raise ValueError("lazy codec needs lazy_u [N] draws")
+        if t == CompressorType.LAZY_COMPRESSOR and lazy_u is not None:
             lazy_u = torch.as_tensor(lazy_u, dtype=torch.float64)
             if lazy_u.numel() != n:
                 raise ValueError(f"lazy_u must hold {n} draws")
             lazy_host = [float(x) for x in lazy_u.detach().cpu().reshape(-1).tolist()]
             lazy_u = lazy_u.to(dev).contiguous()
             keep.append(lazy_u)
-            pat.d_lazy_u = lazy_u.data_ptr()
-        needs_seed = (t == CompressorType.RANDK_COMPRESSOR and randk_idx is None) or \
-                     (t in (CompressorType.NATURAL_COMPRESSOR_FP32, CompressorType.STANDARD_DITHERING_FP32)
-                      and uniforms is None)
-        if needs_seed and self.seed is None and self.comp.device_rng is None:
+        if _pattern_draws(pat, t, randk_idx, uniforms, lazy_u) and self.seed is None and self.comp.device_rng is None:
             raise ValueError("no compat pattern given and no device-RNG seed set")
-        w_ptr, total = None, float(n)
-        if weights is not None:
-            weights = [float(w) for w in weights]
-            if len(weights) != n:
-                raise ValueError(f"weights must hold {n} values")
-            total = weights[0]
-            for w in weights[1:]:
-                total += w
-            wt = torch.tensor(weights, dtype=torch.float32, device=dev)
-            keep.append(wt)
-            w_ptr = wt.data_ptr()
-        if divisor is not None:
-            total = float(divisor)
-        if randk_counts is not None and randk_idx is None:      # device draws: UplinkReducer.randk_counts(n, d, client0)
-            if tuple(randk_counts.shape) != ((d + 4095) // 4096, n) or not randk_counts.is_cuda:
-                raise ValueError("randk_counts must be a [ceil(d / 4096), n] device tensor")
-            pat.d_randk_counts = randk_counts.data_ptr()
-        if d > 0 and sparse:
-            ws = _lib.WORKSPACE.get(dev, lib.flc_randk_shift_reduce_workspace_size(ctypes.byref(prm), ctypes.byref(pat), n, d))
+        w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
+        if randk_counts is not None and randk_idx is None:
+            _pattern_counts(pat, randk_counts, n, d)
+        if d > 0:
+            vp = ctypes.c_void_p
+            ws = _lib.WORKSPACE.get(dev, _shift_workspace_size(lib, mode, prm, pat, n, d))
+            args = [ctypes.byref(prm)] + ([ctypes.byref(pat)] if takes_pat else []) + \
+                   [ctypes.byref(sr), n, d, vp(w_ptr), ctypes.c_float(total)]
+            if takes_pnorms:
+                args.append(vp(pnorms_out.data_ptr() if pnorms_out is not None else None))
             with torch.cuda.device(dev):
-                rc = lib.flc_randk_shift_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.byref(sr), n, d,
-                                                ctypes.c_void_p(w_ptr), ctypes.c_float(total),
-                                                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                                ws.numel(), _lib.stream_ptr(dev))
-            _lib.check(rc, "flc_randk_shift_reduce")          # (a refusal: NotImplementedError with the reason)
-        elif d > 0 and batched:
-            ws = _lib.WORKSPACE.get(dev, lib.flc_topk_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
-            with torch.cuda.device(dev):
-                rc = lib.flc_topk_shift_reduce(ctypes.byref(prm), ctypes.byref(sr), n, d, ctypes.c_void_p(w_ptr),
-                                               ctypes.c_float(total), ctypes.c_void_p(out.data_ptr()),
-                                               ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
-            _lib.check(rc, "flc_topk_shift_reduce")           # (a refusal: NotImplementedError with the reason)
-        elif d > 0 and one_read:
-            ws = _lib.WORKSPACE.get(dev, lib.flc_dither_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
-            with torch.cuda.device(dev):
-                rc = lib.flc_dither_shift_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.byref(sr), n, d,
-                                                 ctypes.c_void_p(w_ptr), ctypes.c_float(total),
-                                                 ctypes.c_void_p(pnorms_out.data_ptr() if pnorms_out is not None else None),
-                                                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                                 ws.numel(), _lib.stream_ptr(dev))
-            _lib.check(rc, "flc_dither_shift_reduce")         # (a refusal: NotImplementedError with the reason)
-        elif d > 0:
-            ws = _lib.WORKSPACE.get(dev, lib.flc_encode_shift_reduce_workspace_size(ctypes.byref(prm), n, d))
-            with torch.cuda.device(dev):
-                rc = lib.flc_encode_shift_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.byref(sr), n, d,
-                                                 ctypes.c_void_p(w_ptr), ctypes.c_float(total),
-                                                 ctypes.c_void_p(pnorms_out.data_ptr() if pnorms_out is not None else None),
-                                                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
-                                                 ws.numel(), _lib.stream_ptr(dev))
-            _lib.check(rc, "flc_encode_shift_reduce")
+                rc = getattr(lib, entry)(*args, vp(out.data_ptr()), vp(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
+            _lib.check(rc, entry)                               # (a refusal: NotImplementedError with the reason)
         for i in range(n):                                        # N compressShift calls' statistics
             if lazy_host is not None:
                 self.comp.testp = lazy_host[i]
@@ -500,24 +497,10 @@ class PayloadReducer:
             for p in payloads:
                 if p.data_ptr() % 16:
                     raise ValueError("payloads must be 16-byte aligned")
-            host_pt = torch.tensor([p.data_ptr() for p in payloads], dtype=torch.int64).pin_memory()
-            pt = host_pt.to(dev, non_blocking=True)
-            keep.extend(payloads)
-            keep.append(pt)
-            base, ldb, ptrs = None, 0, pt.data_ptr()
+            base, ldb, ptrs = None, 0, _pointer_table(payloads, dev, keep)
         if out is None:
             out = torch.empty(d, dtype=torch.float32, device=dev)
-        w_ptr, total = None, float(n)
-        if weights is not None:
-            weights = [float(w) for w in weights]
-            total = weights[0]
-            for w in weights[1:]:
-                total += w
-            wt = torch.tensor(weights, dtype=torch.float32, device=dev)
-            keep.append(wt)
-            w_ptr = wt.data_ptr()
-        if divisor is not None:
-            total = float(divisor)
+        w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
         ws_bytes = lib.flc_unpack_reduce_workspace_size(ctypes.byref(prm), n, d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):
@@ -574,31 +557,17 @@ class ShiftPayloadReducer:
                 if p.data_ptr() % 16 or not p.is_contiguous() or p.numel() < nbytes:
                     raise ValueError(f"payloads must be contiguous, 16-byte aligned and hold {nbytes} bytes")
             if n:
-                host_pt = torch.tensor([p.data_ptr() for p in payloads], dtype=torch.int64).pin_memory()
-                pt = host_pt.to(dev, non_blocking=True)
-                keep.extend(payloads)
-                keep.append(pt)
-                pr.d_payload_ptrs = pt.data_ptr()
+                pr.d_payload_ptrs = _pointer_table(payloads, dev, keep)
+        who = "ShiftPayloadReducer"
 
         def rows(name, v):
-            if v.dtype != torch.float32 or not v.is_cuda:
-                raise TypeError(f"ShiftPayloadReducer: {name} must be an fp32 device tensor")
-            if tuple(v.shape) != (n, d):
-                raise ValueError(f"ShiftPayloadReducer: {name} must be [{n}, {d}] (got {tuple(v.shape)})")
-            if d > 1 and v.stride(1) != 1:
-                raise ValueError(f"ShiftPayloadReducer: {name} must be row-contiguous")
-            return v.data_ptr(), v.stride(0)
+            if not _is_fp32_device(v):
+                raise TypeError(f"{who}: {name} must be an fp32 device tensor")
+            return _row_matrix(who, name, v, n, d)
         if base is not None:
-            if base.dim() == 1:
-                if base.dtype != torch.float32 or not base.is_cuda:
-                    raise TypeError("ShiftPayloadReducer: base must be an fp32 device tensor")
-                if base.numel() != d or (d > 1 and base.stride(0) != 1):
-                    raise ValueError(f"ShiftPayloadReducer: a shared base must be a contiguous [{d}] vector")
-                pr.d_base, pr.ldbase = base.data_ptr(), 0
-            else:
-                pr.d_base, pr.ldbase = rows("base", base)
-                if n > 1 and pr.ldbase == 0:
-                    raise ValueError("ShiftPayloadReducer: pass a shared base as a [D] vector")
+            if base.dim() == 1 and not _is_fp32_device(base):
+                raise TypeError(f"{who}: base must be an fp32 device tensor")
+            pr.d_base, pr.ldbase = _base_rows(who, base, n, d, rows)
         if msg_out is not None:
             pr.d_msg, pr.ldmsg = rows("msg_out", msg_out)
         pr.msg_scale = float(np.float32(scale))
@@ -606,20 +575,7 @@ class ShiftPayloadReducer:
             out = torch.empty(d, dtype=torch.float32, device=dev)
         elif out.dtype != torch.float32 or not out.is_cuda or out.numel() != d or not out.is_contiguous():
             raise ValueError(f"ShiftPayloadReducer: out must be a contiguous fp32 device [{d}] vector")
-        w_ptr, total = None, float(n)
-        if weights is not None:
-            weights = [float(w) for w in weights]
-            if len(weights) != n:
-                raise ValueError(f"weights must hold {n} values")
-            if n:
-                total = weights[0]
-                for w in weights[1:]:
-                    total += w
-                wt = torch.tensor(weights, dtype=torch.float32, device=dev)
-                keep.append(wt)
-                w_ptr = wt.data_ptr()
-        if divisor is not None:
-            total = float(divisor)
+        w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
         ws_bytes = lib.flc_unpack_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):

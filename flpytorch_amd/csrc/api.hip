@@ -68,6 +68,82 @@ static int bad_params(const flc_codec_params* prm, const char* what) {
     return FLC_OK;
 }
 
+// ---- argument checks shared by the shifted entries ------------------------------------------------
+static int too_many(const char* me, int64_t n, const char* what, int rc) {   // kernels index rows by blockIdx.y
+    set_error("%s: n=%lld %s, at most %d per call (fold larger rounds as partials)", me, (long long)n, what, FLC_MAX_ROWS);
+    return rc;
+}
+
+static int orphan_shift_out(const char* me, const float* shift_in, const float* shift_out) {
+    if (shift_out && !shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
+    return FLC_OK;
+}
+
+// One row (flc_encode_shift, flc_pack_shift): the operands and what may be absent.  need_output: a
+// call that writes neither msg nor shift_out is refused (the wire entry always writes its payload).
+static int shift_row_check(const char* me, const float* a, const float* b, int64_t d, const float* base, const float* msg,
+                           const float* shift_in, const float* shift_out, bool need_output) {
+    if (d > 0 && (!a || !b)) { set_error("%s: need a and b", me); return FLC_ERR_ARG; }
+    if (need_output && d > 0 && !msg && !shift_out) { set_error("%s: nothing to write (msg and shift_out null)", me); return FLC_ERR_ARG; }
+    if (int rc = orphan_shift_out(me, shift_in, shift_out)) return rc;
+    if (base && !msg) { set_error("%s: base without msg", me); return FLC_ERR_ARG; }
+    return FLC_OK;
+}
+
+// The n-row entries over flc_shift_rows (flc_encode / randk / topk / dither _shift_reduce): the sizes,
+// the empty call (*empty: return FLC_OK, nothing else is looked at), the operands every shape needs,
+// and *sr, the copy the round hosts work on: a shift nobody stores is not read, and the leading
+// dimensions of absent operands are zero.  late_tie: TopK parameters whose tie rule is checked
+// here, after the operands (the entry that checks it first passes null).
+static int shift_rows_prepare(const char* me, const flc_codec_params* late_tie, const flc_shift_rows* rows, int64_t n,
+                              int64_t d, const float* d_out, flc_shift_rows* sr, bool* empty) {
+    *empty = false;
+    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) return too_many(me, n, "rows", FLC_ERR_ARG);
+    if (n == 0 || d == 0) { *empty = true; return FLC_OK; }
+    if (!rows || !rows->d_a || !rows->d_b || !d_out) { set_error("%s: need rows, a, b and out", me); return FLC_ERR_ARG; }
+    if (late_tie)
+        if (int rc = bad_params(late_tie, me)) return rc;
+    *sr = *rows;
+    if (int rc = orphan_shift_out(me, sr->d_shift_in, sr->d_shift_out)) return rc;
+    if (!sr->d_shift_out) { sr->d_shift_in = nullptr; sr->ldin = sr->ldout = 0; }
+    if (!sr->d_base) sr->ldbase = 0;
+    if (!sr->d_msg) sr->ldmsg = 0;
+    return FLC_OK;
+}
+
+// the element range [lo, hi) that n rows of d elements at p + i * ld cover
+static void row_span(const float* p, int64_t ld, int64_t n, int64_t d, uintptr_t* lo, uintptr_t* hi) {
+    const int64_t last = (n - 1) * ld;
+    const float* a = p + std::min<int64_t>(0, last);
+    const float* b = p + std::max<int64_t>(0, last) + d;
+    *lo = (uintptr_t)a;
+    *hi = (uintptr_t)b;
+}
+
+// Output matrices of an n-row round (absent: p null): the rows of one must not overlap each other,
+// and with ONE base vector for every row (ldbase == 0) no output may lie over it: a store there
+// would change the base under the later rows.
+struct OutRows { const char* name; const char* ldname; const float* p; int64_t ld; };
+static int outputs_overlap(const char* me, std::initializer_list<OutRows> outs, const float* base, int64_t ldbase,
+                           int64_t n, int64_t d) {
+    if (n <= 1) return FLC_OK;
+    for (const OutRows& o : outs)
+        if (o.p && (o.ld < 0 ? -o.ld : o.ld) < d) {
+            set_error("%s: the %s rows overlap (|%s| < d)", me, o.name, o.ldname);
+            return FLC_ERR_ARG;
+        }
+    if (!base || ldbase != 0) return FLC_OK;
+    const uintptr_t b0 = (uintptr_t)base, b1 = (uintptr_t)(base + d);
+    for (const OutRows& o : outs) {
+        if (!o.p) continue;
+        uintptr_t lo, hi;
+        row_span(o.p, o.ld, n, d, &lo, &hi);
+        if (lo < b1 && b0 < hi) { set_error("%s: %s overlaps the shared base", me, o.name); return FLC_ERR_ARG; }
+    }
+    return FLC_OK;
+}
+
 }  // namespace flc
 
 using namespace flc;
@@ -249,13 +325,11 @@ extern "C" int flc_encode_shift(const flc_codec_params* prm, const flc_pattern* 
                                 const float* d_b, int64_t d, float msg_scale, const float* d_base, float* d_msg,
                                 float shift_alpha, const float* d_shift_in, float* d_shift_out, float* d_pnorm_out,
                                 void* d_ws, size_t ws_bytes, void* stream) {
-    if (!prm || !known(prm->codec)) { set_error("flc_encode_shift: unknown codec"); return FLC_ERR_UNSUPPORTED; }
-    if (int rc = bad_params(prm, "flc_encode_shift")) return rc;
-    if (d < 0) { set_error("flc_encode_shift: d < 0"); return FLC_ERR_ARG; }
-    if (d > 0 && (!d_a || !d_b)) { set_error("flc_encode_shift: need a and b"); return FLC_ERR_ARG; }
-    if (d > 0 && !d_msg && !d_shift_out) { set_error("flc_encode_shift: nothing to write (msg and shift_out null)"); return FLC_ERR_ARG; }
-    if (d_shift_out && !d_shift_in) { set_error("flc_encode_shift: shift_out without shift_in"); return FLC_ERR_ARG; }
-    if (d_base && !d_msg) { set_error("flc_encode_shift: base without msg"); return FLC_ERR_ARG; }
+    const char* me = "flc_encode_shift";
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (int rc = bad_params(prm, me)) return rc;
+    if (d < 0) { set_error("%s: d < 0", me); return FLC_ERR_ARG; }
+    if (int rc = shift_row_check(me, d_a, d_b, d, d_base, d_msg, d_shift_in, d_shift_out, /*need_output=*/true)) return rc;
     ShiftArgs sh{d_b, msg_scale, d_base, d_msg, shift_alpha, d_shift_in, d_shift_out};
     return shift_run(prm, pat, d_a, d, sh, d_pnorm_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
@@ -265,51 +339,19 @@ extern "C" size_t flc_encode_shift_reduce_workspace_size(const flc_codec_params*
     return shift_reduce_workspace(prm, n, d);
 }
 
-namespace flc {
-// the element range [lo, hi) that n rows of d elements at p + i * ld cover
-static void row_span(const float* p, int64_t ld, int64_t n, int64_t d, uintptr_t* lo, uintptr_t* hi) {
-    const int64_t last = (n - 1) * ld;
-    const float* a = p + std::min<int64_t>(0, last);
-    const float* b = p + std::max<int64_t>(0, last) + d;
-    *lo = (uintptr_t)a;
-    *hi = (uintptr_t)b;
-}
-}  // namespace flc
-
 extern "C" int flc_encode_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
                                        int64_t n, int64_t d, const float* d_w, float w_total, float* d_pnorms_out,
                                        float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
     const char* me = "flc_encode_shift_reduce";
     if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
     if (int rc = bad_params(prm, me)) return rc;
-    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
-    if (n > FLC_MAX_ROWS) {
-        set_error("%s: n=%lld rows, at most %d per call (fold larger rounds as partials)", me, (long long)n, FLC_MAX_ROWS);
-        return FLC_ERR_ARG;
-    }
-    if (n == 0 || d == 0) return FLC_OK;
-    if (!rows || !rows->d_a || !rows->d_b || !d_out) { set_error("%s: need rows, a, b and out", me); return FLC_ERR_ARG; }
-    flc_shift_rows sr = *rows;
-    if (sr.d_shift_out && !sr.d_shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
-    if (!sr.d_shift_out) { sr.d_shift_in = nullptr; sr.ldin = sr.ldout = 0; }   // a shift nobody stores is not read
-    if (!sr.d_base) sr.ldbase = 0;
-    if (!sr.d_msg) sr.ldmsg = 0;
-    auto short_ld = [&](int64_t ld) { return n > 1 && (ld < 0 ? -ld : ld) < d; };
-    if (sr.d_msg && short_ld(sr.ldmsg)) { set_error("%s: the d_msg rows overlap (|ldmsg| < d)", me); return FLC_ERR_ARG; }
-    if (sr.d_shift_out && short_ld(sr.ldout)) { set_error("%s: the d_shift_out rows overlap (|ldout| < d)", me); return FLC_ERR_ARG; }
-    if (sr.d_base && sr.ldbase == 0 && n > 1) {
-        // one base vector for every row: an output that overlaps it would change it under the later rows
-        const uintptr_t b0 = (uintptr_t)sr.d_base, b1 = (uintptr_t)(sr.d_base + d);
-        uintptr_t lo, hi;
-        if (sr.d_msg) {
-            row_span(sr.d_msg, sr.ldmsg, n, d, &lo, &hi);
-            if (lo < b1 && b0 < hi) { set_error("%s: d_msg overlaps the shared base", me); return FLC_ERR_ARG; }
-        }
-        if (sr.d_shift_out) {
-            row_span(sr.d_shift_out, sr.ldout, n, d, &lo, &hi);
-            if (lo < b1 && b0 < hi) { set_error("%s: d_shift_out overlaps the shared base", me); return FLC_ERR_ARG; }
-        }
-    }
+    flc_shift_rows sr;
+    bool empty;
+    if (int rc = shift_rows_prepare(me, nullptr, rows, n, d, d_out, &sr, &empty)) return rc;
+    if (empty) return FLC_OK;
+    if (int rc = outputs_overlap(me, {{"d_msg", "ldmsg", sr.d_msg, sr.ldmsg}, {"d_shift_out", "ldout", sr.d_shift_out, sr.ldout}},
+                                 sr.d_base, sr.ldbase, n, d))
+        return rc;
     return shift_reduce_run(prm, pat, sr, n, d, d_w, w_total, d_pnorms_out, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -327,18 +369,10 @@ extern "C" int flc_randk_shift_reduce(const flc_codec_params* prm, const flc_pat
         set_error("%s: only FLC_RANDK has a sparse shifted round (use flc_encode_shift_reduce)", me);
         return FLC_ERR_UNSUPPORTED;
     }
-    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
-    if (n > FLC_MAX_ROWS) {
-        set_error("%s: n=%lld rows, at most %d per call (fold larger rounds as partials)", me, (long long)n, FLC_MAX_ROWS);
-        return FLC_ERR_ARG;
-    }
-    if (n == 0 || d == 0) return FLC_OK;
-    if (!rows || !rows->d_a || !rows->d_b || !d_out) { set_error("%s: need rows, a, b and out", me); return FLC_ERR_ARG; }
-    flc_shift_rows sr = *rows;
-    if (sr.d_shift_out && !sr.d_shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
-    if (!sr.d_shift_out) { sr.d_shift_in = nullptr; sr.ldin = sr.ldout = 0; }   // a shift nobody stores is not read
-    if (!sr.d_base) sr.ldbase = 0;
-    if (!sr.d_msg) sr.ldmsg = 0;
+    flc_shift_rows sr;
+    bool empty;
+    if (int rc = shift_rows_prepare(me, nullptr, rows, n, d, d_out, &sr, &empty)) return rc;
+    if (empty) return FLC_OK;
     return randk_shift_run(prm, pat, sr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -355,19 +389,10 @@ extern "C" int flc_topk_shift_reduce(const flc_codec_params* prm, const flc_shif
         set_error("%s: only FLC_TOPK has a batched shifted round (use flc_encode_shift_reduce)", me);
         return FLC_ERR_UNSUPPORTED;
     }
-    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
-    if (n > FLC_MAX_ROWS) {
-        set_error("%s: n=%lld rows, at most %d per call (fold larger rounds as partials)", me, (long long)n, FLC_MAX_ROWS);
-        return FLC_ERR_ARG;
-    }
-    if (n == 0 || d == 0) return FLC_OK;
-    if (!rows || !rows->d_a || !rows->d_b || !d_out) { set_error("%s: need rows, a, b and out", me); return FLC_ERR_ARG; }
-    if (int rc = bad_params(prm, me)) return rc;
-    flc_shift_rows sr = *rows;
-    if (sr.d_shift_out && !sr.d_shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
-    if (!sr.d_shift_out) { sr.d_shift_in = nullptr; sr.ldin = sr.ldout = 0; }   // a shift nobody stores is not read
-    if (!sr.d_base) sr.ldbase = 0;
-    if (!sr.d_msg) sr.ldmsg = 0;
+    flc_shift_rows sr;
+    bool empty;
+    if (int rc = shift_rows_prepare(me, prm, rows, n, d, d_out, &sr, &empty)) return rc;
+    if (empty) return FLC_OK;
     return topk_shift_run(prm, sr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -384,18 +409,10 @@ extern "C" int flc_dither_shift_reduce(const flc_codec_params* prm, const flc_pa
         set_error("%s: only FLC_STD_DITHERING with FLC_NORM_L2 (QSGD) has a one-read shifted round (use flc_encode_shift_reduce)", me);
         return FLC_ERR_UNSUPPORTED;
     }
-    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
-    if (n > FLC_MAX_ROWS) {
-        set_error("%s: n=%lld rows, at most %d per call (fold larger rounds as partials)", me, (long long)n, FLC_MAX_ROWS);
-        return FLC_ERR_ARG;
-    }
-    if (n == 0 || d == 0) return FLC_OK;
-    if (!rows || !rows->d_a || !rows->d_b || !d_out) { set_error("%s: need rows, a, b and out", me); return FLC_ERR_ARG; }
-    flc_shift_rows sr = *rows;
-    if (sr.d_shift_out && !sr.d_shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
-    if (!sr.d_shift_out) { sr.d_shift_in = nullptr; sr.ldin = sr.ldout = 0; }   // a shift nobody stores is not read
-    if (!sr.d_base) sr.ldbase = 0;
-    if (!sr.d_msg) sr.ldmsg = 0;
+    flc_shift_rows sr;
+    bool empty;
+    if (int rc = shift_rows_prepare(me, nullptr, rows, n, d, d_out, &sr, &empty)) return rc;
+    if (empty) return FLC_OK;
     return dither_shift_run(prm, pat, sr, n, d, d_w, w_total, d_pnorms_out, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
@@ -477,9 +494,7 @@ extern "C" int flc_pack_shift(const flc_codec_params* prm, const flc_pattern* pa
     if (d < 0) { set_error("%s: d < 0", me); return FLC_ERR_ARG; }
     if (!d_payload) { set_error("%s: need a payload", me); return FLC_ERR_ARG; }
     if ((uintptr_t)d_payload & 15u) { set_error("%s: payload must be 16-byte aligned", me); return FLC_ERR_ARG; }
-    if (d > 0 && (!d_a || !d_b)) { set_error("%s: need a and b", me); return FLC_ERR_ARG; }
-    if (d_shift_out && !d_shift_in) { set_error("%s: shift_out without shift_in", me); return FLC_ERR_ARG; }
-    if (d_base && !d_msg) { set_error("%s: base without msg", me); return FLC_ERR_ARG; }
+    if (int rc = shift_row_check(me, d_a, d_b, d, d_base, d_msg, d_shift_in, d_shift_out, /*need_output=*/false)) return rc;
     ShiftArgs sh{d_b, msg_scale, d_base, d_msg, shift_alpha, d_shift_out ? d_shift_in : nullptr, d_shift_out};
     return pack_shift_run(prm, pat, d_a, d, sh, (char*)d_payload, d_ws, ws_bytes, (hipStream_t)stream);
 }
@@ -496,10 +511,7 @@ extern "C" int flc_unpack_shift_reduce(const flc_codec_params* prm, const flc_pa
     if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
     if (prm->codec == FLC_RANK_K) { set_error("%s: Rank-K payloads are not carried by shifted steps", me); return FLC_ERR_UNSUPPORTED; }
     if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
-    if (n > FLC_MAX_ROWS) {
-        set_error("%s: n=%lld payloads, at most %d per call (fold larger rounds as partials)", me, (long long)n, FLC_MAX_ROWS);
-        return FLC_ERR_UNSUPPORTED;
-    }
+    if (n > FLC_MAX_ROWS) return too_many(me, n, "payloads", FLC_ERR_UNSUPPORTED);
     if (d == 0) return FLC_OK;
     if (!d_out) { set_error("%s: need out", me); return FLC_ERR_ARG; }
     flc_payload_rows pr;
@@ -519,17 +531,7 @@ extern "C" int flc_unpack_shift_reduce(const flc_codec_params* prm, const flc_pa
         }
         if (!pr.d_base) pr.ldbase = 0;
         if (!pr.d_msg) pr.ldmsg = 0;
-        if (pr.d_msg && n > 1 && (pr.ldmsg < 0 ? -pr.ldmsg : pr.ldmsg) < d) {
-            set_error("%s: the d_msg rows overlap (|ldmsg| < d)", me);
-            return FLC_ERR_ARG;
-        }
-        if (pr.d_base && pr.ldbase == 0 && n > 1 && pr.d_msg) {
-            // one base vector for every row: a message row over it would change it under the later rows
-            const uintptr_t b0 = (uintptr_t)pr.d_base, b1 = (uintptr_t)(pr.d_base + d);
-            uintptr_t lo, hi;
-            row_span(pr.d_msg, pr.ldmsg, n, d, &lo, &hi);
-            if (lo < b1 && b0 < hi) { set_error("%s: d_msg overlaps the shared base", me); return FLC_ERR_ARG; }
-        }
+        if (int rc = outputs_overlap(me, {{"d_msg", "ldmsg", pr.d_msg, pr.ldmsg}}, pr.d_base, pr.ldbase, n, d)) return rc;
     }
     return unpack_shift_reduce_run(prm, pr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
@@ -562,11 +564,7 @@ extern "C" int flc_encode_reduce_ex(const flc_codec_params* prm, const flc_patte
         if (prm->norm != FLC_NORM_L2) norm_mode = FLC_NORMMODE_EXACT;
     }
     if (n < 0 || d < 0 || (d > 0 && !d_out)) { set_error("flc_encode_reduce: bad n/d/out"); return FLC_ERR_ARG; }
-    if (n > FLC_MAX_ROWS) {   // per-row kernels index rows by blockIdx.y
-        set_error("flc_encode_reduce: n=%lld rows, at most %d per call (fold larger rounds as partials)", (long long)n,
-                  FLC_MAX_ROWS);
-        return FLC_ERR_UNSUPPORTED;
-    }
+    if (n > FLC_MAX_ROWS) return too_many("flc_encode_reduce", n, "rows", FLC_ERR_UNSUPPORTED);
     if (n > 0 && d > 0 && !d_rows && !d_row_ptrs) { set_error("flc_encode_reduce: no rows"); return FLC_ERR_ARG; }
     if (d_rows && ld < d) { set_error("flc_encode_reduce: ld < d"); return FLC_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;

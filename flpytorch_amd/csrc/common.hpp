@@ -185,6 +185,18 @@ int shift_encode_dense(const flc_codec_params* prm, const flc_pattern* pat, cons
 int shift_epi_launch(const float* e, int64_t d, const ShiftArgs& sh, hipStream_t st);
 int shift_fold_launch(const float* m, int64_t d, const float* w, int64_t i, bool last, float wt, float* acc,
                       hipStream_t st);
+// What the sparse rounds (flc_randk / topk / dither_shift_reduce) share on the host (shift.hip).
+// shift_shape: the accepted shape of a round (the table in flcodec.h), recognised by pointer and
+// leading dimension, or -1 with the reason set under the entry's name `me`; sr is api.hip's
+// normalised copy.  The values are template arguments of the rounds' kernels.
+enum { SHAPE_D = 0, SHAPE_A = 1, SHAPE_C = 2, SHAPE_B = 3 };
+int shift_shape(const flc_shift_rows& sr, const char* me);
+// the in-place shapes (A, B) store into the b rows: they must not overlap
+int inplace_rows_check(const char* me, int shape, const flc_shift_rows& sr, int64_t n, int64_t d);
+// a round over (index, value) lists: K in [1, D], D within 32-bit entry indices, then inplace_rows_check
+int sparse_round_precheck(const char* me, int shape, const flc_shift_rows& sr, int64_t n, int64_t d, int64_t K);
+// shape B's tail: the dense fold of the rows the round has just updated in place
+int fold_updated_rows(const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt, float* out, hipStream_t st);
 // the SPARSE payload of a dense row (wire.hip k_pack_count / scan / write): bc holds pack_blocks(d)
 // counters, the payload is zeroed by the caller
 int64_t pack_blocks(int64_t d);
@@ -254,11 +266,6 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
 // shape C's fold of base + t over lists in the RkLists layout (k_randk_shift_lfold)
 int randk_shift_lfold_launch(const float* base, int64_t n, int64_t d, RkLists lists, const float* w, float wt, float* out,
                              hipStream_t st);
-// The accepted shape of a sparse shifted round (flcodec.h: A DIANA in place, B EF21 in place, C one
-// shared base, D the plain fold), recognised by pointer and leading dimension, or -1 with the reason
-// set under the entry's name `me`.  sr: api.hip's normalised copy.
-enum { RKS_D = 0, RKS_A = 1, RKS_C = 2, RKS_B = 3 };
-int rks_shape(const flc_shift_rows& sr, const char* me);
 // The many-row TopK selection by itself (select.hip): after topk_lists_build row r's entries of chunk
 // c are ent_idx / ent_val[r * cap + tab[c * n + r].x + t], t < tab[c * n + r].y, and an entry is
 // admitted iff (mag_key(val), idx ^ txm) >= (T, cut) with T, cut taken from thr / flags / tiecut as
@@ -287,7 +294,7 @@ int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_
 // the one-read QSGD shifted round (flc_dither_shift_reduce): dither_shift.hip decides on the host,
 // before any launch, whether the call is taken (else the refusal with its reason) and runs it;
 // dither_sparse.hip's ds_shift_run is the sparse pipeline over a - b with the in-place epilogues
-// (shape: RKS_A / RKS_B / RKS_D), ds_flags_at the DsWs.flags of a workspace
+// (shape: SHAPE_A / SHAPE_B / SHAPE_D), ds_flags_at the DsWs.flags of a workspace
 size_t dither_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 int dither_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
                      const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st);

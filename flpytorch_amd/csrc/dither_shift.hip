@@ -16,10 +16,8 @@
 // call writes nothing), the workspace, and the flags hook.  The kernels live with the pipeline they
 // extend, in dither_sparse.hip.
 //
-//   shape A  DIANA / FRECON / COFIG in place   shift_in == shift_out == b, msg_scale == 1   h' stored, fold of e
-//   shape B  EF21 in place                     base == msg == b (rows)                      m stored, then reduce_impl
-//   shape D  C(a - b) fold                     nothing stored, msg_scale == 1               fold of e
-//   shape C  MARINA (one shared base)          refused: its fold needs the (index, value) list form
+// Shapes: the table in flcodec.h.  A and D fold e itself, so msg_scale must be 1 there; C (MARINA's one
+// shared base) is refused: its fold needs the (index, value) list form.
 #include <algorithm>
 #include <cmath>
 
@@ -50,21 +48,18 @@ int dither_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const 
                   (long long)n, (long long)d, (int)(prm->flags & FLC_PATH_MASK));
         return FLC_ERR_UNSUPPORTED;
     }
-    const int shape = rks_shape(sr, me);
+    const int shape = shift_shape(sr, me);
     if (shape < 0) return FLC_ERR_UNSUPPORTED;
-    if (shape == RKS_C) {
+    if (shape == SHAPE_C) {
         set_error("%s: a shared base (MARINA) is not taken yet: its fold needs the (index, value) list form "
                   "(use flc_encode_shift_reduce)", me);
         return FLC_ERR_UNSUPPORTED;
     }
-    if (shape != RKS_B && sr.msg_scale != 1.0f) {
+    if (shape != SHAPE_B && sr.msg_scale != 1.0f) {
         set_error("%s: msg_scale must be 1 when the messages themselves are folded (got %g)", me, (double)sr.msg_scale);
         return FLC_ERR_UNSUPPORTED;
     }
-    if (n > 1 && (shape == RKS_A || shape == RKS_B) && (sr.ldb < 0 ? -sr.ldb : sr.ldb) < d) {
-        set_error("%s: the in-place rows overlap (|ldb| < d)", me);
-        return FLC_ERR_ARG;
-    }
+    if (int rc = inplace_rows_check(me, shape, sr, n, d)) return rc;
     if (ws_bytes < dither_shift_workspace(prm, n, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
     return ds_shift_run(prm, pat, sr, shape, n, d, w, wt, pnorms_out, out, ws, ws_bytes, st);
 }

@@ -2079,7 +2079,7 @@ struct DsShift {
 };
 
 __device__ inline float ds_shift_upd(int mode, float bv, float e, const DsShift& g) {
-    return mode == RKS_A ? bv + g.alpha * e : bv + e * g.ms;
+    return mode == SHAPE_A ? bv + g.alpha * e : bv + e * g.ms;
 }
 
 // Sparse rows.  One wave per (half chunk h, 64-row batch): per row its list ent16[h][row][0 .. sure +
@@ -2195,32 +2195,27 @@ int ds_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_
     // b — it re-reads a and b for dense rows and -0 columns — and ds_run_t returns with the row-group
     // pipeline joined into st.  B folds the updated rows afterwards instead.
     if (int rc = ds_run_t<DiffSrc>(prm, pat, rows, n, d, w, wt, pnorm_out, out, wsp, ws_bytes, st, nullptr, FLC_NORMMODE_EXACT,
-                                   /*fold=*/shape != RKS_B))
+                                   /*fold=*/shape != SHAPE_B))
         return rc;
-    if (shape != RKS_A && shape != RKS_B) return FLC_OK;
+    if (shape != SHAPE_A && shape != SHAPE_B) return FLC_OK;
     const DsWs ws = carve_ds(wsp, n, d, nullptr);
     const DsShift g{sr.d_a, sr.lda, const_cast<float*>(sr.d_b), sr.ldb, sr.msg_scale, sr.shift_alpha};
     {
         ProfScope _ps("k_ds_shift_lists", st);
         const int64_t waves = nhalves(d) * ((n + 63) / 64);
         const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 65536)));
-        if (shape == RKS_A) hipLaunchKernelGGL(k_ds_shift_lists<RKS_A>, grid, dim3(256), 0, st, g, n, d, ws, prm->d_levels, prm->s);
-        else hipLaunchKernelGGL(k_ds_shift_lists<RKS_B>, grid, dim3(256), 0, st, g, n, d, ws, prm->d_levels, prm->s);
+        if (shape == SHAPE_A) hipLaunchKernelGGL(k_ds_shift_lists<SHAPE_A>, grid, dim3(256), 0, st, g, n, d, ws, prm->d_levels, prm->s);
+        else hipLaunchKernelGGL(k_ds_shift_lists<SHAPE_B>, grid, dim3(256), 0, st, g, n, d, ws, prm->d_levels, prm->s);
         FLC_CHECK_LAUNCH("k_ds_shift_lists");
     }
     {
         ProfScope _ps("k_ds_shift_dense_rows", st);
         const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((d + 2047) / 2048, 256)), (unsigned)n);
-        if (shape == RKS_A) hipLaunchKernelGGL(k_ds_shift_dense_rows<RKS_A>, grid, dim3(256), 0, st, g, n, d, ws, prm->s);
-        else hipLaunchKernelGGL(k_ds_shift_dense_rows<RKS_B>, grid, dim3(256), 0, st, g, n, d, ws, prm->s);
+        if (shape == SHAPE_A) hipLaunchKernelGGL(k_ds_shift_dense_rows<SHAPE_A>, grid, dim3(256), 0, st, g, n, d, ws, prm->s);
+        else hipLaunchKernelGGL(k_ds_shift_dense_rows<SHAPE_B>, grid, dim3(256), 0, st, g, n, d, ws, prm->s);
         FLC_CHECK_LAUNCH("k_ds_shift_dense_rows");
     }
-    if (shape == RKS_B) {                                     // the dense fold of the updated rows
-        const bool vec = (((uintptr_t)sr.d_b & 15u) == 0) && (sr.ldb % 4 == 0);
-        const RowSrc brows{sr.d_b, sr.ldb, nullptr};
-        return reduce_impl(brows, vec, n, d, nullptr, w, wt, FLC_REDUCE_PLAIN, out, st);
-    }
-    return FLC_OK;
+    return shape == SHAPE_B ? fold_updated_rows(sr, n, d, w, wt, out, st) : FLC_OK;
 }
 
 }  // namespace flc

@@ -8,10 +8,8 @@
 // 128-B line granularity of the gathers), not to N D.  Every operation is rounded separately, in
 // the order above: a selected element and d_out carry flc_encode_shift_reduce's bits.
 //
-//   shape A  DIANA / FRECON / COFIG in place   shift_in == shift_out == b       h' stored, fold of t
-//   shape B  EF21 in place                     base == msg == b (rows)          m stored, then reduce_impl
-//   shape C  MARINA                            ONE shared base, nothing stored  fold of base + t
-//   shape D  C(a - b) fold                     nothing stored                   fold of t
+// Shapes A - D: the table in flcodec.h (shift_shape, shift.hip).  A stores h' and folds t, B stores m
+// and folds the updated rows (fold_updated_rows), C folds base + t, D folds t.
 //
 // Device draws: k_randk_shift, k_randk_fold's walk (select.hip) with two gathers per member and an
 // epilogue — one wave per chunk (or 1/2, 1/4 of its columns), rows in order, AP rows' gathers in
@@ -74,7 +72,7 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
                                                      float wt, float* __restrict__ out) {
     constexpr int PARTS = CHUNK / TS;
     constexpr int AP = RKS_AP;
-    constexpr int NR = MODE == RKS_C ? TS / 64 : 1;        // shape C: columns per lane, summed in registers
+    constexpr int NR = MODE == SHAPE_C ? TS / 64 : 1;        // shape C: columns per lane, summed in registers
     constexpr uint32_t NOCOL = 0xFFFFu;                    // past the chunk: the buffer load returns 0
     static_assert(64 % AP == 0, "the ring walks a 64-row batch in whole turns");
     __shared__ __attribute__((aligned(16))) float tile[4][TS];
@@ -90,7 +88,7 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
         const int64_t cbase = c * CHUNK;
         const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - cbase);
         float acc[NR], bs[NR];
-        if (MODE == RKS_C) {
+        if (MODE == SHAPE_C) {
 #pragma unroll
             for (int k = 0; k < NR; ++k) {
                 const uint32_t col = pbase + (uint32_t)(k * 64 + lane);
@@ -120,11 +118,11 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
             const float v = av - bv;
             const float e = g.scale * v;
             const float tt = e * g.ms;
-            if (MODE == RKS_A) {
+            if (MODE == SHAPE_A) {
                 const auto rsb = chunk_rsrc(g.b + r * g.ldb, cbase, d);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bv + g.alpha * e), rsb, (int)((pbase + loc) * 4u), 0, 0);
             }
-            if (MODE == RKS_C) tl[loc] = tt;
+            if (MODE == SHAPE_C) tl[loc] = tt;
             else tl[loc] = tl[loc] + wi * tt;
         };
         RksMeta cur = rks_meta(cnt, ckey, w, c, n, lane, clen), nxt;
@@ -157,7 +155,7 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
                                 if (l2 < (uint32_t)TS) member(l2, ap[col], bp[col], r, wi);
                             }
                         }
-                        if (MODE == RKS_C) {                  // every column: w * (base + t), t = +0 outside the set
+                        if (MODE == SHAPE_C) {                  // every column: w * (base + t), t = +0 outside the set
                             rks_tile_fence();
 #pragma unroll
                             for (int k = 0; k < NR; ++k) {
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
         }
         const int64_t len = min((int64_t)TS, (int64_t)clen - (int64_t)pbase);
         rks_tile_fence();
-        if (MODE == RKS_C) {
+        if (MODE == SHAPE_C) {
 #pragma unroll
             for (int k = 0; k < NR; ++k)
                 if (k * 64 + lane < len) out[cbase + pbase + k * 64 + lane] = acc[k] / wt;
@@ -229,7 +227,7 @@ __global__ __launch_bounds__(256) void k_randk_shift_lists(RksArgs g, int64_t n,
                 const float bv = bp[j];
                 const float e = g.scale * (ap[j] - bv);
                 tt = e * g.ms;
-                if (MODE == RKS_A) bp[j] = bv + g.alpha * e;
+                if (MODE == SHAPE_A) bp[j] = bv + g.alpha * e;
             }
             L.val[row * L.cap + t] = tt;
         }
@@ -253,7 +251,7 @@ __global__ __launch_bounds__(256) void k_randk_shift_idx(RksArgs g, int64_t n, i
     }
 }
 
-// Compat, shape C: the fold of base + t from the lists, the form of k_randk_shift<TS, RKS_C>
+// Compat, shape C: the fold of base + t from the lists, the form of k_randk_shift<TS, SHAPE_C>
 template <int TS>
 __global__ __launch_bounds__(256) void k_randk_shift_lfold(const float* __restrict__ base, int64_t n, int64_t d, RkLists L,
                                                            const float* __restrict__ w, float wt, float* __restrict__ out) {
@@ -307,40 +305,6 @@ constexpr int RKS_CTS = 1024;                               // shape C's part: 1
 static int64_t rks_chunks(int64_t d) { return (d + CHUNK - 1) / CHUNK; }
 static int rks_blocks(int64_t items, int64_t cap) { return (int)std::max<int64_t>(1, std::min<int64_t>(items, cap)); }
 
-// The accepted shape of a round (flcodec.h), or -1 with the reason set.  sr: api.hip's normalised copy
-// (no shift_in without a shift_out, leading dimensions of absent operands zeroed).  Shared with the
-// batched TopK round (topk_shift.hip), whose entry accepts the same four shapes.
-int rks_shape(const flc_shift_rows& sr, const char* me) {
-    if (!(std::isfinite(sr.msg_scale) && sr.msg_scale > 0.f)) {
-        set_error("%s: msg_scale must be finite and > 0 (got %g)", me, (double)sr.msg_scale);
-        return -1;
-    }
-    if (sr.d_shift_out) {
-        if (sr.d_base || sr.d_msg) { set_error("%s: a shift together with a base or stored messages is not a sparse shape", me); return -1; }
-        if ((const float*)sr.d_shift_out != sr.d_b || sr.d_shift_in != sr.d_b || sr.ldout != sr.ldb || sr.ldin != sr.ldb) {
-            set_error("%s: the shift must be updated in place over the b rows (d_shift_in == d_shift_out == d_b, equal leading dimensions)", me);
-            return -1;
-        }
-        if (!(std::isfinite(sr.shift_alpha) && sr.shift_alpha > 0.f)) {
-            set_error("%s: shift_alpha must be finite and > 0 (got %g)", me, (double)sr.shift_alpha);
-            return -1;
-        }
-        return RKS_A;
-    }
-    if (sr.d_msg) {
-        if (sr.d_base != sr.d_b || (const float*)sr.d_msg != sr.d_b || sr.ldbase != sr.ldb || sr.ldmsg != sr.ldb) {
-            set_error("%s: stored messages only as the in-place EF21 step (d_base == d_msg == d_b, equal leading dimensions)", me);
-            return -1;
-        }
-        return RKS_B;
-    }
-    if (sr.d_base) {
-        if (sr.ldbase != 0) { set_error("%s: a per-row base that is not d_msg == d_b (only ONE shared base, ldbase == 0, folds without a store)", me); return -1; }
-        return RKS_C;
-    }
-    return RKS_D;
-}
-
 int randk_shift_lfold_launch(const float* base, int64_t n, int64_t d, RkLists L, const float* w, float wt, float* out,
                              hipStream_t st) {
     ProfScope _ps("k_randk_shift_lfold", st);
@@ -359,27 +323,17 @@ size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n
 int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
                     const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
     const char* me = "flc_randk_shift_reduce";
-    const int shape = rks_shape(sr, me);
+    const int shape = shift_shape(sr, me);
     if (shape < 0) return FLC_ERR_UNSUPPORTED;
     const bool compat = pat && pat->d_randk_idx;
     const int64_t K = prm->k;
-    if (K < 1 || K > d) { set_error("%s: K=%lld outside [1, D=%lld]", me, (long long)K, (long long)d); return FLC_ERR_ARG; }
-    if (d >= (int64_t)0xFFFFFFFF) { set_error("%s: D too large for 32-bit entry indices", me); return FLC_ERR_ARG; }
-    if (n > 1 && (shape == RKS_A || shape == RKS_B) && (sr.ldb < 0 ? -sr.ldb : sr.ldb) < d) {
-        set_error("%s: the in-place rows overlap (|ldb| < d)", me);
-        return FLC_ERR_ARG;
-    }
+    if (int rc = sparse_round_precheck(me, shape, sr, n, d, K)) return rc;
     if (ws_bytes < randk_shift_workspace(prm, compat, n, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
     const int64_t C = rks_chunks(d);
     RksArgs g{sr.d_a, sr.lda, const_cast<float*>(sr.d_b), sr.ldb, sr.d_base, prm->randk_scale, sr.msg_scale, sr.shift_alpha};
     const unsigned gy = (unsigned)std::min<int64_t>(n, 65535);
-    auto fold_b = [&]() {                                   // shape B: the dense fold of the updated rows
-        const bool vec = (((uintptr_t)sr.d_b & 15u) == 0) && (sr.ldb % 4 == 0);
-        RowSrc rows{sr.d_b, sr.ldb, nullptr};
-        return reduce_impl(rows, vec, n, d, nullptr, w, wt, FLC_REDUCE_PLAIN, out, st);
-    };
     if (compat) {
-        if (shape == RKS_B) {
+        if (shape == SHAPE_B) {
             {
                 ProfScope _ps("k_randk_shift_lists", st);
                 const int gx = rks_blocks((K + 255) / 256, 1024);
@@ -387,7 +341,7 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
                                    pat->idx_ld ? pat->idx_ld : K);
                 FLC_CHECK_LAUNCH("k_randk_shift_idx");
             }
-            return fold_b();
+            return fold_updated_rows(sr, n, d, w, wt, out, st);
         }
         RkLists L;
         RowSrc rows{sr.d_a, sr.lda, nullptr};
@@ -395,28 +349,28 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
         {
             ProfScope _ps("k_randk_shift_lists", st);
             const int gx = rks_blocks((K + 255) / 256, 1024);
-            if (shape == RKS_A) hipLaunchKernelGGL(k_randk_shift_lists<RKS_A>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L);
-            else hipLaunchKernelGGL(k_randk_shift_lists<RKS_D>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L);
+            if (shape == SHAPE_A) hipLaunchKernelGGL(k_randk_shift_lists<SHAPE_A>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L);
+            else hipLaunchKernelGGL(k_randk_shift_lists<SHAPE_D>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L);
             FLC_CHECK_LAUNCH("k_randk_shift_lists");
         }
-        if (shape != RKS_C) return randk_lists_fold(n, d, K, ws, w, wt, out, st);
+        if (shape != SHAPE_C) return randk_lists_fold(n, d, K, ws, w, wt, out, st);
         return randk_shift_lfold_launch(sr.d_base, n, d, L, w, wt, out, st);
     }
     const uint32_t* cnt = nullptr;
     const uint64_t* ckey = nullptr;
     if (int rc = randk_device_prepare(prm, pat, n, d, ws, &cnt, &ckey, st)) return rc;
-    if (shape == RKS_B) {
+    if (shape == SHAPE_B) {
         {
             ProfScope _ps("k_randk_shift", st);
             const int gx = rks_blocks((C + 3) / 4, 4096);
             hipLaunchKernelGGL(k_randk_shift_scatter, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, cnt, ckey);
             FLC_CHECK_LAUNCH("k_randk_shift_scatter");
         }
-        return fold_b();
+        return fold_updated_rows(sr, n, d, w, wt, out, st);
     }
     ProfScope _ps("k_randk_shift", st);
     // few chunks (short rows): split each chunk's columns over 2 or 4 waves, as k_chunk_accum does
-    const int parts = shape == RKS_C ? CHUNK / RKS_CTS : (C >= 1024 ? 1 : (C >= 256 ? 2 : 4));
+    const int parts = shape == SHAPE_C ? CHUNK / RKS_CTS : (C >= 1024 ? 1 : (C >= 256 ? 2 : 4));
     const int ab = rks_blocks((C * parts + 3) / 4, 16384);
     auto go = [&](auto ts, auto mode) {
         hipLaunchKernelGGL((k_randk_shift<decltype(ts)::value, decltype(mode)::value>), dim3(ab), dim3(256), 0, st, g, n, d,
@@ -427,9 +381,9 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
         else if (parts == 2) go(std::integral_constant<int, CHUNK / 2>{}, mode);
         else go(std::integral_constant<int, CHUNK / 4>{}, mode);
     };
-    if (shape == RKS_C) go(std::integral_constant<int, RKS_CTS>{}, std::integral_constant<int, RKS_C>{});
-    else if (shape == RKS_A) by_parts(std::integral_constant<int, RKS_A>{});
-    else by_parts(std::integral_constant<int, RKS_D>{});
+    if (shape == SHAPE_C) go(std::integral_constant<int, RKS_CTS>{}, std::integral_constant<int, SHAPE_C>{});
+    else if (shape == SHAPE_A) by_parts(std::integral_constant<int, SHAPE_A>{});
+    else by_parts(std::integral_constant<int, SHAPE_D>{});
     FLC_CHECK_LAUNCH("k_randk_shift");
     return FLC_OK;
 }

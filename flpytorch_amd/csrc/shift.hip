@@ -10,6 +10,8 @@
 // written once, e never stored.  RandK / TopK / Rank-K select or factor the whole difference first:
 // a - b is formed once in the workspace, encoded by the ordinary single-row path into a second
 // workspace row, and k_shift_epi applies the same epilogue.
+#include <cmath>
+
 #include "common.hpp"
 
 namespace flc {
@@ -181,6 +183,62 @@ int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const 
         if (int rc = shift_fold_launch(m, d, w, i, i == n - 1, wt, out, st)) return rc;
     }
     return FLC_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Host plumbing shared by the sparse rounds (randk_shift.hip, topk_shift.hip, dither_shift.hip)
+// ------------------------------------------------------------------------------------------
+// sr: api.hip's normalised copy (no shift_in without a shift_out, leading dimensions of absent
+// operands zeroed)
+int shift_shape(const flc_shift_rows& sr, const char* me) {
+    if (!(std::isfinite(sr.msg_scale) && sr.msg_scale > 0.f)) {
+        set_error("%s: msg_scale must be finite and > 0 (got %g)", me, (double)sr.msg_scale);
+        return -1;
+    }
+    if (sr.d_shift_out) {
+        if (sr.d_base || sr.d_msg) { set_error("%s: a shift together with a base or stored messages is not a sparse shape", me); return -1; }
+        if ((const float*)sr.d_shift_out != sr.d_b || sr.d_shift_in != sr.d_b || sr.ldout != sr.ldb || sr.ldin != sr.ldb) {
+            set_error("%s: the shift must be updated in place over the b rows (d_shift_in == d_shift_out == d_b, equal leading dimensions)", me);
+            return -1;
+        }
+        if (!(std::isfinite(sr.shift_alpha) && sr.shift_alpha > 0.f)) {
+            set_error("%s: shift_alpha must be finite and > 0 (got %g)", me, (double)sr.shift_alpha);
+            return -1;
+        }
+        return SHAPE_A;
+    }
+    if (sr.d_msg) {
+        if (sr.d_base != sr.d_b || (const float*)sr.d_msg != sr.d_b || sr.ldbase != sr.ldb || sr.ldmsg != sr.ldb) {
+            set_error("%s: stored messages only as the in-place EF21 step (d_base == d_msg == d_b, equal leading dimensions)", me);
+            return -1;
+        }
+        return SHAPE_B;
+    }
+    if (sr.d_base) {
+        if (sr.ldbase != 0) { set_error("%s: a per-row base that is not d_msg == d_b (only ONE shared base, ldbase == 0, folds without a store)", me); return -1; }
+        return SHAPE_C;
+    }
+    return SHAPE_D;
+}
+
+int inplace_rows_check(const char* me, int shape, const flc_shift_rows& sr, int64_t n, int64_t d) {
+    if (n > 1 && (shape == SHAPE_A || shape == SHAPE_B) && (sr.ldb < 0 ? -sr.ldb : sr.ldb) < d) {
+        set_error("%s: the in-place rows overlap (|ldb| < d)", me);
+        return FLC_ERR_ARG;
+    }
+    return FLC_OK;
+}
+
+int sparse_round_precheck(const char* me, int shape, const flc_shift_rows& sr, int64_t n, int64_t d, int64_t K) {
+    if (K < 1 || K > d) { set_error("%s: K=%lld outside [1, D=%lld]", me, (long long)K, (long long)d); return FLC_ERR_ARG; }
+    if (d >= (int64_t)0xFFFFFFFF) { set_error("%s: D too large for 32-bit entry indices", me); return FLC_ERR_ARG; }
+    return inplace_rows_check(me, shape, sr, n, d);
+}
+
+int fold_updated_rows(const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt, float* out, hipStream_t st) {
+    const bool vec = (((uintptr_t)sr.d_b & 15u) == 0) && (sr.ldb % 4 == 0);
+    RowSrc rows{sr.d_b, sr.ldb, nullptr};
+    return reduce_impl(rows, vec, n, d, nullptr, w, wt, FLC_REDUCE_PLAIN, out, st);
 }
 
 }  // namespace flc

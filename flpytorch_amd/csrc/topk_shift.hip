@@ -15,10 +15,7 @@
 // Every operation is rounded separately, in the order above: a selected element and d_out carry
 // flc_encode_shift_reduce's bits; an in-place operand is written at the row's K members only.
 //
-//   shape A  DIANA / FRECON / COFIG in place   shift_in == shift_out == b       h' stored, fold of t
-//   shape B  EF21 in place                     base == msg == b (rows)          m stored, then reduce_impl
-//   shape C  MARINA                            ONE shared base, nothing stored  fold of base + t
-//   shape D  C(a - b) fold                     nothing stored                   fold of t
+// Shapes A - D: the table in flcodec.h, the folds as the RandK round's (randk_shift.hip).
 #include <algorithm>
 #include <cmath>
 
@@ -99,11 +96,11 @@ __global__ __launch_bounds__(256) void k_topk_shift_lists(TksArgs g, int64_t n, 
                 const uint64_t key = ((uint64_t)mag_key(ev) << 32) | (uint64_t)(ix ^ txm);
                 if (key >= bound && (int64_t)ix < d) {
                     const float t = ev * g.ms;
-                    if (MODE == RKS_A) {
+                    if (MODE == SHAPE_A) {
                         const float bv = bp[ix];
                         bp[ix] = bv + g.alpha * ev;
                     }
-                    if (MODE == RKS_B) {
+                    if (MODE == SHAPE_B) {
                         const float bv = bp[ix];
                         bp[ix] = bv + t;
                     } else {
@@ -144,15 +141,10 @@ size_t topk_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
 int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt,
                    float* out, void* ws, size_t ws_bytes, hipStream_t st) {
     const char* me = "flc_topk_shift_reduce";
-    const int shape = rks_shape(sr, me);
+    const int shape = shift_shape(sr, me);
     if (shape < 0) return FLC_ERR_UNSUPPORTED;
     const int64_t K = prm->k;
-    if (K < 1 || K > d) { set_error("%s: K=%lld outside [1, D=%lld]", me, (long long)K, (long long)d); return FLC_ERR_ARG; }
-    if (d >= (int64_t)0xFFFFFFFF) { set_error("%s: D too large for 32-bit entry indices", me); return FLC_ERR_ARG; }
-    if (n > 1 && (shape == RKS_A || shape == RKS_B) && (sr.ldb < 0 ? -sr.ldb : sr.ldb) < d) {
-        set_error("%s: the in-place rows overlap (|ldb| < d)", me);
-        return FLC_ERR_ARG;
-    }
+    if (int rc = sparse_round_precheck(me, shape, sr, n, d, K)) return rc;
     if (ws_bytes < topk_shift_workspace(prm, n, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
     const int64_t ldd = tks_ldd(d);
     Carver cv(ws);
@@ -179,19 +171,15 @@ int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_
         const int64_t C = nchunks(d);
         const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((C + 3) / 4, std::max<int64_t>(1, 32768 / gy)));
         const dim3 grid(gx, gy);
-        if (shape == RKS_A) hipLaunchKernelGGL(k_topk_shift_lists<RKS_A>, grid, dim3(256), 0, st, g, n, d, L);
-        else if (shape == RKS_B) hipLaunchKernelGGL(k_topk_shift_lists<RKS_B>, grid, dim3(256), 0, st, g, n, d, L);
-        else hipLaunchKernelGGL(k_topk_shift_lists<RKS_D>, grid, dim3(256), 0, st, g, n, d, L);
+        if (shape == SHAPE_A) hipLaunchKernelGGL(k_topk_shift_lists<SHAPE_A>, grid, dim3(256), 0, st, g, n, d, L);
+        else if (shape == SHAPE_B) hipLaunchKernelGGL(k_topk_shift_lists<SHAPE_B>, grid, dim3(256), 0, st, g, n, d, L);
+        else hipLaunchKernelGGL(k_topk_shift_lists<SHAPE_D>, grid, dim3(256), 0, st, g, n, d, L);
         FLC_CHECK_LAUNCH("k_topk_shift_lists");
     }
     hipLaunchKernelGGL(k_topk_shift_admit, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 256)), dim3(256), 0, st, n, L);
     FLC_CHECK_LAUNCH("k_topk_shift_admit");
-    if (shape == RKS_B) {                                     // the dense fold of the updated rows
-        const bool vec = (((uintptr_t)sr.d_b & 15u) == 0) && (sr.ldb % 4 == 0);
-        RowSrc brows{sr.d_b, sr.ldb, nullptr};
-        return reduce_impl(brows, vec, n, d, nullptr, w, wt, FLC_REDUCE_PLAIN, out, st);
-    }
-    if (shape == RKS_C) {
+    if (shape == SHAPE_B) return fold_updated_rows(sr, n, d, w, wt, out, st);
+    if (shape == SHAPE_C) {
         RkLists R{L.tab, L.ent_idx, L.ent_val, L.cap};
         return randk_shift_lfold_launch(sr.d_base, n, d, R, w, wt, out, st);
     }

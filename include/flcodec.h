@@ -290,7 +290,9 @@ int flc_encode_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat,
  * replacement; an index >= d is never stored to), or device draws from (seed, client0 + i), with
  * d_randk_counts ([ceil(d / 4096)][n], flc_device_randk_counts) honoured when given.
  *
- * Accepted shapes, recognised by pointer and leading dimension:
+ * THE SHAPE TABLE of the sparse rounds (this entry, flc_topk_shift_reduce and
+ * flc_dither_shift_reduce; stated here once).  Accepted shapes, recognised by pointer and leading
+ * dimension:
  *   A  DIANA / FRECON / COFIG in place: no base, no d_msg, d_shift_in == d_shift_out == d_b with
  *      equal leading dimensions.  Only row i's K selected elements of h_i are read and written;
  *      d_out is the fold of the sparse messages.
@@ -350,30 +352,9 @@ int flc_randk_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat, 
  * d_out is folded in row order, the first term assigned, d_w == NULL meaning no multiply, one
  * division by w_total at the end.
  *
- * Accepted shapes, recognised by pointer and leading dimension (those of flc_randk_shift_reduce):
- *   A  DIANA / FRECON / COFIG in place: no base, no d_msg, d_shift_in == d_shift_out == d_b with
- *      equal leading dimensions.  Only row i's K selected elements of h_i are written; d_out is the
- *      fold of the sparse messages.
- *   B  EF21 in place: d_base == d_msg == d_b with equal leading dimensions, no shift.  Only the K
- *      selected elements of g_prev_i are written (the K-sparse scatter); d_out is then the dense fold
- *      of the updated rows (flc_reduce_matrix's pass on the same stream: 4 n d bytes read).
- *   C  MARINA: ONE shared [d] base (ldbase == 0), no d_msg, no shift.  d_out is the fold of
- *      base + t_i; a row that did not select column j contributes exactly
- *      w_i * (base[j] + 0.0f * msg_scale) (evaluated, not skipped).
- *   D  the plain fold of C_i(a_i - b_i) * msg_scale: no base, no d_msg, no shift.
- *
- * THE CONTRACT that makes this an entry of its own: elements of an in-place operand (h_i in A,
- * g_prev_i in B) OUTSIDE row i's index set are NOT WRITTEN.  flc_encode_shift_reduce stores
- * x + (+0) there, which is x for every float except -0, which becomes +0.  Therefore
- *   - every element of h_i' / g_next_i that row i selected has exactly flc_encode_shift's bits;
- *   - every other element keeps its stored bits;
- *   - if the in-place operand holds no -0 at an unselected place, the rows and d_out are
- *     bit-identical to flc_encode_shift_reduce's.  That is the case whenever the operand started
- *     as +0 and was only ever updated by these steps (a sum is -0 only when both operands are);
- *   - if it does hold one, the row differs from the dense step only in that zero's sign, and in
- *     shape B d_out can differ only in the sign of a zero;
- *   - shapes C and D have no in-place operand: bit-identical to flc_encode_shift_reduce without
- *     condition, the -0 columns of the fold included.
+ * Accepted shapes: A, B, C and D of flc_randk_shift_reduce's shape table, with S_i as the row's
+ * index set, and THE CONTRACT stated there: elements of an in-place operand outside S_i are NOT
+ * WRITTEN, with the same consequences for the bits of the rows and of d_out.
  *
  * FLC_ERR_UNSUPPORTED before any launch (the caller then uses flc_encode_shift_reduce): a codec
  * other than FLC_TOPK (the size query then returns 0); any other operand shape (a dense output
@@ -412,14 +393,9 @@ int flc_topk_shift_reduce(const flc_codec_params* prm, const flc_shift_rows* row
  * NULL).  d_out is folded in row order, the first term assigned, d_w == NULL meaning no multiply,
  * one division by w_total at the end.
  *
- * Accepted shapes, recognised by pointer and leading dimension as flc_randk_shift_reduce does:
- *   A  DIANA / FRECON / COFIG in place: no base, no d_msg, d_shift_in == d_shift_out == d_b with
- *      equal leading dimensions, msg_scale == 1.0f.  d_out is the fold of the messages.
- *   B  EF21 in place: d_base == d_msg == d_b with equal leading dimensions, no shift, any finite
- *      msg_scale > 0.  g_prev_i[j] += e * msg_scale at the nonzero elements; d_out is then the dense
- *      fold of the updated rows (flc_reduce_matrix's pass on the same stream).
- *   D  the plain fold of C_i(a_i - b_i): no base, no d_msg, no shift, msg_scale == 1.0f.
- *   (C, MARINA's one shared base, is refused: its fold needs the (index, value) list form.)
+ * Accepted shapes: A, B and D of flc_randk_shift_reduce's shape table, with msg_scale == 1.0f in A
+ * and D (the messages themselves are folded; B takes any finite msg_scale > 0).  C, MARINA's one
+ * shared base, is refused: its fold needs the (index, value) list form.
  *
  * THE CONTRACT is flc_randk_shift_reduce's with "selected" read as "e is nonzero": an element of
  * the in-place operand whose encoded value is +-0 is NOT WRITTEN (flc_encode_shift_reduce stores
