@@ -1,4 +1,4 @@
-// Chunked-row helpers shared by the sparsifying paths (select.hip: TopK / RandK;
+// Chunked-row helpers shared by the sparsifying paths (the selection core, select_impl.hpp: TopK / RandK;
 // dither_sparse.hip: sparse QSGD): chunk = 4096 elements = one wave's tile of 16 wave-loads.
 #pragma once
 #include "common.hpp"

@@ -111,7 +111,7 @@ struct RowSrc {
     }
 };
 
-// Internal entry points of the codec families (reduce.hip, codecs.hip, select.hip).
+// Internal entry points of the codec families (reduce.hip, codecs.hip, select.hip with randk.hip and chunk_accum.hip).
 int reduce_impl(RowSrc src, bool rows_vec_ok, int64_t n, int64_t d, const float* x, const float* w, float wt,
                 int mode, float* out, hipStream_t st);
 // norms_given / norm_mode: flc_encode_reduce_ex's selectors (0, FLC_NORMMODE_EXACT: flc_encode_reduce)

@@ -11,13 +11,13 @@
 // Shapes A - D: the table in flcodec.h (shift_shape, shift.hip).  A stores h' and folds t, B stores m
 // and folds the updated rows (fold_updated_rows), C folds base + t, D folds t.
 //
-// Device draws: k_randk_shift, k_randk_fold's walk (select.hip) with two gathers per member and an
+// Device draws: k_randk_shift, k_randk_fold's walk (randk.hip) with two gathers per member and an
 // epilogue — one wave per chunk (or 1/2, 1/4 of its columns), rows in order, AP rows' gathers in
 // flight.  The lane that loaded b_q[j] is the only one that stores to (q, j), and a row's members
 // are distinct, so in place is safe.  Shape C keeps the sum in registers (the LDS tile holds the
 // current row's t by column, +0 elsewhere): every column takes w_q * (base[j] + tile[j]) per row,
 // which is w_q * (base[j] + 0.0f * msg_scale) outside the row's set (msg_scale is finite and > 0).
-// Compat draws: the chunk-bucketed lists of select.hip (k_randk_coarse / k_randk_fine), their values
+// Compat draws: the chunk-bucketed lists of randk.hip (k_randk_coarse / k_randk_fine), their values
 // rewritten to t by k_randk_shift_lists (which also stores the in-place element), then k_chunk_accum
 // (A, D) or the list form of the shape C fold.  Shape B needs no lists.
 #include <algorithm>

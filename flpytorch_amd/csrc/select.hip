@@ -1,303 +1,11 @@
-// Sparsifying codecs: TopK (compressors.py:330-335) and RandK (240-245), dense single-vector
-// encode and fused batch encode + reduce.
-//
-// Data flow of the batch path (N client rows x D, chunk = 4096 elements = one wave's tile):
-//
-//   TopK  sample   : one workgroup per row keys a spread sample (<= 16 K elements, LDS) and picks a
-//                    conservative threshold T_lo with count(|x| >= T_lo) >= K w.h.p.
-//         filter   : ONE pass over every row (the only full HBM read): entries with key >= T_lo
-//                    are appended to the row's candidate list (idx, val), per chunk -> tab[c][row]
-//         select   : exact K-th largest key among the candidates (3 radix passes, 11/11/9 bits)
-//         fallback : rows whose list overflowed, came up short (sample unlucky), or whose K-th
-//                    magnitude is tied ambiguously are redone exactly on the full row
-//                    (3 radix passes + tie prefix + exact filter, ties -> lowest index first)
-//   RandK device   : the device sampler (randk_tree.hpp) is generated chunk by chunk: per row the
-//                    chunk counts (k_randk_counts, a hypergeometric tree), then one wave per chunk
-//                    regenerates every row's members of its chunk, gathers (D/K) * x[j] and folds
-//                    them in row order (k_randk_fold) — no index lists in memory; the only HBM
-//                    traffic is the gathered 128-B lines and the [D] result
-//   RandK compat   : the K numpy-stream indices of each row are bucketed by chunk in two coalesced
-//                    levels — superchunks in one workgroup per row (LDS counts + multi-split),
-//                    then chunks inside each superchunk (LDS counting sort) with the gather of
-//                    (D/K) * x[j] in ascending order (k_randk_coarse / k_randk_fine)
-//   accumulate     : one wave owns one chunk (or 1/2, 1/4 of it when the rows are short) as an
-//                    fp32 LDS tile and folds the rows' admitted
-//                    entries in row order -> (sum_i w_i C_i(x_i)) / w_total, bit-identical to the
-//                    sequential reduction of the dense compressVector outputs (indices are
-//                    distinct within a row, so every element sees its terms in row order).
-//
-// Keys: |x| bits with the sign cleared (uint32, monotone; NaN above inf like torch.topk).
-#include <stdlib.h>
-
-#include <atomic>
-#include <map>
-#include <mutex>
-#include <vector>
-
-#include "chunks.hpp"
-#include "randk_tree.hpp"
+// The selection core's host end and its TopK kernels: workspace sizes and carving, the TopK pipeline
+// (sample, filters, candidate selects, radix and exact fallback, tie kernels, the lone resident
+// row), sel_run — a dispatcher over the TopK regimes and the RandK paths — the lists on their own for
+// the shifted rounds, and the sparse wire unpack.  RandK: randk.hip; the chunk-owner fold:
+// chunk_accum.hip.  Data flow, workspace and switches: select_impl.hpp.
+#include "select_impl.hpp"
 
 namespace flc {
-
-constexpr uint32_t ALL = 0xFFFFFFFFu;
-constexpr uint32_t F_OVERFLOW = 1u, F_SHORT = 2u, F_TIES = 4u, F_EXACT = 8u;
-constexpr uint32_t F_RESIDENT = 16u;  // a lone row selected exactly in registers (k_lone_resident)
-constexpr uint32_t F_REPAIR = 32u;    // ... whose grid was not co-resident: re-selected by its last workgroup
-constexpr int SMAX = 16384;          // sample size kept in LDS
-constexpr int HBINS = 2048;          // radix histogram bins (11 bits)
-constexpr uint32_t TIECAP = HBINS;   // fast-path tie list (LDS); more ties at the K-th key -> exact path
-constexpr int CS_SH = 64;            // few rows: shards of a row's candidate list (k_cs_pass workgroups)
-constexpr int64_t CS_FEW = 16;       // rows: sharded lists + k_cs_pass up to here, else k_cand_select
-constexpr int CS_ST = 8;             // words of a row's k_cs_pass state
-constexpr int CS_LCAP = 2048;        // entries of the first digit's bin ranked directly (list mode)
-constexpr int RS_U = 16;             // (<= 16: kept-tie mask of 64 bits) k_lone_resident: float4 of the row per thread at most (64 VGPRs)
-#ifndef FLC_RS_NG
-#define FLC_RS_NG 4                   // k_lone_resident: workgroup groups (histogram replicas, barrier tree);
-#endif                                // us a call at D = 10 M: 1 -> 57, 2 -> 53, 4 -> 52, 8 -> 54.6, 16 -> 60
-constexpr int RS_NG = FLC_RS_NG;
-constexpr int RS_NG_MAX = 16;
-static_assert(RS_NG >= 1 && RS_NG <= RS_NG_MAX, "FLC_RS_NG: 1..16 groups");
-// its control words: counters on lines of their own, per-group digit histograms, tie counts
-// (RS_GAVE: the sequence number of a call that was aborted; RS_XGRP: workgroups that have left)
-constexpr int RS_GLOB = 0, RS_GEN = 32, RS_GAVE = 64, RS_CCNT = 96, RS_CDONE = 112, RS_GRP = 128;
-constexpr int RS_XGRP = RS_GRP + 32 * RS_NG_MAX;  // per group: workgroups counted out (runs on across calls)
-constexpr int RS_ABV = RS_XGRP + 32 * RS_NG_MAX;   // per group: keys above the speculated first digits
-constexpr int RS_CAP = 2048;          // candidates (22-bit prefix of the K-th key) ranked by the last workgroup
-constexpr int RS_SS = 8192;           // the speculative first digit's sample (32 pieces of 256)
-#ifndef FLC_RS_SR
-#define FLC_RS_SR 1                   // replicas of the sample's histogram (LDS; 8 measured 0.35 us slower a call)
-#endif
-constexpr int RS_SR = FLC_RS_SR;
-#ifndef FLC_RS_STPOL
-#define FLC_RS_STPOL 2                // the dense output's stores: nontemporal (2) or default (0)
-#endif
-#ifndef FLC_RS_GACQ
-#define FLC_RS_GACQ 1                 // k_lone_resident: a group's last arriver acquires before its release
-#endif
-#ifndef FLC_RS_POLLAB
-#define FLC_RS_POLLAB 1               // k_lone_resident: a grid wait reads the abort word every n-th poll
-#endif
-#ifndef FLC_RS_DONE
-// k_lone_resident's candidate hand-over: 1 = a workgroup holding candidates reserves their place in
-// the shared list (one returning add), stores them and then adds their number to a delivered count;
-// the ranking workgroup waits for that count to reach the candidates' total (known to all from the
-// round's payload), not for every workgroup to count out, and reads the list in one pass.
-// 0 = per-workgroup slots gathered after every workgroup counted out.
-#define FLC_RS_DONE 1
-#endif
-#ifndef FLC_RS_RANKFIRST
-#define FLC_RS_RANKFIRST 0            // 1: the ranking workgroup ranks before its own dense stores (measured 0.2 us slower)
-#endif
-#ifndef FLC_RS_PROBE_NOCOUNT
-#define FLC_RS_PROBE_NOCOUNT 0        // (cost probes only: no exit count — an aborted call would not repair)
-#endif
-#ifndef FLC_RS_G0REL
-#define FLC_RS_G0REL 1                // workgroup 0 releases the row state before it counts out
-#endif
-#ifndef FLC_RS_FENCE
-// k_lone_resident's grid rounds: 1 = agent-scope release / acquire fences around the counters (an
-// L2 write-back or L1 invalidate each, ~1.7 us; five on the last arriver's path); 0 = no fences —
-// every byte handed over inside the launch is written by an agent-scope atomic (histogram adds,
-// list entries, counters, the release word) and read by agent-scope (sc1) loads, every writing
-// wave drains (vmcnt(0)) before its workgroup's one counter add, and the counters never need a
-// reset store (see rs_arrive)
-#define FLC_RS_FENCE 0
-#endif
-#ifndef FLC_RS_SPEC
-#define FLC_RS_SPEC 1                 // k_lone_resident: speculative first digit (two digits in one round)
-#endif
-constexpr int RS_HREP = RS_ABV + 32 * RS_NG_MAX;
-constexpr int RS_HSPEC = RS_HREP + 3 * RS_NG * HBINS;    // [RS_NG][3][HBINS] speculative second digit
-constexpr int RS_CLIST = RS_HSPEC + 3 * RS_NG * HBINS;   // [RS_CAP] (value bits, index)
-constexpr int RS_TCNT = RS_CLIST + 2 * RS_CAP;               // (tie counts: 64-bit (call << 32 | count) per workgroup)
-constexpr int RS_GMAX = 1024;                                  // workgroups a launch may have (tie counts, list slots)
-constexpr int RS_CS = 4;                                       // listed elements a workgroup keeps in slots of its own
-constexpr int RS_CNUM = RS_TCNT + 2 * RS_GMAX;                 // [RS_GMAX] elements a workgroup listed (this call)
-constexpr int RS_CREG = RS_CNUM + RS_GMAX;                     // [RS_GMAX][RS_CS] 64-bit (value bits, index)
-#ifdef FLC_RS_PRINT
-constexpr int RS_PROBE = RS_CREG + 2 * RS_CS * RS_GMAX;        // probe builds: per-workgroup phase stamps
-constexpr int RS_CTL = RS_PROBE + 4096;
-#else
-constexpr int RS_CTL = RS_CREG + 2 * RS_CS * RS_GMAX;
-#endif
-#ifndef FLC_RS_SPECST
-#define FLC_RS_SPECST 0               // 1: the dense output outside the speculative window stored during the round (slower: 42.5 vs 36.7 us, the writes delay the merger)
-#endif
-#ifndef FLC_CS_LIST
-#define FLC_CS_LIST 1
-#endif
-#ifndef FLC_CS_TWO_MAXD
-#define FLC_CS_TWO_MAXD (int64_t(64) << 20)   // rows up to this long: two k_cs_pass launches
-#endif
-
-struct SelWs {            // carved from the caller workspace
-    uint2* tab;           // [C][N] (offset, count) of each row's entries in chunk c
-    uint32_t* ent_idx;    // [N][cap] element index within the row
-    float* ent_val;       // [N][cap] entry value (already scaled for RandK)
-    uint32_t* rowcnt;     // [N * RCS] entries used (one counter per 128 B line)
-    uint32_t* flags;      // [N]
-    uint32_t* thr;        // [N] admission key: entries with key >= thr are summed
-    uint32_t* prefix;     // [N] radix-select state
-    uint32_t* krem;       // [N]
-    uint32_t* tieprefix;  // [C][N] ties (key == thr) in chunks before c   (exact path only)
-    uint32_t* tiecut;     // [N] fast path, F_TIES: the last index admitted among key == thr (tie_pref order);
-                          // rows selected by k_radix_select<FULLROW> (dense K): the count of keys == thr
-    uint32_t* hist;       // [N][HBINS]
-    uint32_t* worklist;   // [N] rows on the exact path
-    uint32_t* nwork;      // [1]
-    uint32_t* cursor;     // [C][N] RandK scatter cursors
-    uint32_t* cstate;     // [N][CS_ST] few-row candidate select: shift, prefix, krem, stage, bin count, list fill (k_cs_pass)
-    uint64_t* clist;      // [min(N, CS_FEW)][CS_LCAP] few rows: the first digit bin's entries (k_cs_pass list mode)
-    uint32_t* carrive;    // [N * RCS] its per-row arrival counters
-    uint32_t* shcnt;      // [N][CS_SH * RCS] few rows: the filter's reservation counters, one per shard
-    uint32_t* zm;         // [C][CHUNK / 32] k_chunk_accum (one-wave blocks): a fold job's kept-column mask
-    float* part;          // [D] TopK row-group folds: the running tiles carried from one group to the next
-    int64_t cap;
-    uint32_t tie_hi;      // TopK ties at the K-th key: 0 the lowest indices are kept (default), 1 the highest
-};
-
-// Tie order of TopK (flc_codec_params.tie): tie_pref(ix) is larger for the index kept first among
-// equal magnitudes — ~ix for the lowest-index rule (the oracle's, torch.topk's CPU order on the
-// reference's rows), ix for the highest-index rule.  A row's tie cut is the last kept tie's index:
-// a tie is admitted iff tie_pref(ix) >= tie_pref(cut); tie_all(ws) is the cut that admits every tie.
-__device__ __host__ inline uint32_t tie_pref(uint32_t ix, uint32_t hi) { return hi ? ix : ~ix; }
-__device__ __host__ inline uint32_t tie_all(uint32_t hi) { return hi ? 0u : 0xFFFFFFFFu; }
-
-
-// ------------------------------------------------------------------------------------------
-// Block-level helpers
-// ------------------------------------------------------------------------------------------
-// Find, scanning a 2048-bin histogram from the TOP bin down, the bin b where the running count
-// reaches k (1-based).  Returns b and the count strictly above b.  256 threads, 8 bins each.
-// (t, own): the thread's index in the 256 that scan; every thread of the block takes the barriers.
-// A workgroup barrier for LDS only: this wave's LDS operations done, then s_barrier — unlike
-// __syncthreads it does not wait for the wave's global loads (vmcnt), so loads stay in flight.
-__device__ inline void lds_bar() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-template <bool RAW>
-__device__ inline void blk_bar() {
-    if (RAW) lds_bar();
-    else __syncthreads();
-}
-template <bool RAW = false>
-__device__ inline void hist_find_at(const uint32_t* h, uint32_t k, uint32_t& bin, uint32_t& above,
-                                    uint32_t* scratch /* LDS 256+2 */, int t, bool own) {
-    // thread t owns bins [HBINS-8(t+1), HBINS-8t)  (top bins first)
-    uint32_t local[8];
-    uint32_t s = 0;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { local[q] = own ? h[HBINS - 1 - (t * 8 + q)] : 0u; s += local[q]; }
-    if (t == 0) { scratch[256] = 0; scratch[257] = 0; }   // defined result even if k > total
-    // inclusive scan over the 256 thread sums: inside each wave by shuffles, then the totals of the
-    // waves before (one barrier instead of the 16 of a Hillis-Steele scan through LDS)
-    const int lane = t & 63, w = t >> 6;
-    uint32_t inc = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(inc, off, 64);
-        inc += lane >= off ? v : 0u;
-    }
-    if (own && lane == 63) scratch[w] = inc;
-    blk_bar<RAW>();
-    uint32_t before = 0;
-    if (own)
-        for (int q = 0; q < w; ++q) before += scratch[q];
-    uint32_t incl = own ? before + inc : 0u, excl = incl - s;
-    if (own && excl < k && incl >= k) {
-        uint32_t run = excl;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            if (run + local[q] >= k) {
-                scratch[256] = (uint32_t)(HBINS - 1 - (t * 8 + q));
-                scratch[257] = run;
-                break;
-            }
-            run += local[q];
-        }
-    }
-    blk_bar<RAW>();
-    bin = scratch[256];
-    above = scratch[257];
-    blk_bar<RAW>();
-}
-// The same search over NB bins (NB / 256 a thread, threads 0..255 of a larger block; the rest only
-// sync); found = false when the bins hold fewer than k in all.
-template <int NB>
-__device__ inline void hist_find_n(const uint32_t* h, uint32_t k, uint32_t& bin, uint32_t& above, bool& found,
-                                   uint32_t* scratch /* LDS 256+3 */) {
-    constexpr int PER = NB / 256;
-    static_assert(NB % 256 == 0, "256 threads scan NB / 256 bins each");
-    const int t = (int)threadIdx.x;
-    const bool own = t < 256;
-    uint32_t local[PER];
-    uint32_t s = 0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) { local[q] = own ? h[NB - 1 - (t * PER + q)] : 0u; s += local[q]; }
-    if (t == 0) { scratch[256] = 0; scratch[257] = 0; scratch[258] = 0; }
-    const int lane = t & 63, w = t >> 6;
-    uint32_t inc = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(inc, off, 64);
-        inc += lane >= off ? v : 0u;
-    }
-    if (own && lane == 63) scratch[w] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    if (own)
-        for (int q = 0; q < w; ++q) before += scratch[q];
-    const uint32_t incl = own ? before + inc : 0u, excl = incl - s;
-    if (own && excl < k && incl >= k) {
-        uint32_t run = excl;
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            if (run + local[q] >= k) {
-                scratch[256] = (uint32_t)(NB - 1 - (t * PER + q));
-                scratch[257] = run;
-                scratch[258] = 1;
-                break;
-            }
-            run += local[q];
-        }
-    }
-    __syncthreads();
-    bin = scratch[256];
-    above = scratch[257];
-    found = scratch[258] != 0u;
-    __syncthreads();
-}
-template <bool RAW = false>
-__device__ inline void hist_find(const uint32_t* h, uint32_t k, uint32_t& bin, uint32_t& above,
-                                 uint32_t* scratch /* LDS 256+2 */) {
-    hist_find_at<RAW>(h, k, bin, above, scratch, (int)threadIdx.x, threadIdx.x < 256);   // larger blocks: the rest only sync
-}
-// Two searches side by side (blocks of >= 512 threads): threads 0-255 scan ha for ka, 256-511 hb for kb.
-__device__ inline void hist_find2(const uint32_t* ha, uint32_t ka, uint32_t& bina, uint32_t& abovea, uint32_t* sa,
-                                  const uint32_t* hb, uint32_t kb, uint32_t& binb, uint32_t& aboveb, uint32_t* sb) {
-    const bool second = threadIdx.x >= 256;
-    uint32_t bin, above;
-    hist_find_at(second ? hb : ha, second ? kb : ka, bin, above, second ? sb : sa, (int)(threadIdx.x & 255u),
-                 threadIdx.x < 512);
-    bina = sa[256]; abovea = sa[257];
-    binb = sb[256]; aboveb = sb[257];
-    __syncthreads();
-}
-
-// pass p: 0 -> bits [30:20], 1 -> [19:9], 2 -> [8:0]
-__device__ inline uint32_t pass_shift(int p) { return p == 0 ? 20u : (p == 1 ? 9u : 0u); }
-__device__ inline uint32_t pass_bits(int p) { return p == 2 ? 9u : 11u; }
-__device__ inline bool key_in_prefix(uint32_t key, int p, uint32_t prefix) {
-    // prefix holds the bits above this pass's field
-    if (p == 0) return true;
-    uint32_t sh = pass_shift(p) + pass_bits(p);
-    return (key >> sh) == prefix;
-}
-__device__ inline uint32_t key_bin(uint32_t key, int p) {
-    return (key >> pass_shift(p)) & ((1u << pass_bits(p)) - 1u);
-}
 
 // ------------------------------------------------------------------------------------------
 // TopK: sample threshold (one workgroup per row)
@@ -423,10 +131,7 @@ __global__ __launch_bounds__(NT) void k_topk_sample(RowSrc rows, int64_t n, int6
 // path.  Result as k_radix_select's last pass: thr = K-th key, krem = ties to admit, F_TIES when
 // the list has more keys equal to thr than that.
 // ------------------------------------------------------------------------------------------
-// candidate values of a row, read twice per launch (measured: nt loads 0.335 -> 0.293 ms at C3)
-#ifndef FLC_CS_NT
-#define FLC_CS_NT 1
-#endif
+// candidate values of a row, read twice per launch (FLC_CS_NT: nontemporal loads)
 __device__ inline float4 cs_ld(const float4* p) {
 #if FLC_CS_NT
     typedef float v4f __attribute__((ext_vector_type(4)));
@@ -924,20 +629,6 @@ __global__ __launch_bounds__(256) void k_topk_filter(RowSrc rows, int64_t n, int
 // ~20 % of the filter's bandwidth (tools/probe_filter.hip); a group of 4 amortises them 4x and the
 // copy-out stores become full 256 B wave writes.
 // ------------------------------------------------------------------------------------------
-constexpr int GCAP = 512;             // staged entries per group (4 chunks: 3.1 %, ~2.5x the mean at 1.2 %; more -> row overflow)
-static_assert(GCAP % 64 == 0, "copy-out runs in whole wave slots");
-
-
-#ifndef FLC_TK_STPOL
-#define FLC_TK_STPOL 0               // A/B: the filter's list copy-out stores nontemporal (2) or default (0)
-#endif
-#ifndef FLC_TK_COPY4
-#define FLC_TK_COPY4 1               // TopK filter copy-out: 16-B stores of whole quads
-#endif
-#ifndef FLC_TK_PROBE
-#define FLC_TK_PROBE 0               // A/B cost probes (outputs NOT valid): 1 no staging writes, 2 no copy-out, 3 loads only,
-                                     // 4 copy-out aimed at a small per-wave region that stays in the L2 (reservation and tab real)
-#endif
 
 // Copy-out of one 4-chunk group's staged entries (tot of them, indices at si, values at sv) to
 // position pos of row's list, as 16-B stores of 4 entries a lane (the group's whole quads) plus the
@@ -975,12 +666,6 @@ __device__ inline void tk_copy_out(const uint32_t* si, const uint32_t* sv, const
 // num_records 0 and its loads return zeros without touching memory).
 // FGS: chunks per work item (group).
 template <int RING, int FGS, int LONE = 0>
-#ifndef FLC_TK_RING
-#define FLC_TK_RING 16               // loads in flight per wave (ring registers: 4 x RING VGPRs)
-#endif
-#ifndef FLC_TK_WPE
-#define FLC_TK_WPE 1                 // unconstrained (143 VGPRs); 4 waves per SIMD spilled and ran slower
-#endif
 // LONE (a lone compressVector row on the list path): every float4 read is also written as zeros to
 // zout, the dense output the selected entries are then scattered into (no separate fill of the output).
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FLC_TK_WPE))) void k_topk_filter_fast(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_t rb, int64_t d, SelWs ws, int shards,
@@ -1174,24 +859,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FLC_TK_WPE)
 // own workgroup to stage item k, a loader only for the writer to have drained item k - 2, and all
 // waves of a workgroup are resident together; by induction over k nothing waits for ever.
 // ------------------------------------------------------------------------------------------
-#ifndef FLC_TK_WG
-#define FLC_TK_WG 1                   // many-row TopK filter: 1 workgroup items, 0 the per-wave groups of k_topk_filter_fast
-#endif
-#ifndef FLC_TK_WG_NL
-#define FLC_TK_WG_NL 4                // loader waves (groups per item); the workgroup has one wave more (3: +0.02 ms at C3)
-#endif
-#ifndef FLC_TK_WG_RING
-#define FLC_TK_WG_RING FLC_TK_RING    // loads in flight per loader wave (8: 73 VGPRs, four workgroups per CU, the same step time,
-                                      // but the side stream's sample ran 1.19 instead of 0.14 ms beside it)
-#endif
-#ifndef FLC_TK_WG_STPOL
-#define FLC_TK_WG_STPOL 17            // the writer's copy-out stores: sc0 sc1, written through the L2 at once: C3 -0.11 .. -0.18 ms
-                                      // a step against k_topk_filter_fast, same allocation; 0 (default policy) -0.045, sc1 alone
-                                      // as 17, sc0 -0.03, nt 0, sc1 nt / sc0 sc1 nt +0.12 (profiles/r07/wgfilter/)
-#endif
-#ifndef FLC_TK_WG_WPE
-#define FLC_TK_WG_WPE 4               // 127 VGPRs: three 5-wave workgroups per CU (unconstrained: 129 VGPRs, two, +0.66 ms at C3)
-#endif
 __device__ inline uint32_t lds_addr(const void* p) {
     return (uint32_t)(size_t)(const __attribute__((address_space(3))) void*)p;
 }
@@ -1465,32 +1132,6 @@ __global__ void k_build_worklist(int64_t n, int64_t K, int64_t d, SelWs ws, int 
 // the whole list).  The same selection as the multi-launch path (k_build_worklist, k_radix_*,
 // k_tie_*, k_topk_filter<true>) that dense-K rows take, without its ~10 launches per call when no
 // row failed.
-constexpr int EX_NT = 1024;
-constexpr int EX_U = 8;                      // float4 loads per thread in flight in the radix passes
-
-// exclusive prefix of v over the workgroup's threads (in thread order) and the total
-template <int NT = EX_NT>
-__device__ inline uint32_t ex_scan(uint32_t v, uint32_t* wsum /* LDS [NT / 64] */, uint32_t& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(inc, o, 64);
-        inc += lane >= o ? t : 0u;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < NT / 64; ++k) {
-        const uint32_t x = wsum[k];
-        before += k < wv ? x : 0u;
-        tot += x;
-    }
-    __syncthreads();
-    total = tot;
-    return before + inc - v;
-}
 
 // One row's exact selection by one EX_NT-thread workgroup: three radix passes over the row, then the
 // row's list rewritten with exactly its admitted entries in index order (ties: the lowest indices).
@@ -1687,884 +1328,6 @@ __global__ __launch_bounds__(256) void k_tie_scan(int64_t n, int64_t d, SelWs ws
     }
 }
 
-// ------------------------------------------------------------------------------------------
-// RandK compat lists (indices given: the reference's numpy-stream draws)
-// ------------------------------------------------------------------------------------------
-// Chunk-bucketed RandK lists in two coalesced levels.
-//   k_randk_coarse (one workgroup per row): the row's K indices copied once into the row's ent_val region;
-//     LDS counts per superchunk (SB buckets of SPC chunks), LDS scan, then each index appended to
-//     its superchunk's segment of ent_idx: SB write frontiers per row, which stay in L2.
-//   k_randk_fine (one workgroup per (superchunk, row)): counting sort of the segment by chunk with
-//     LDS counters (the segment is copied to ent_val first, scattered back inside the segment),
-//     the (offset, count) table entries, then the gather (D/K) * x[j] in ascending chunk order.
-constexpr int RK_T = 1024;
-constexpr int RK_SB = 256;                   // superchunks per row (max)
-constexpr int RK_TILE = 8192;                // indices per LDS multi-split tile (32 KB)
-
-__host__ __device__ inline int64_t rk_spc(int64_t C) { return (C + RK_SB - 1) / RK_SB; }   // chunks per superchunk
-
-template <class Emit>
-__device__ inline void randk_walk(const flc_pattern& pat, int64_t row, int64_t K, int64_t ldi, int tid, Emit emit) {
-    for (int64_t t = tid; t < K; t += RK_T) emit(t, (uint32_t)pat.d_randk_idx[row * ldi + t]);
-}
-
-// FINAL (one chunk per superchunk, C <= RK_SB): the superchunks are the chunks, so this kernel also
-// writes the (offset, count) table and gathers the values; k_randk_fine is skipped.
-template <bool FINAL>
-__global__ __launch_bounds__(RK_T) void k_randk_coarse(RowSrc rows, int64_t n, int64_t d, int64_t K, flc_pattern pat,
-                                                       int64_t ldi, float scale, SelWs ws) {
-    __shared__ uint32_t cnt[RK_SB], tcnt[RK_SB], toff[RK_SB], gbase[RK_SB];
-    __shared__ uint32_t tile[RK_TILE];
-    const int64_t row = blockIdx.x;
-    const int64_t C = nchunks(d), spc = rk_spc(C);
-    const int tid = threadIdx.x;
-    if (tid < RK_SB) cnt[tid] = 0;
-    __syncthreads();
-    uint32_t* jbuf = reinterpret_cast<uint32_t*>(ws.ent_val + row * ws.cap);
-    randk_walk(pat, row, K, ldi, tid, [&](int64_t t, uint32_t j) {
-        jbuf[t] = j;
-        atomicAdd(&cnt[(j >> CHUNK_SHIFT) / spc], 1u);
-    });
-    __syncthreads();
-    if (tid < 64) {                          // exclusive scan of the RK_SB counts: 4 per lane
-        uint32_t v[RK_SB / 64], loc = 0;
-#pragma unroll
-        for (int q = 0; q < RK_SB / 64; ++q) { v[q] = cnt[tid * (RK_SB / 64) + q]; loc += v[q]; }
-        uint32_t incl = loc;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t u = __shfl_up(incl, o, WAVE);
-            if (tid >= o) incl += u;
-        }
-        uint32_t run = incl - loc;
-#pragma unroll
-        for (int q = 0; q < RK_SB / 64; ++q) {
-            const int b = tid * (RK_SB / 64) + q;
-            if (FINAL) {
-                if (b < C) ws.tab[(int64_t)b * n + row] = make_uint2(run, v[q]);
-            } else {
-                ws.cursor[row * RK_SB + b] = run;         // segment offsets, read by k_randk_fine
-            }
-            cnt[b] = run;
-            run += v[q];
-        }
-    }
-    __syncthreads();
-    // Append to the superchunk segments tile by tile: an LDS counting sort of RK_TILE indices, then
-    // each bucket's run of the tile is written contiguously (a scattered 4-B store per index would
-    // run at a small fraction of the store rate).  Thread tid only re-reads jbuf slots it wrote.
-    uint32_t* oi = ws.ent_idx + row * ws.cap;
-    constexpr int Q = RK_TILE / RK_T;
-    for (int64_t t0 = 0; t0 < K; t0 += RK_TILE) {
-        const int m = (int)min<int64_t>(RK_TILE, K - t0);
-        if (tid < RK_SB) tcnt[tid] = 0;
-        __syncthreads();
-        uint32_t jj[Q], rnk[Q];
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int k = tid + q * RK_T;
-            if (k < m) {
-                jj[q] = jbuf[t0 + k];
-                rnk[q] = atomicAdd(&tcnt[(jj[q] >> CHUNK_SHIFT) / spc], 1u);
-            }
-        }
-        __syncthreads();
-        if (tid < 64) {
-            uint32_t v[RK_SB / 64], loc = 0;
-#pragma unroll
-            for (int q = 0; q < RK_SB / 64; ++q) { v[q] = tcnt[tid * (RK_SB / 64) + q]; loc += v[q]; }
-            uint32_t incl = loc;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t u = __shfl_up(incl, o, WAVE);
-                if (tid >= o) incl += u;
-            }
-            uint32_t run = incl - loc;
-#pragma unroll
-            for (int q = 0; q < RK_SB / 64; ++q) {
-                const int b = tid * (RK_SB / 64) + q;
-                toff[b] = run;
-                gbase[b] = cnt[b];
-                cnt[b] += v[q];
-                run += v[q];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int k = tid + q * RK_T;
-            if (k < m) tile[toff[(jj[q] >> CHUNK_SHIFT) / spc] + rnk[q]] = jj[q];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int k = tid + q * RK_T;
-            if (k < m) {
-                const uint32_t j = tile[k];
-                const uint32_t b = (j >> CHUNK_SHIFT) / spc;
-                oi[gbase[b] + (uint32_t)k - toff[b]] = j;
-            }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        ws.thr[row] = 0;
-        ws.flags[row] = F_EXACT;
-        ws.rowcnt[row * RCS] = (uint32_t)K;
-    }
-    if (FINAL) {
-        __syncthreads();                                  // block-scope visibility of the idx writes
-        const float* r = rows.row(row);
-        float* val = ws.ent_val + row * ws.cap;
-        for (int64_t t = tid; t < K; t += RK_T) val[t] = scale * r[oi[t]];   // (D/K) * x[S] in fp32
-    }
-}
-
-// Segments up to RK_FT entries (the device sampler's ~K / RK_SB, far above any binomial tail) are
-// sorted in LDS and written back, with the values, in one coalesced sweep; a larger segment (an
-// arbitrary compat index list) takes the slower in-memory counting sort.
-constexpr int RK_FT = 8192, RK_FTHR = 512;
-__global__ __launch_bounds__(RK_FTHR) void k_randk_fine(RowSrc rows, int64_t n, int64_t d, int64_t K, float scale,
-                                                        SelWs ws) {
-    extern __shared__ uint32_t fc[];                       // [spc] counts, then offsets / cursors
-    __shared__ uint32_t wsum[RK_FTHR / 64];
-    __shared__ uint32_t tile[RK_FT];
-    const int64_t row = blockIdx.y, b = blockIdx.x;
-    const int64_t C = nchunks(d), spc = rk_spc(C);
-    const int64_t cb0 = b * spc, cb1 = min(C, cb0 + spc);
-    const int tid = threadIdx.x;
-    if (cb0 >= C) return;
-    const uint32_t s0 = ws.cursor[row * RK_SB + b];
-    const uint32_t s1 = (b + 1 < RK_SB) ? ws.cursor[row * RK_SB + b + 1] : (uint32_t)K;
-    const int64_t nc = cb1 - cb0;
-    const bool in_lds = s1 - s0 <= (uint32_t)RK_FT;
-    for (int64_t c = tid; c < nc; c += RK_FTHR) fc[c] = 0;
-    __syncthreads();
-    uint32_t* idx = ws.ent_idx + row * ws.cap;
-    uint32_t* tmp = reinterpret_cast<uint32_t*>(ws.ent_val + row * ws.cap);
-    constexpr int Q = RK_FT / RK_FTHR;
-    uint32_t jj[Q], rnk[Q];
-    if (in_lds) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const uint32_t t = s0 + tid + q * RK_FTHR;
-            if (t < s1) {
-                jj[q] = idx[t];
-                rnk[q] = atomicAdd(&fc[(jj[q] >> CHUNK_SHIFT) - cb0], 1u);
-            }
-        }
-    } else {
-        for (uint32_t t = s0 + tid; t < s1; t += RK_FTHR) {
-            const uint32_t j = idx[t];
-            tmp[t] = j;
-            atomicAdd(&fc[(j >> CHUNK_SHIFT) - cb0], 1u);
-        }
-    }
-    __syncthreads();
-    // exclusive scan of nc counters: thread t owns a contiguous block
-    const int64_t per = (nc + RK_FTHR - 1) / RK_FTHR;
-    const int64_t q0 = min<int64_t>(nc, tid * per), q1 = min<int64_t>(nc, q0 + per);
-    uint32_t loc = 0;
-    for (int64_t c = q0; c < q1; ++c) loc += fc[c];
-    uint32_t incl = loc;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(incl, o, WAVE);
-        if ((tid & 63) >= o) incl += u;
-    }
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    uint32_t run = incl - loc;
-    for (int w = 0; w < (tid >> 6); ++w) run += wsum[w];
-    for (int64_t c = q0; c < q1; ++c) {
-        const uint32_t v = fc[c];
-        ws.tab[(cb0 + c) * n + row] = make_uint2(s0 + run, v);
-        fc[c] = run;                                        // segment-relative offset
-        run += v;
-    }
-    __syncthreads();
-    const float* r = rows.row(row);
-    float* val = ws.ent_val + row * ws.cap;
-    if (in_lds) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const uint32_t t = s0 + tid + q * RK_FTHR;
-            if (t < s1) tile[fc[(jj[q] >> CHUNK_SHIFT) - cb0] + rnk[q]] = jj[q];
-        }
-        __syncthreads();
-        for (uint32_t k = tid; k < s1 - s0; k += RK_FTHR) {
-            const uint32_t j = tile[k];
-            idx[s0 + k] = j;
-            val[s0 + k] = scale * r[j];                     // (D/K) * x[S] in fp32, ascending columns
-        }
-        return;
-    }
-    for (uint32_t t = s0 + tid; t < s1; t += RK_FTHR) {
-        const uint32_t j = tmp[t];
-        idx[s0 + atomicAdd(&fc[(j >> CHUNK_SHIFT) - cb0], 1u)] = j;
-    }
-    __syncthreads();                                        // block-scope visibility of the idx writes
-    for (uint32_t t = s0 + tid; t < s1; t += RK_FTHR) val[t] = scale * r[idx[t]];
-}
-
-// ------------------------------------------------------------------------------------------
-// Chunk-owner accumulation.  One wave per chunk, fp32 tile in LDS; rows folded in order.
-// ASSIGN (single row, no weights): out = tile with the entry values stored, not added
-// (keeps -0.0 like torch's out[ind] = x[ind]).
-// ------------------------------------------------------------------------------------------
-// Admission per entry: exact-path rows (F_EXACT) hold exactly their admitted entries; fast-path
-// rows admit key > thr, and key == thr either all (no F_TIES) or up to the row's tie cut (the
-// largest index admitted among the ties, k_cand_select).
-//
-// One wave owns one chunk: a 4096-float LDS tile into which the rows are folded in row order
-// (bit-exact sequential sum; within a row the entries' columns are distinct).  The walk over the
-// N rows is a software pipeline: the per-row state (tab entry, thr, cut, mode, weight) of 64 rows
-// is fetched one batch ahead with lane = row, and the entry lists of the next AP rows are in
-// flight while a row is folded (a ring of AP register slots, 2 x 64 entries per row), so the
-// wave never waits on a dependent tab -> entries round trip.
-// ------------------------------------------------------------------------------------------
-#ifndef FLC_CA_PROBE
-#define FLC_CA_PROBE 0               // A/B cost probe of k_chunk_accum (outputs NOT valid): 1 no tile update
-#endif
-#ifndef FLC_CA_AP1
-#define FLC_CA_AP1 4                 // one-wave fold workgroups: rows in flight (<= 113 VGPRs: beside the TopK filter's 3 waves per SIMD)
-#endif
-#ifndef FLC_CA_WPB1
-#define FLC_CA_WPB1 0                // k_chunk_accum over whole chunks: one-wave workgroups
-#endif
-#ifndef FLC_CA_AP
-#define FLC_CA_AP 8
-#endif
-constexpr int AP = FLC_CA_AP;              // rows of entry lists in flight
-
-struct RowMeta {
-    uint2 te;          // (offset, count) of the row's list in this chunk
-    uint32_t thr, cut, mode;   // cut: tie_pref of the row's tie cut (0 admits every tie)
-    float w;
-};
-
-__device__ inline RowMeta load_meta(const SelWs& ws, int64_t c, int64_t n, int64_t r, const float* w, int64_t rend = -1) {
-    RowMeta m;
-    m.te = make_uint2(0, 0);
-    m.thr = 0; m.cut = 0u; m.mode = 0; m.w = 1.f;
-    if (r < (rend < 0 ? n : rend)) {
-        m.te = ws.tab[c * n + r];
-        m.thr = ws.thr[r];
-        const uint32_t f = ws.flags[r];
-        m.mode = (f & F_EXACT) ? 2u : ((f & F_TIES) ? 1u : 0u);
-        if (m.mode == 1u) m.cut = tie_pref(ws.tiecut[r], ws.tie_hi);
-        if (m.mode == 2u) m.thr = 0u;          // exact list: every entry admitted (key >= 0, cut ~0)
-        if (w) m.w = w[r];
-    }
-    return m;
-}
-
-
-// Sign of zero.  The reference adds every client's DENSE row, so a column a row did not keep
-// receives the term w_i * (+0) (-0 when w_i's sign bit is set).  The fold skips those terms and
-// starts its tile at -0 (the additive identity), which gives the same bits for every nonzero
-// result.  A sum is -0 only if every term was -0: the tile ends at -0 exactly when every KEPT
-// term was -0 (or none was kept), and the reference's sum is then -0 iff, in addition, every row
-// that did not keep the column has a negative-signed weight.  Those columns are resolved here:
-// for each row with a positive-signed weight (stopping once no candidate is left) the -0
-// columns it does not keep turn +0.  Untouched columns die at the first such row, so this costs
-// one extra list walk for chunks that have them and nothing for the others.
-template <int TS>
-__device__ void resolve_neg_zero(float* tl, uint32_t* rm, const SelWs& ws, int64_t c, int64_t n, uint32_t cbase,
-                                 int64_t len, const float* w, int lane) {
-    constexpr int NW = TS / 32;                        // mask words (32 columns each)
-    constexpr int WL = (NW + 63) / 64;                 // mask words per lane (word k = lane + 64 j)
-    bool any = false;
-    for (int k = 0; k < TS / 64; ++k) {
-        const int64_t i = (int64_t)k * 64 + lane;
-        const uint64_t b = __ballot(i < len && __float_as_uint(tl[i]) == 0x80000000u);
-        if (lane == 0) { rm[2 * k] = (uint32_t)b; rm[2 * k + 1] = (uint32_t)(b >> 32); }
-        any |= b != 0ull;
-    }
-    if (!any) return;
-    uint32_t z0[WL], zc[WL];
-#pragma unroll
-    for (int j = 0; j < WL; ++j) {
-        const int k = lane + 64 * j;
-        z0[j] = k < NW ? rm[k] : 0u;
-        zc[j] = z0[j];
-    }
-    for (int64_t r = 0; r < n; ++r) {
-        if (w && (__float_as_uint(w[r]) >> 31)) continue;      // its skipped term is -0: no constraint
-#pragma unroll
-        for (int j = 0; j < WL; ++j) if (lane + 64 * j < NW) rm[lane + 64 * j] = 0u;
-        const RowMeta m = load_meta(ws, c, n, r, w);
-        const uint32_t mode = m.mode, T = m.thr, cut = m.cut;
-        for (uint32_t e = (uint32_t)lane; e < m.te.y; e += 64) {
-            const uint32_t ix = ws.ent_idx[r * ws.cap + m.te.x + e];
-            const uint32_t key = mag_key(ws.ent_val[r * ws.cap + m.te.x + e]);
-            const uint32_t loc = ix - cbase;
-            if (loc < (uint32_t)TS && (mode == 2u || key > T || (key == T && tie_pref(ix, ws.tie_hi) >= cut)))
-                atomicOr(&rm[loc >> 5], 1u << (loc & 31));
-        }
-        bool left = false;
-#pragma unroll
-        for (int j = 0; j < WL; ++j) {
-            if (lane + 64 * j < NW) zc[j] &= rm[lane + 64 * j];
-            left |= zc[j] != 0u;
-        }
-        if (__ballot(left) == 0ull) break;
-    }
-#pragma unroll
-    for (int j = 0; j < WL; ++j) {
-        uint32_t dead = z0[j] & ~zc[j];
-        while (dead) {
-            const int b = __builtin_ctz(dead);
-            dead &= dead - 1u;
-            tl[(lane + 64 * j) * 32 + b] = 0.f;
-        }
-    }
-}
-
-// resolve_neg_zero for one-wave workgroups whose LDS holds only the tile: the -0 column masks
-// live in registers (word k of the tile's TS / 32 in lane k % 64), a row's kept columns are OR-ed
-// into the job's global scratch `rm` (TS / 32 words) and read back at L2 (atomic reads: no stale
-// L1 line).  Same rule, same bits; it runs once per job and usually stops after one row.
-template <int TS>
-__device__ void resolve_neg_zero_g(float* tl, uint32_t* rm, const SelWs& ws, int64_t c, int64_t n, uint32_t cbase,
-                                   int64_t len, const float* w, int lane) {
-    constexpr int NW = TS / 32;                        // mask words (32 columns each)
-    constexpr int WL = (NW + 63) / 64;                 // mask words per lane (word k = lane + 64 j)
-    uint32_t z0[WL], zc[WL];
-#pragma unroll
-    for (int j = 0; j < WL; ++j) z0[j] = 0u;
-    bool any = false;
-#pragma unroll 4
-    for (int k = 0; k < TS / 64; ++k) {
-        const int64_t i = (int64_t)k * 64 + lane;
-        const uint64_t b = __ballot(i < len && __float_as_uint(tl[i]) == 0x80000000u);
-        const int w0 = 2 * k, w1 = 2 * k + 1;          // words of columns 64 k .. 64 k + 63
-#pragma unroll
-        for (int j = 0; j < WL; ++j) {
-            if (lane == (w0 & 63) && (w0 >> 6) == j) z0[j] = (uint32_t)b;
-            if (lane == (w1 & 63) && (w1 >> 6) == j) z0[j] = (uint32_t)(b >> 32);
-        }
-        any |= b != 0ull;
-    }
-    if (!any) return;
-#pragma unroll
-    for (int j = 0; j < WL; ++j) zc[j] = z0[j];
-    for (int64_t r = 0; r < n; ++r) {
-        if (w && (__float_as_uint(w[r]) >> 31)) continue;      // its skipped term is -0: no constraint
-#pragma unroll
-        for (int j = 0; j < WL; ++j) if (lane + 64 * j < NW) rm[lane + 64 * j] = 0u;
-        __threadfence_block();
-        const RowMeta m = load_meta(ws, c, n, r, w);
-        const uint32_t mode = m.mode, T = m.thr, cut = m.cut;
-        for (uint32_t e = (uint32_t)lane; e < m.te.y; e += 64) {
-            const uint32_t ix = ws.ent_idx[r * ws.cap + m.te.x + e];
-            const uint32_t key = mag_key(ws.ent_val[r * ws.cap + m.te.x + e]);
-            const uint32_t loc = ix - cbase;
-            if (loc < (uint32_t)TS && (mode == 2u || key > T || (key == T && tie_pref(ix, ws.tie_hi) >= cut)))
-                atomicOr(&rm[loc >> 5], 1u << (loc & 31));
-        }
-        __threadfence_block();
-        bool left = false;
-#pragma unroll
-        for (int j = 0; j < WL; ++j) {
-            if (lane + 64 * j < NW) zc[j] &= atomicOr(&rm[lane + 64 * j], 0u);
-            left |= zc[j] != 0u;
-        }
-        if (__ballot(left) == 0ull) break;
-    }
-#pragma unroll
-    for (int j = 0; j < WL; ++j) {
-        uint32_t dead = z0[j] & ~zc[j];
-        while (dead) {
-            const int b = __builtin_ctz(dead);
-            dead &= dead - 1u;
-            tl[(lane + 64 * j) * 32 + b] = 0.f;
-        }
-    }
-}
-
-// TS < CHUNK: a wave owns TS columns of a chunk (CHUNK / TS waves read the same lists and each
-// folds its part): a smaller LDS tile per wave, so more waves per CU hide the list latency.
-// WPB = 1 (whole chunks): one-wave workgroups holding only their 16 KB tile, so ten fit a CU's
-// 160 KB and every chunk of a 10 M row (2442) has its wave resident at once — with 4-wave blocks
-// (67.5 KB with the masks) two fit a CU, 2048 chunk waves ran and the last 394 formed a second
-// round of the same length.
-// Row groups: rows [r0, rend) only; `first` starts the tiles at -0, else from ws.part (the previous
-// group's tiles); `last` resolves the -0 columns over ALL n rows and writes out = sums / wt, else
-// the tiles go back to ws.part.  (r0 = 0, rend = n, first = last = 1: one fold of every row.)
-template <bool ASSIGN, int TS, bool W, int WPB, int AP = AP>
-__device__ __forceinline__ void chunk_accum_body(int64_t n, int64_t d, SelWs ws, const float* __restrict__ w, float wt,
-                                                 float* __restrict__ out, int64_t r0, int64_t rend, int first, int last,
-                                                 float (*tile)[TS], uint32_t (*zmask)[WPB == 1 ? 1 : TS / 32]) {
-    if (rend < 0) rend = n;
-    constexpr int PARTS = CHUNK / TS;
-    const int lane = threadIdx.x & 63;
-    const int wv = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t C = nchunks(d);
-    float* tl = tile[wv];
-    const int64_t nb = (rend - r0 + 63) / 64;          // row batches
-    for (int64_t t = (int64_t)blockIdx.x * WPB + wv; t < C * PARTS; t += (int64_t)gridDim.x * WPB) {
-        const int64_t c = t / PARTS;
-        const uint32_t cbase = (uint32_t)(c * CHUNK + (t % PARTS) * TS);
-        // ASSIGN (compressVector: out = zeros, out[kept] = x) stores into +0; the fold adds into -0
-        if (FLC_TILE_V4 && !ASSIGN && !first && (int64_t)cbase + TS <= d) {
-            // the carried tile with its loads in flight 8 float4 at a time (the loop of load -> LDS
-            // write pairs below waits one memory latency per 64 columns: 64 per 4096-column tile)
-            const float4* p4 = reinterpret_cast<const float4*>(ws.part + cbase);
-#pragma unroll
-            for (int k0 = 0; k0 < TS / 256; k0 += 8) {
-                float4 v[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] = k0 + k < TS / 256 ? p4[(k0 + k) * 64 + lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k0 + k < TS / 256) reinterpret_cast<float4*>(tl)[(k0 + k) * 64 + lane] = v[k];
-            }
-        } else {
-            for (int i = lane; i < TS; i += 64)
-                tl[i] = ASSIGN ? 0.f : (first || (int64_t)cbase + i >= d ? -0.f : ws.part[cbase + i]);
-        }
-        RowMeta cur = load_meta(ws, c, n, r0 + lane, w, rend), nxt;
-        // ring of AP rows' entries (the first 128 of each list; range-checked buffer loads, lanes
-        // past the list end get index ~0 = no column)
-        uint32_t ri[AP][2];
-        float rv[AP][2];
-        auto fetch = [&](const RowMeta& m, int q, int64_t row, int slot) {
-            const uint32_t off = __builtin_amdgcn_readlane(m.te.x, q), cnt = __builtin_amdgcn_readlane(m.te.y, q);
-            const auto di = list_rsrc(ws.ent_idx + row * ws.cap + off, cnt);
-            const auto dv = list_rsrc(ws.ent_val + row * ws.cap + off, cnt);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t e = (uint32_t)lane + 64u * h;
-                const uint32_t x = __builtin_amdgcn_raw_buffer_load_b32(di, lane * 4, h * 256, 0);
-                ri[slot][h] = e < cnt ? x : 0xFFFFFFFFu;
-                rv[slot][h] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(dv, lane * 4, h * 256, 0));
-            }
-        };
-        // admission (key > T, or key == T and tie_pref(ix) >= tie_pref(cut); load_meta folds the
-        // exact mode into T = 0, cut 0) as ONE 64-bit compare: (key, tie_pref(ix)) >= (T, cut)
-        const uint32_t txm = ws.tie_hi ? 0u : 0xFFFFFFFFu;   // tie_pref(ix) = ix ^ txm
-        auto fold = [&](uint32_t ix, float vv, uint32_t T, uint32_t cut, uint32_t mode, float wi) {
-            (void)mode;
-            const uint32_t loc = ix - cbase;                   // ~0 index / other part: loc >= TS
-            const uint64_t a = ((uint64_t)mag_key(vv) << 32) | (uint64_t)(ix ^ txm);
-            const uint64_t b = ((uint64_t)T << 32) | (uint64_t)cut;
-            if (FLC_CA_PROBE == 1) {                          // cost probe: no tile update
-                if (loc < (uint32_t)TS && a >= b && vv == 1.2345f) tl[0] = vv;
-                return;
-            }
-            if (loc < (uint32_t)TS && a >= b) {
-                if (ASSIGN) tl[loc] = vv;
-                else tl[loc] = W ? tl[loc] + wi * vv : tl[loc] + vv;
-            }
-        };
-#pragma unroll
-        for (int q = 0; q < AP; ++q) fetch(cur, q, r0 + q, q);
-        for (int64_t b = 0; b < nb; ++b) {
-            const int64_t i0 = r0 + b * 64;
-            nxt = load_meta(ws, c, n, i0 + 64 + lane, w, rend);   // next batch's state, one batch ahead
-            if (__builtin_expect(__ballot(cur.te.y > 128u) == 0ull, 1)) {
-                // every list of the batch fits the ring slots: straight-line pipeline
-#pragma unroll
-                for (int q = 0; q < 64; ++q) {
-                    const int slot = q % AP;
-                    const uint32_t T = __builtin_amdgcn_readlane(cur.thr, q);
-                    const uint32_t cut = __builtin_amdgcn_readlane(cur.cut, q);
-                    const uint32_t mode = 0u;
-                    const float wi = W ? __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(cur.w), q)) : 1.f;
-                    fold(ri[slot][0], rv[slot][0], T, cut, mode, wi);
-                    // the second slot holds entries only when the list is longer than 64
-                    if (__builtin_amdgcn_readlane(cur.te.y, q) > 64u) fold(ri[slot][1], rv[slot][1], T, cut, mode, wi);
-                    if (q + AP < 64) fetch(cur, q + AP, i0 + q + AP, slot);
-                    else fetch(nxt, q + AP - 64, i0 + q + AP, slot);   // past n: empty lists
-                }
-            } else {
-                // some list is longer than 128 entries: the same walk with the tails folded in place
-                for (int q = 0; q < 64; ++q) {
-                    const int slot = q % AP;
-                    const uint32_t T = __shfl(cur.thr, q, WAVE), cut = __shfl(cur.cut, q, WAVE);
-                    const uint32_t mode = __shfl(cur.mode, q, WAVE), cnt = __shfl(cur.te.y, q, WAVE);
-                    const uint32_t off = __shfl(cur.te.x, q, WAVE);
-                    const float wi = W ? __shfl(cur.w, q, WAVE) : 1.f;
-                    uint32_t i_0 = 0, i_1 = 0;
-                    float v_0 = 0.f, v_1 = 0.f;
-#pragma unroll
-                    for (int z = 0; z < AP; ++z)
-                        if (z == slot) { i_0 = ri[z][0]; i_1 = ri[z][1]; v_0 = rv[z][0]; v_1 = rv[z][1]; }
-                    fold(i_0, v_0, T, cut, mode, wi);
-                    fold(i_1, v_1, T, cut, mode, wi);
-                    const int64_t row = i0 + q;
-                    for (uint32_t e = 128u + lane; e < cnt; e += 64)
-                        fold(ws.ent_idx[row * ws.cap + off + e], ws.ent_val[row * ws.cap + off + e], T, cut, mode, wi);
-                    // refill the slot (same contract as the straight-line path)
-                    const RowMeta& m = (q + AP < 64) ? cur : nxt;
-                    const int qq = (q + AP) & 63;
-                    const uint32_t offn = __shfl(m.te.x, qq, WAVE), cntn = __shfl(m.te.y, qq, WAVE);
-                    const int64_t rown = i0 + q + AP;
-                    uint32_t xi[2];
-                    float xv[2];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const uint32_t e = (uint32_t)lane + 64u * h;
-                        xi[h] = e < cntn ? ws.ent_idx[rown * ws.cap + offn + e] : 0xFFFFFFFFu;
-                        xv[h] = e < cntn ? ws.ent_val[rown * ws.cap + offn + e] : 0.f;
-                    }
-#pragma unroll
-                    for (int z = 0; z < AP; ++z)
-                        if (z == slot) { ri[z][0] = xi[0]; ri[z][1] = xi[1]; rv[z][0] = xv[0]; rv[z][1] = xv[1]; }
-                }
-            }
-            cur = nxt;
-        }
-        const int64_t len = min((int64_t)TS, d - (int64_t)cbase);
-        if (!last) {                                   // row groups: the tiles carry on to the next group
-            for (int64_t i = lane; i < len; i += 64) ws.part[cbase + i] = tl[i];
-            continue;
-        }
-        if (!ASSIGN) {
-            if (WPB == 1) resolve_neg_zero_g<TS>(tl, ws.zm + t * (TS / 32), ws, c, n, cbase, len, w, lane);
-            else resolve_neg_zero<TS>(tl, zmask[wv], ws, c, n, cbase, len, w, lane);
-        }
-        for (int64_t i = lane; i < len; i += 64) out[cbase + i] = ASSIGN ? tl[i] : tl[i] / wt;
-    }
-}
-
-template <bool ASSIGN, int TS = CHUNK, bool W = true>
-__global__ __launch_bounds__(256) void k_chunk_accum(int64_t n, int64_t d, SelWs ws, const float* __restrict__ w, float wt,
-                                                     float* __restrict__ out, int64_t r0 = 0, int64_t rend = -1,
-                                                     int first = 1, int last = 1) {
-    __shared__ __attribute__((aligned(16))) float tile[4][TS];
-    __shared__ uint32_t zmask[4][TS / 32];
-    chunk_accum_body<ASSIGN, TS, W, 4>(n, d, ws, w, wt, out, r0, rend, first, last, tile, zmask);
-}
-
-// one-wave workgroups holding only their tile (16 KB) and at most FLC_CA_VGPR1 VGPRs: they fit in
-// what the TopK filter's waves leave free on a CU (row-group folds under the next group's filter)
-// (the tile is dynamic LDS, CHUNK floats given at launch: with a static 16 KB array the compiler
-// takes LDS as the occupancy limit and ignores the waves-per-EU request)
-template <bool W>
-__global__ __launch_bounds__(64) void k_chunk_accum1(
-        int64_t n, int64_t d, SelWs ws, const float* __restrict__ w, float wt, float* __restrict__ out, int64_t r0,
-        int64_t rend, int first, int last) {
-    extern __shared__ __attribute__((aligned(16))) float dyn_tile[];
-    chunk_accum_body<false, CHUNK, W, 1, FLC_CA_AP1>(n, d, ws, w, wt, out, r0, rend, first, last,
-                                         reinterpret_cast<float (*)[CHUNK]>(dyn_tile), nullptr);
-}
-
-// ------------------------------------------------------------------------------------------
-// RandK device mode (randk_tree.hpp): no index lists.
-//   k_randk_counts : one workgroup per row walks the hypergeometric tree level by level (ping-pong
-//                    level arrays in the workspace) -> cnt[c][row] = the row's members in chunk c,
-//                    and the row's client key
-//   k_randk_fold   : one wave per chunk (or 1/2, 1/4 of its columns when the rows are short) folds
-//                    the rows in order into an fp32 LDS tile: row q's members of the chunk are the
-//                    first cnt[c][q] images of the chunk permutation (lane t -> offset P(t)), their
-//                    values (D/K) * x_q[j] gathered with range-checked buffer loads (AP rows in
-//                    flight), added as w_q * v — the sequential fold of the dense compressVector
-//                    outputs, bit for bit (a row's members are distinct)
-// ------------------------------------------------------------------------------------------
-struct RkdWs {
-    uint32_t* cnt;     // [C][N]
-    uint64_t* ckey;    // [N]
-};
-
-// Chunk counts of the device sampler (randk_tree.hpp): each workgroup takes one row and a range of
-// RKC_BINS chunks, evaluates Pi(t) for all t < K with a persistent cycle walk (every lane does
-// useful work each trip) and histograms the chunk ids in LDS (16-bit bins: a chunk holds <= 4096).
-constexpr int RKC_NT = 1024;
-constexpr int64_t RKC_BINS = 32768;
-
-// the client keys of the device sampler (k_randk_counts writes them beside the counts)
-__global__ __launch_bounds__(256) void k_randk_ckeys(int64_t n, uint64_t seed, int64_t client0, uint64_t* __restrict__ ckey) {
-    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (row < n) ckey[row] = client_key(seed, client0 + row);
-}
-
-__global__ __launch_bounds__(RKC_NT) void k_randk_counts(int64_t n, int64_t d, int64_t K, uint64_t seed, int64_t client0,
-                                                         RkdWs ws) {
-    __shared__ uint32_t bins[RKC_BINS / 2];
-    const int64_t row = blockIdx.y;
-    const int tid = threadIdx.x;
-    const int64_t C = nchunks(d);
-    const int64_t c0 = (int64_t)blockIdx.x * RKC_BINS, nc = min(C, c0 + RKC_BINS) - c0;
-    const uint64_t ck = client_key(seed, client0 + row);
-    for (int64_t i = tid; i < (nc + 1) / 2; i += RKC_NT) bins[i] = 0;
-    __syncthreads();
-    const rktree::RowPerm P(ck, (uint64_t)d);
-    int64_t t = tid;
-    bool live = t < K;
-    uint64_t x = (uint64_t)t;
-    while (__ballot(live) != 0ull) {
-        const uint64_t v = P.once(x);
-        if (live) {
-            if (v < (uint64_t)d) {
-                const int64_t c = (int64_t)(v >> CHUNK_SHIFT) - c0;
-                if ((uint64_t)c < (uint64_t)nc) atomicAdd(&bins[c >> 1], 1u << (16 * (c & 1)));
-                t += RKC_NT;
-                live = t < K;
-                x = (uint64_t)t;
-            } else {
-                x = v;
-            }
-        }
-    }
-    __syncthreads();
-    if (blockIdx.x == 0 && tid == 0) ws.ckey[row] = ck;
-    for (int64_t c = tid; c < nc; c += RKC_NT) ws.cnt[(c0 + c) * n + row] = (bins[c >> 1] >> (16 * (c & 1))) & 0xFFFFu;
-}
-
-// lists view of the counts (the short-row path): tab[c][row] = (offset, count) with the members
-// laid out chunk by chunk, and the F_EXACT row state (every listed entry is kept)
-__global__ __launch_bounds__(256) void k_randk_tab(int64_t n, int64_t d, int64_t K, const uint32_t* __restrict__ cnt,
-                                                   SelWs ls) {
-    __shared__ uint32_t part[256];
-    const int64_t row = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int64_t C = nchunks(d), per = (C + 255) / 256;
-    const int64_t c0 = min(C, tid * per), c1 = min(C, c0 + per);
-    uint32_t loc = 0;
-    for (int64_t c = c0; c < c1; ++c) loc += cnt[c * n + row];
-    part[tid] = loc;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const uint32_t v = tid >= off ? part[tid - off] : 0u;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] - loc;
-    for (int64_t c = c0; c < c1; ++c) {
-        const uint32_t m = cnt[c * n + row];
-        ls.tab[c * n + row] = make_uint2(run, m);
-        run += m;
-    }
-    if (tid == 0) {
-        ls.thr[row] = 0;
-        ls.flags[row] = F_EXACT;
-        ls.rowcnt[row * RCS] = (uint32_t)K;
-    }
-}
-
-// Row-major member generation + gather: each wave takes RKG_CPW consecutive chunks of one row,
-// lane t < m_c writes member t of chunk c (its global index and (D/K) x[j]) at the row's list
-// position tab[c][row].x + t — the lists k_chunk_accum folds.  The gathers of a wave stay inside one
-// row's 16 KB windows, chunk after chunk (page- and DRAM-row-local, like the compat path's
-// k_randk_fine); the RKG_CPW chunks' loads are issued before any store.
-constexpr int RKG_CPW = 4;
-__global__ __launch_bounds__(256) void k_randk_gen(RowSrc rows, int64_t n, int64_t d, const uint64_t* __restrict__ ckey,
-                                                   float scale, SelWs ws) {
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t C = nchunks(d);
-    for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
-        const uint64_t k = ckey[row];
-        const float* r = rows.row_s(row);
-        uint32_t* oi = ws.ent_idx + row * ws.cap;
-        float* ov = ws.ent_val + row * ws.cap;
-        for (int64_t c0 = ((int64_t)blockIdx.x * 4 + wv) * RKG_CPW; c0 < C; c0 += (int64_t)gridDim.x * 4 * RKG_CPW) {
-            uint2 te[RKG_CPW];
-            uint32_t col[RKG_CPW];
-            float v[RKG_CPW];
-#pragma unroll
-            for (int q = 0; q < RKG_CPW; ++q) {
-                const int64_t c = c0 + q;
-                te[q] = c < C ? ws.tab[c * n + row] : make_uint2(0u, 0u);
-                const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - c * CHUNK);
-                const rktree::ChunkPerm P(k, c, clen);
-                col[q] = (uint32_t)lane < te[q].y ? P((uint32_t)lane) : 0u;
-                v[q] = (uint32_t)lane < te[q].y ? r[c * CHUNK + col[q]] : 0.f;
-            }
-#pragma unroll
-            for (int q = 0; q < RKG_CPW; ++q) {
-                const int64_t c = c0 + q;
-                if ((uint32_t)lane < te[q].y) {
-                    oi[te[q].x + lane] = (uint32_t)(c * CHUNK + col[q]);
-                    ov[te[q].x + lane] = scale * v[q];
-                }
-                if (te[q].y > 64u) {                      // a chunk with more than 64 members
-                    const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - c * CHUNK);
-                    const rktree::ChunkPerm P(k, c, clen);
-                    for (uint32_t t = 64u + lane; t < te[q].y; t += 64) {
-                        const uint32_t cc = P(t);
-                        oi[te[q].x + t] = (uint32_t)(c * CHUNK + cc);
-                        ov[te[q].x + t] = scale * r[c * CHUNK + cc];
-                    }
-                }
-            }
-        }
-    }
-}
-
-__device__ inline uint64_t join64(uint32_t hi, uint32_t lo) { return ((uint64_t)hi << 32) | (uint64_t)lo; }
-
-struct RkMeta {            // lane = row of a 64-row batch
-    uint32_t m;            // members of this chunk
-    uint32_t klo, khi;     // client key
-    uint32_t plo, phi;     // row pointer
-    float w;
-};
-
-__device__ inline RkMeta rk_meta(RowSrc rows, const uint32_t* cnt, const uint64_t* ckey, const float* w, int64_t c,
-                                 int64_t n, int64_t r, uint32_t clen) {
-    RkMeta m{0u, 0u, 0u, 0u, 0u, 1.f};
-    if (r < n) {
-        m.m = min(cnt[c * n + r], clen);                 // <= clen by construction; never index past it
-        const uint64_t k = ckey[r];
-        m.klo = (uint32_t)k;
-        m.khi = (uint32_t)(k >> 32);
-        const uintptr_t p = (uintptr_t)rows.row(r);
-        m.plo = (uint32_t)p;
-        m.phi = (uint32_t)((uint64_t)p >> 32);
-        if (w) m.w = w[r];
-    }
-    return m;
-}
-
-// (rk_resolve_neg_zero, the -0 column rule after the fold: randk_tree.hpp, shared with randk_shift.hip)
-
-#ifndef FLC_RK_AP
-#define FLC_RK_AP 8
-#endif
-constexpr int RK_AP = FLC_RK_AP;
-template <int TS>
-__global__ __launch_bounds__(256) void k_randk_fold(RowSrc rows, int64_t n, int64_t d, const uint32_t* __restrict__ cnt,
-                                                    const uint64_t* __restrict__ ckey, float scale,
-                                                    const float* __restrict__ w, float wt, float* __restrict__ out) {
-    constexpr int PARTS = CHUNK / TS;
-    constexpr uint32_t NOCOL = 0xFFFFu;                    // past the chunk: the buffer load returns 0
-    __shared__ __attribute__((aligned(16))) float tile[4][TS];
-    __shared__ uint32_t zmask[4][TS / 32];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t C = nchunks(d);
-    float* tl = tile[wv];
-    const int64_t nb = (n + 63) / 64;
-    for (int64_t t = (int64_t)blockIdx.x * 4 + wv; t < C * PARTS; t += (int64_t)gridDim.x * 4) {
-        const int64_t c = t / PARTS;
-        const uint32_t pbase = (uint32_t)((t % PARTS) * TS);
-        const int64_t cbase = c * CHUNK;
-        const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - cbase);
-        for (int i = lane; i < TS; i += 64) tl[i] = -0.f;     // the additive identity
-        constexpr int AP = RK_AP;                             // rows in flight (their gathers)
-        uint32_t ro[AP];                                      // ring: part-local column (>= TS: none)
-        float rv[AP];                                         //       gathered x
-        // row q of the current batch: its members' columns for this lane, one gather in flight
-        auto fetch = [&](const RkMeta& mt, int q, int slot) {
-            const uint32_t m = __builtin_amdgcn_readlane(mt.m, q);
-            // readlane returns int: widen through uint32_t (a sign-extended low word would set the high one)
-            const uint64_t k = join64((uint32_t)__builtin_amdgcn_readlane(mt.khi, q), (uint32_t)__builtin_amdgcn_readlane(mt.klo, q));
-            const float* rp = (const float*)join64((uint32_t)__builtin_amdgcn_readlane(mt.phi, q),
-                                                   (uint32_t)__builtin_amdgcn_readlane(mt.plo, q));
-            const rktree::ChunkPerm P(k, c, clen);
-            uint32_t col = (uint32_t)lane < m ? P((uint32_t)lane) : NOCOL;
-            if (PARTS > 1 && col - pbase >= (uint32_t)TS) col = NOCOL;   // another wave's part: no gather
-            const auto rs = chunk_rsrc(rp ? rp : rows.base, cbase, d);
-            ro[slot] = col - pbase;
-            rv[slot] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)(col * 4u), 0, 0));
-        };
-        auto fold = [&](int slot, float wi) {
-            const uint32_t loc = ro[slot];
-            if (loc < (uint32_t)TS) tl[loc] = tl[loc] + wi * (scale * rv[slot]);
-        };
-        RkMeta cur = rk_meta(rows, cnt, ckey, w, c, n, lane, clen), nxt;
-#pragma unroll
-        for (int q = 0; q < AP; ++q) fetch(cur, q, q);
-        for (int64_t b = 0; b < nb; ++b) {
-            const int64_t i0 = b * 64;
-            nxt = rk_meta(rows, cnt, ckey, w, c, n, i0 + 64 + lane, clen);
-            if (__builtin_expect(__ballot(cur.m > 64u) == 0ull, 1)) {
-#pragma unroll
-                for (int q = 0; q < 64; ++q) {
-                    const int slot = q % AP;
-                    fold(slot, __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(cur.w), q)));
-                    if (q + AP < 64) fetch(cur, q + AP, slot);
-                    else fetch(nxt, q + AP - 64, slot);
-                }
-            } else {
-                // a row with more than 64 members here: the same walk with its tail folded in place
-                for (int q = 0; q < 64; ++q) {
-                    const int slot = q % AP;
-                    const float wi = __shfl(cur.w, q, WAVE);
-                    uint32_t lo = NOCOL;
-                    float vv = 0.f;
-#pragma unroll
-                    for (int z = 0; z < AP; ++z)
-                        if (z == slot) { lo = ro[z]; vv = rv[z]; }
-                    if (lo < (uint32_t)TS) tl[lo] = tl[lo] + wi * (scale * vv);
-                    const uint32_t m = __shfl(cur.m, q, WAVE);
-                    if (m > 64u) {
-                        const int64_t row = i0 + q;
-                        const rktree::ChunkPerm P(ckey[row], c, clen);
-                        const float* rp = rows.row(row);
-                        for (uint32_t e = 64u + lane; e < m; e += 64) {
-                            const uint32_t col = P(e), l2 = col - pbase;
-                            if (l2 < (uint32_t)TS) tl[l2] = tl[l2] + wi * (scale * rp[cbase + col]);
-                        }
-                    }
-                    // refill the slot (same contract as the straight-line path)
-                    const RkMeta& mt = (q + AP < 64) ? cur : nxt;
-                    const int qq = (q + AP) & 63;
-                    const uint32_t mn = __shfl(mt.m, qq, WAVE);
-                    const uint64_t kn = join64((uint32_t)__shfl(mt.khi, qq, WAVE), (uint32_t)__shfl(mt.klo, qq, WAVE));
-                    const float* rpn = (const float*)join64((uint32_t)__shfl(mt.phi, qq, WAVE), (uint32_t)__shfl(mt.plo, qq, WAVE));
-                    const rktree::ChunkPerm Pn(kn, c, clen);
-                    const uint32_t col = (uint32_t)lane < mn ? Pn((uint32_t)lane) : NOCOL;
-                    const float xv = col < clen ? rpn[cbase + col] : 0.f;
-#pragma unroll
-                    for (int z = 0; z < AP; ++z)
-                        if (z == slot) { ro[z] = col - pbase; rv[z] = xv; }
-                }
-            }
-            cur = nxt;
-        }
-        const int64_t len = min((int64_t)TS, (int64_t)clen - (int64_t)pbase);
-        rk_resolve_neg_zero<TS>(tl, zmask[wv], cnt, ckey, c, n, pbase, clen, len, w, lane);
-        for (int64_t i = lane; i < len; i += 64) out[cbase + pbase + i] = tl[i] / wt;
-    }
-}
-
-// Single row (compressVector): out = 0, then each wave writes the members of its chunks
-__global__ __launch_bounds__(256) void k_randk_scatter_dev(const float* __restrict__ x, int64_t d, const uint32_t* cnt,
-                                                           const uint64_t* ckey, float scale, float* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t C = nchunks(d);
-    const uint64_t k = ckey[0];
-    for (int64_t c = ((int64_t)blockIdx.x * 256 + threadIdx.x) / 64; c < C; c += (int64_t)gridDim.x * 4) {
-        const int64_t cbase = c * CHUNK;
-        const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - cbase);
-        const rktree::ChunkPerm P(k, c, clen);
-        const uint32_t m = min(cnt[c], clen);
-        for (uint32_t t = (uint32_t)lane; t < m; t += 64) {
-            const int64_t j = cbase + P(t);
-            out[j] = scale * x[j];
-        }
-    }
-}
-
-// Single-row dense output (compressVector: out = zeros; out[admitted] = x, stored not added, so a
-// selected -0.0 stays -0.0 like torch's out[ind] = x[ind]): after a memset, the row's list
-// (entries [0, rowcnt), distinct indices) is scattered with the fold's admission rule — no per-chunk
-// tile walk for one row.
-__global__ __launch_bounds__(256) void k_assign_scatter(SelWs ws, float* __restrict__ out, int sharded) {
-    const uint32_t T = ws.thr[0], f = ws.flags[0];
-    const uint32_t mode = (f & F_EXACT) ? 2u : ((f & F_TIES) ? 1u : 0u);
-    const uint32_t cut = mode == 1u ? tie_pref(ws.tiecut[0], ws.tie_hi) : 0u;
-    // the list: [0, rowcnt) (one reservation counter, or rewritten by the exact path), else the
-    // filter's CS_SH shards, block b taking shards b, b + gridDim.x, ...
-    const bool shd = sharded && mode != 2u;
-    const int64_t segcap = (ws.cap / CS_SH) & ~int64_t(3);
-    for (int sh = shd ? (int)blockIdx.x : 0; sh < (shd ? CS_SH : 1); sh += shd ? (int)gridDim.x : 1) {
-        const uint32_t cnt = shd ? ws.shcnt[sh * RCS] : ws.rowcnt[0];
-        const int64_t o = shd ? sh * segcap : 0;
-        for (uint32_t e = (shd ? 0u : blockIdx.x * 256u) + threadIdx.x; e < cnt; e += shd ? 256u : gridDim.x * 256u) {
-            const uint32_t ix = ws.ent_idx[o + e];
-            const float v = ws.ent_val[o + e];
-            const uint32_t key = mag_key(v);
-            if (mode == 2u || key > T || (key == T && tie_pref(ix, ws.tie_hi) >= cut)) out[ix] = v;
-        }
-    }
-}
-
 // A lone compressVector row on the fast path (its output zeroed by the filter): the exact fallback and
 // the scatter in ONE launch.  A failed row (overflow / short list / ambiguous ties) is selected
 // exactly by workgroup 0, which then scatters the rewritten list alone; otherwise every workgroup
@@ -2631,9 +1394,6 @@ __global__ __launch_bounds__(EX_NT) void k_assign_finish(RowSrc rows, int64_t d,
 // its repair.
 // ------------------------------------------------------------------------------------------
 constexpr int RS_NT = 1024;
-#ifndef FLC_RS_SPIN
-#define FLC_RS_SPIN 10000000ull          // 0.1 s of the 100 MHz clock
-#endif
 
 struct RsTree {
     uint32_t* ctl;
@@ -2830,9 +1590,6 @@ __device__ inline void rs_repair(const float* x, uint32_t d, uint32_t K, uint32_
 }
 
 #ifdef FLC_RS_PRINT                       // probe builds: phase stamps of workgroup 0 (printf)
-#ifndef FLC_RS_TLK
-#define FLC_RS_TLK 0, 4, 1, 2, 3, 10, 12   // the 7 stamps the timeline reports (13: the merger flag)
-#endif
 #define RS_STAMP(i) do { if (threadIdx.x == 0) stamp[i] = (uint64_t)wall_clock64(); } while (0)
 #else
 #define RS_STAMP(i) do { } while (0)
@@ -3632,8 +2389,6 @@ done:;
 // ------------------------------------------------------------------------------------------
 // Host orchestration
 // ------------------------------------------------------------------------------------------
-static int64_t host_chunks(int64_t d) { return (d + CHUNK - 1) / CHUNK; }
-
 int64_t sel_capacity(int codec, int64_t d, int64_t K) {
     if (codec == FLC_RANDK) return std::max<int64_t>(K, 1);
     // candidates of the fast path (~K (1 + 4/sqrt(ks))) with margin; the exact path needs K + CHUNK
@@ -3642,7 +2397,7 @@ int64_t sel_capacity(int codec, int64_t d, int64_t K) {
     return (cap + 3) & ~int64_t(3);        // rows of the candidate lists start 16 B aligned
 }
 
-static SelWs carve_sel(void* base, int codec, int64_t n, int64_t d, int64_t K, size_t* bytes) {
+SelWs carve_sel(void* base, int codec, int64_t n, int64_t d, int64_t K, size_t* bytes) {
     Carver cv(base);
     const int64_t C = std::max<int64_t>(host_chunks(d), 1), nn = std::max<int64_t>(n, 1);
     SelWs s;
@@ -3683,8 +2438,6 @@ static SelWs carve_sel(void* base, int codec, int64_t n, int64_t d, int64_t K, s
     return s;
 }
 
-size_t randk_device_workspace(int64_t n, int64_t d);
-
 size_t sel_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
     size_t b = 0;
     carve_sel(nullptr, prm->codec, n, d, prm->k, &b);
@@ -3692,20 +2445,6 @@ size_t sel_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
     // draws use the same lists plus the count tree
     if (prm->codec == FLC_RANDK) b += randk_device_workspace(n, d);
     return b;
-}
-
-static int grid_stride_blocks(int64_t items, int64_t cap = 4096) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>(items, cap));
-}
-
-// Runs the TopK / RandK pipeline for n rows and writes out (ASSIGN: n == 1 dense encode).
-static int accum_parts() {
-    static const int p = [] {
-        const char* e = tuning_env("FLC_ACCUM_PARTS");   // tuning runs only (0 / unset: by chunk count)
-        const int v = e ? atoi(e) : 0;
-        return (v == 1 || v == 2 || v == 4) ? v : 0;
-    }();
-    return p;
 }
 
 static bool assign_fold() {          // tuning runs: FLC_ASSIGN_FOLD=1 writes a lone row's output chunk by chunk
@@ -3718,15 +2457,6 @@ static bool cs_single() {            // tuning runs: FLC_CS_SINGLE=1 keeps the o
     return v;
 }
 
-#ifndef FLC_LONE_PATH
-#define FLC_LONE_PATH 2                // a lone compressVector row: 2 in registers (k_lone_resident, rows up to
-#endif                                 // RS_U * 4096 per CU; longer: the list path), 0 the list path
-#ifndef FLC_RS_EVREC
-#define FLC_RS_EVREC 1                 // the completion event recorded after every resident launch (0: at a stream switch)
-#endif
-#ifndef FLC_RS_COOP
-#define FLC_RS_COOP 0                  // 1: k_lone_resident launched cooperatively (HIP's launch: +22 us a call
-#endif                                 // measured; residency holds anyway: G <= CUs, one workgroup per CU, launches serialised)
 // k_lone_resident's control block (library-owned, one per device, zeroed once: the kernel leaves it
 // clean) and the serialisation of its launches: two resident grids at once could each hold part of
 // the chip and wait for the other forever, so a launch on another stream than the previous one
@@ -3814,25 +2544,6 @@ static void launch_filter(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_
                            std::min(rb, std::max<int64_t>(rn, 1)), d, ws, shards, (float*)nullptr);
 }
 
-#ifndef FLC_TK_SPLIT_SAMPLE
-#define FLC_TK_SPLIT_SAMPLE 1         // TopK row groups: only group 0's sample before the first filter
-#endif
-#ifndef FLC_TK_LASTPCT
-#define FLC_TK_LASTPCT 100            // size of the last TopK row group in % of the others (its tail is exposed)
-#endif
-static_assert(FLC_TK_LASTPCT >= 1 && FLC_TK_LASTPCT <= 100, "FLC_TK_LASTPCT: the last row group is 1..100 % of the others");
-#ifndef FLC_TK_LAST_TS
-#define FLC_TK_LAST_TS 4096           // the exposed last group fold's tile (columns per wave)
-#endif
-#ifndef FLC_TK_GFOLD
-#define FLC_TK_GFOLD 1                // many-row TopK: fold each row group under the next group's filter
-#endif
-#ifndef FLC_TK_SIDE_NT
-#define FLC_TK_SIDE_NT 512            // threads of the side-stream candidate selects (256 or 512)
-#endif
-#ifndef FLC_TK_EXACT_WG
-#define FLC_TK_EXACT_WG 256           // workgroups of the one exact-rows launch (one per CU)
-#endif
 // Row groups of the TopK fast path whose candidate select + exact fallback run on a side stream
 // under the next group's filter (one fold of all rows at the end), at least 64 rows each: 4
 // (measured at C3, same box, two runs each: 8.18 ms / step with 1 group, 8.15 with 2, 8.00-8.01
@@ -3854,210 +2565,282 @@ std::mutex g_tk_mu;
 std::map<int, TkCtx> g_tk_ctx;
 }  // namespace
 
-static int launch_chunk_accum(int64_t n, int64_t d, SelWs ws, bool assign, const float* w, float wt, float* out,
-                              hipStream_t st);
+static uint32_t tie_hi_of(const flc_codec_params* prm) { return prm->tie == FLC_TIE_HIGHEST ? 1u : 0u; }
 
-static RkdWs carve_rkd(void* base, int64_t n, int64_t d, size_t* bytes) {
-    Carver cv(base);
-    const int64_t C = std::max<int64_t>(host_chunks(d), 1), nn = std::max<int64_t>(n, 1);
-    RkdWs s;
-    s.cnt = cv.take<uint32_t>((size_t)C * nn);
-    s.ckey = cv.take<uint64_t>((size_t)nn);
-    if (bytes) *bytes = cv.bytes();
-    return s;
-}
+// One sel_run call as its TopK regimes see it.  few: sharded candidate lists (k_topk_filter_fast) and
+// the spread select (k_cs_pass); lone_assign: a lone compressVector row on the few-row path, its
+// output zeroed by the filter and finished by k_assign_finish; gfold: many rows, each row group folded
+// right after its select (tiles carried in ws.part), the last group's fold writing out.
+struct TkCall {
+    const flc_codec_params* prm;
+    RowSrc rows;
+    bool vec;
+    int64_t n, d, K;
+    bool assign;
+    const float* w;
+    float wt;
+    float* out;
+    SelWs ws;
+    hipStream_t st;
+    bool few, lone_assign, gfold;
+};
 
-size_t randk_device_workspace(int64_t n, int64_t d) {
-    size_t b = 0;
-    carve_rkd(nullptr, n, d, &b);
-    return b;
-}
-
-static int randk_counts(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, RkdWs ws,
-                        hipStream_t st) {
-    ProfScope _ps("k_randk_counts", st);
-    const int64_t parts = (host_chunks(d) + RKC_BINS - 1) / RKC_BINS;
-    hipLaunchKernelGGL(k_randk_counts, dim3((unsigned)parts, (unsigned)n), dim3(RKC_NT), 0, st, n, d, prm->k, prm->seed,
-                       pat ? pat->client0 : (int64_t)0, ws);
-    FLC_CHECK_LAUNCH("k_randk_counts");
-    return FLC_OK;
-}
-
-// chunk counts of a fold: the caller's (flc_pattern.d_randk_counts, made by flc_device_randk_counts) or
-// computed into ws; the client keys are cheap and always computed here
-static int randk_counts_or_given(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, RkdWs* rw,
-                                 hipStream_t st) {
-    if (pat && pat->d_randk_counts) {
-        rw->cnt = const_cast<uint32_t*>(pat->d_randk_counts);          // read only by the folds
-        hipLaunchKernelGGL(k_randk_ckeys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, prm->seed,
-                           pat->client0, rw->ckey);
-        FLC_CHECK_LAUNCH("k_randk_ckeys");
-        return FLC_OK;
+// k_lone_resident for a row of up to RS_U * 4096 elements per CU (any K): one launch.  *took = false,
+// nothing launched, for a longer row: the list path takes it.
+static int lone_resident_launch(RowSrc rows, int64_t d, int64_t K, SelWs ws, float* out, hipStream_t st, bool* took) {
+    const int64_t cus = rs_cus();
+    const int mult = std::max(1, g_rs_dbg_mult.load());              // (test hook: > 1 forces an aborted call)
+    const int64_t G = std::min<int64_t>(cus * mult, (d + RS_NT * 4 - 1) / (RS_NT * 4));
+    const int64_t e4 = G > 0 ? (d + G * RS_NT * 4 - 1) / (G * RS_NT * 4) : RS_U + 1;
+    if (!(e4 <= RS_U && d * 4 < ((int64_t)1 << 31))) return FLC_OK;
+    const int64_t Gu = (d + e4 * RS_NT * 4 - 1) / (e4 * RS_NT * 4);   // no workgroup of padding only
+    const long long dspin = g_rs_dbg_spin.load();
+    const uint64_t spin = dspin > 0 ? (uint64_t)dspin : (uint64_t)FLC_RS_SPIN;
+    ProfScope _ps("k_lone_resident", st);
+    int dev = 0;
+    FLC_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_rs_mu);
+    RsCtx& rc = g_rs_ctx[dev];
+    if (!rc.ctl) {
+        FLC_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&rc.ctl), (size_t)RS_CTL * sizeof(uint32_t)));
+        FLC_CHECK_HIP(hipMemsetAsync(rc.ctl, 0, (size_t)RS_CTL * sizeof(uint32_t), st));
+        FLC_CHECK_HIP(hipEventCreateWithFlags(&rc.done, FLC_SYNC_EVENT_FLAGS));
     }
-    return randk_counts(prm, pat, n, d, *rw, st);
-}
-
-// the same for randk_shift.hip: wsp holds randk_device_workspace(n, d) bytes
-int randk_device_prepare(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, void* wsp,
-                         const uint32_t** cnt, const uint64_t** ckey, hipStream_t st) {
-    RkdWs rw = carve_rkd(wsp, n, d, nullptr);
-    if (int rc = randk_counts_or_given(prm, pat, n, d, &rw, st)) return rc;
-    *cnt = rw.cnt;
-    *ckey = rw.ckey;
-    return FLC_OK;
-}
-
-// the device sampler's chunk counts of n clients (flc_device_randk_counts: the sampler's test hook)
-int randk_device_counts(uint64_t seed, int64_t client0, int64_t n, int64_t d, int64_t k, uint32_t* cnt, void* wsp,
-                        size_t ws_bytes, hipStream_t st) {
-    if (ws_bytes < randk_device_workspace(n, d)) { set_error("randk counts: workspace too small"); return FLC_ERR_WORKSPACE; }
-    RkdWs ws = carve_rkd(wsp, n, d, nullptr);
-    ws.cnt = cnt;                                    // the counts straight into the caller's array
-    flc_codec_params prm{};
-    prm.codec = FLC_RANDK;
-    prm.k = k;
-    prm.seed = seed;
-    flc_pattern pat{};
-    pat.client0 = client0;
-    return randk_counts(&prm, &pat, n, d, ws, st);
-}
-
-// device-RNG RandK encode + reduce: counts, then the list-free chunk fold
-int randk_device_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d,
-                     const float* w, float wt, float* out, void* wsp, size_t ws_bytes, hipStream_t st) {
-    size_t lb = 0;
-    carve_sel(nullptr, FLC_RANDK, n, d, prm->k, &lb);
-    if (ws_bytes < lb + randk_device_workspace(n, d)) { set_error("randk: workspace too small"); return FLC_ERR_WORKSPACE; }
-    SelWs sw = carve_sel(wsp, FLC_RANDK, n, d, prm->k, nullptr);
-    RkdWs rw = carve_rkd(static_cast<char*>(wsp) + lb, n, d, nullptr);
-    const int64_t C = host_chunks(d);
-    // Long rows (>= 1024 chunks, one wave per chunk fills the chip): the list-free chunk fold, each
-    // wave regenerating the rows' members of its chunk.  Short rows: too few chunks for the
-    // row-serial fold, so the members are written per row (k_randk_gen) and the chunk fold runs
-    // over the lists with its column split (k_chunk_accum).
-    // chunk counts: the caller's (flc_pattern.d_randk_counts, made by flc_device_randk_counts) or
-    // computed here; the client keys are cheap and always computed here
-    auto counts = [&]() -> int { return randk_counts_or_given(prm, pat, n, d, &rw, st); };
-    if (C >= 1024) {
-        if (int rc = counts()) return rc;
-        ProfScope _ps("k_randk_fold", st);
-        const int ab = grid_stride_blocks((C + 3) / 4, 16384);
-        hipLaunchKernelGGL((k_randk_fold<CHUNK>), dim3(ab), dim3(256), 0, st, rows, n, d, rw.cnt, rw.ckey,
-                           prm->randk_scale, w, wt, out);
-        FLC_CHECK_LAUNCH("k_randk_fold");
-        return FLC_OK;
+    if (rc.last && rc.last != st) {
+        if (!FLC_RS_EVREC) FLC_CHECK_HIP(hipEventRecord(rc.done, rc.last));   // (probe builds)
+        FLC_CHECK_HIP(hipStreamWaitEvent(st, rc.done, 0));
     }
-    if (int rc = counts()) return rc;
-    hipLaunchKernelGGL(k_randk_tab, dim3((unsigned)n), dim3(256), 0, st, n, d, prm->k, rw.cnt, sw);
-    FLC_CHECK_LAUNCH("k_randk_tab");
-    {
-        ProfScope _ps("k_randk_gen", st);
-        const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((C + 4 * RKG_CPW - 1) / (4 * RKG_CPW), 4096));
-        hipLaunchKernelGGL(k_randk_gen, dim3((unsigned)gx, (unsigned)std::min<int64_t>(n, 65535)), dim3(256), 0, st, rows,
-                           n, d, rw.ckey, prm->randk_scale, sw);
-        FLC_CHECK_LAUNCH("k_randk_gen");
-    }
-    return launch_chunk_accum(n, d, sw, false, w, wt, out, st);
-}
-
-// TopK row-group fold: rows [r0, r1) into the running tiles (ws.part); beside a filter the
-// one-wave workgroups (<= 102 VGPRs, 16 KB of LDS: room is left beside the filter's waves), the
-// exposed last group in 4-wave workgroups
-static int launch_group_fold(int64_t n, int64_t d, SelWs ws, const float* w, float wt, float* out, int64_t r0, int64_t r1,
-                             bool first, bool last, bool exposed, hipStream_t st) {
-    const int64_t C = host_chunks(d);
-    ProfScope _ps("k_chunk_accum", st);
-    if (!exposed) {
-        const int ab = grid_stride_blocks(C, 16384);
-        if (w) hipLaunchKernelGGL((k_chunk_accum1<true>), dim3(ab), dim3(64), CHUNK * sizeof(float), st, n, d, ws, w, wt, out, r0, r1,
-                                  first ? 1 : 0, last ? 1 : 0);
-        else hipLaunchKernelGGL((k_chunk_accum1<false>), dim3(ab), dim3(64), CHUNK * sizeof(float), st, n, d, ws, w, wt, out, r0, r1,
-                                first ? 1 : 0, last ? 1 : 0);
+    if (++rc.seq == 0u) rc.seq = 1u;                              // (0: no call; RS_GAVE's cleared value)
+    const int e4i = (int)e4;
+    if (FLC_RS_COOP) {
+        RowSrc ra = rows;
+        int64_t da = d, ka = K;
+        SelWs wa = ws;
+        float* oa = out;
+        int ea = e4i;
+        uint32_t* ca = rc.ctl;
+        uint32_t sa = rc.seq;
+        uint64_t pa = spin;
+        uint32_t xa = rc.xcum;
+        void* args[] = {&ra, &da, &ka, &wa, &oa, &ea, &ca, &sa, &pa, &xa};
+        FLC_CHECK_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&k_lone_resident<RS_U>), dim3((unsigned)Gu),
+                                                 dim3(RS_NT), args, 0, st));
     } else {
-        constexpr int LTS = FLC_TK_LAST_TS;
-        const int ab = grid_stride_blocks((C * (CHUNK / LTS) + 3) / 4, 4096);
-        if (w) hipLaunchKernelGGL((k_chunk_accum<false, LTS, true>), dim3(ab), dim3(256), 0, st, n, d, ws, w, wt, out, r0, r1,
-                                  first ? 1 : 0, last ? 1 : 0);
-        else hipLaunchKernelGGL((k_chunk_accum<false, LTS, false>), dim3(ab), dim3(256), 0, st, n, d, ws, w, wt, out, r0, r1,
-                                first ? 1 : 0, last ? 1 : 0);
+        hipLaunchKernelGGL((k_lone_resident<RS_U>), dim3((unsigned)Gu), dim3(RS_NT), 0, st, rows, d, K, ws, out, e4i,
+                           rc.ctl, rc.seq, spin, rc.xcum);
     }
-    FLC_CHECK_LAUNCH("k_chunk_accum(group)");
+    FLC_CHECK_LAUNCH("k_lone_resident");
+    rc.xcum += (uint32_t)Gu;                                      // (every workgroup counts out once)
+    if (FLC_RS_EVREC) FLC_CHECK_HIP(hipEventRecord(rc.done, st));
+    rc.last = st;
+    *took = true;
     return FLC_OK;
 }
 
-// chunk-owner fold of the rows' lists (TopK candidates, RandK members)
-static int launch_chunk_accum(int64_t n, int64_t d, SelWs ws, bool assign, const float* w, float wt, float* out,
-                              hipStream_t st) {
-    const int64_t C = host_chunks(d);
-    { ProfScope _ps("k_chunk_accum", st);
-    // few chunks (short rows: C2's D = 1 M has 245): split each chunk's columns over 2 or 4 waves so
-    // the latency-bound row walk runs on more of the chip (many chunks: one wave each, measured best)
-    int parts = accum_parts();
-    if (parts == 0) parts = C >= 1024 ? 1 : (C >= 256 ? 2 : 4);
-    auto go = [&](auto ts, int ab) {
-        constexpr int TS = decltype(ts)::value;
-        if (assign) hipLaunchKernelGGL((k_chunk_accum<true, TS>), dim3(ab), dim3(256), 0, st, n, d, ws, w, wt, out);
-        else if (w) hipLaunchKernelGGL((k_chunk_accum<false, TS, true>), dim3(ab), dim3(256), 0, st, n, d, ws, w, wt, out);
-        else hipLaunchKernelGGL((k_chunk_accum<false, TS, false>), dim3(ab), dim3(256), 0, st, n, d, ws, w, wt, out);
+// A lone compressVector row up to RS_U * 4096 elements per CU (any K): in registers, one
+// launch.  Not inside a stream capture (the call's sequence number and the cross-stream
+// serialisation are host state a replayed graph would not redo): the list path there.
+static int topk_lone_resident(const TkCall& c, bool* took) {
+    *took = false;
+    if (!(c.assign && c.n == 1 && !assign_fold() && lone_path() == 2)) return FLC_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    FLC_CHECK_HIP(hipStreamIsCapturing(c.st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return FLC_OK;
+    return lone_resident_launch(c.rows, c.d, c.K, c.ws, c.out, c.st, took);
+}
+
+// the candidate select of rows [r0, r0 + rn) on stream sx.  few rows (a lone compressVector): each
+// list over 64 workgroups, one launch per digit (a finished row's workgroups exit at once); with
+// list mode two launches settle a row whose first digit's bin holds <= CS_LCAP entries
+// (~(4 sqrt(ks) + 8) D / 16 K spread over 256-512 bins: up to ~900 at D = 64 M), else 3 cover every
+// shift; many rows: 512-thread workgroups (measured 0.289 -> 0.263 ms against 256 at C3)
+static void launch_select(const TkCall& c, int64_t r0, int64_t rn, bool last_of_many, hipStream_t sx) {
+    const int64_t n = c.n, d = c.d, K = c.K;
+    const SelWs& ws = c.ws;
+    if (c.few) {
+        const int np = (FLC_CS_LIST && d <= FLC_CS_TWO_MAXD) ? 2 : 3;
+        for (int p = 0; p < np; ++p)
+            hipLaunchKernelGGL(k_cs_pass, dim3((unsigned)CS_SH, (unsigned)n), dim3(CS_NT), 0, c.st, K, ws,
+                               p == np - 1 ? 1 : 0);
+    } else if (c.gfold) {
+        // the select with the exact fallback in the same workgroup (every row final after it)
+        const bool big = rn < 128 || last_of_many;
+        const int nt = big ? 1024 : FLC_TK_SIDE_NT;
+        const dim3 grid((unsigned)(big ? rn : grid_stride_blocks(rn, 8192)));
+        with_vec(c.vec, [&](auto v) {
+            constexpr bool V = decltype(v)::value;
+            if (big) hipLaunchKernelGGL((k_cand_select_x<1024, V>), grid, dim3(nt), 0, sx, c.rows, n, r0, rn, d, K, ws);
+            else if (FLC_TK_SIDE_NT == 256) hipLaunchKernelGGL((k_cand_select_x<256, V>), grid, dim3(nt), 0, sx, c.rows, n, r0, rn, d, K, ws);
+            else hipLaunchKernelGGL((k_cand_select_x<512, V>), grid, dim3(nt), 0, sx, c.rows, n, r0, rn, d, K, ws);
+        });
+    } else if (rn < 128 || last_of_many)
+        // few rows, or the last tail group (its select is exposed, nothing runs beside it):
+        // 1024-thread workgroups, twice the loads in flight per row
+        hipLaunchKernelGGL(k_cand_select<1024>, dim3((unsigned)rn), dim3(1024), 0, sx, r0, rn, K, ws);
+    else if (FLC_TK_SIDE_NT == 256)
+        // beside the next group's filter: one wave per SIMD (66 VGPRs) fits in the VGPRs the
+        // filter's three waves per SIMD leave free, so the select co-resides with the
+        // filter's blocks instead of displacing one (512-thread selects slowed the filter
+        // they ran beside by ~8 %, round-4 trace)
+        hipLaunchKernelGGL(k_cand_select<256>, dim3(grid_stride_blocks(rn, 8192)), dim3(256), 0, sx, r0, rn, K, ws);
+    else hipLaunchKernelGGL(k_cand_select<512>, dim3(grid_stride_blocks(rn, 8192)), dim3(512), 0, sx, r0, rn, K, ws);
+}
+
+// Every K that is not dense (K <= D / 16): the sample, then per row group the filter (the full
+// read), the candidate select and the exact fallback of the group's rows; with TG > 1 groups the
+// select + fallback of group g run on a side stream under the filter of group g + 1 (both per-row,
+// other rows' lists), and the side stream is joined back to st at the end.
+static int topk_fast_groups(const TkCall& c) {
+    const int64_t n = c.n, d = c.d, K = c.K;
+    const SelWs& ws = c.ws;
+    const hipStream_t st = c.st;
+    const bool few = c.few;
+    const int TG = few ? 1 : tk_tail_groups(c.prm, n);
+    hipStream_t sside = st;
+    TkCtx* cx = nullptr;
+    std::unique_lock<std::mutex> lk;
+    if (TG > 1) {
+        int dev = 0;
+        FLC_CHECK_HIP(hipGetDevice(&dev));
+        lk = std::unique_lock<std::mutex>(g_tk_mu);
+        cx = &g_tk_ctx[dev];
+        if (!cx->side) {
+            int lo = 0, hi = 0;
+            FLC_CHECK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+            FLC_CHECK_HIP(hipStreamCreateWithPriority(&cx->side, hipStreamNonBlocking, hi));
+        }
+        while ((int)cx->ev.size() < TG + 3) {
+            hipEvent_t e;
+            FLC_CHECK_HIP(hipEventCreateWithFlags(&e, FLC_SYNC_EVENT_FLAGS));
+            cx->ev.push_back(e);
+        }
+        sside = cx->side;
+    }
+    // the sample: group 0's rows before its filter; with row groups the other rows' samples run
+    // on the side stream beside group 0's filter (after the work queued before this call), and
+    // group 1's filter waits for them — only group 0's share of the sample is exposed
+    const bool split = FLC_TK_SPLIT_SAMPLE && TG > 1;
+    const int64_t rs1 = split ? group_row(n, TG, 1, FLC_TK_LASTPCT) : n;
+    auto sample = [&](int64_t a, int64_t b, hipStream_t sx) {
+        if (b <= a) return;
+        ProfScope _ps("k_topk_sample", sx);
+        // 1024-thread workgroups for any row count (measured 0.098 -> 0.066 ms against 256 at C3)
+        hipLaunchKernelGGL((few ? k_topk_sample<1024, true> : k_topk_sample<1024, false>), dim3((unsigned)(b - a)), dim3(1024), 0, sx,
+                           c.rows, n, d, K, ws, few ? 1 : 0, a);
     };
-    if (parts == 4) go(std::integral_constant<int, CHUNK / 4>{}, grid_stride_blocks((4 * C + 3) / 4, 8192));
-    else if (parts == 2) go(std::integral_constant<int, CHUNK / 2>{}, grid_stride_blocks((2 * C + 3) / 4, 8192));
-    else if (FLC_CA_WPB1 && !assign) {
-        // one-wave workgroups (the tile alone in LDS), one per chunk
-        const int ab = grid_stride_blocks(C, 16384);
-        if (w) hipLaunchKernelGGL((k_chunk_accum1<true>), dim3(ab), dim3(64), CHUNK * sizeof(float), st, n, d, ws, w, wt, out, (int64_t)0, n, 1, 1);
-        else hipLaunchKernelGGL((k_chunk_accum1<false>), dim3(ab), dim3(64), CHUNK * sizeof(float), st, n, d, ws, w, wt, out, (int64_t)0, n, 1, 1);
-    } else go(std::integral_constant<int, CHUNK>{}, grid_stride_blocks((C + 3) / 4, 4096));
+    if (split) {
+        FLC_CHECK_HIP(hipEventRecord(cx->ev[TG + 1], st));
+        FLC_CHECK_HIP(hipStreamWaitEvent(sside, cx->ev[TG + 1], 0));
     }
-    FLC_CHECK_LAUNCH("k_chunk_accum");
+    sample(0, rs1, st);
+    FLC_CHECK_LAUNCH("k_topk_sample");
+    if (split) {
+        sample(rs1, n, sside);
+        FLC_CHECK_LAUNCH("k_topk_sample (side)");
+        FLC_CHECK_HIP(hipEventRecord(cx->ev[TG + 2], sside));
+    }
+    for (int g = 0; g < TG; ++g) {
+        const int64_t r0 = group_row(n, TG, g, FLC_TK_LASTPCT), rn = group_row(n, TG, g + 1, FLC_TK_LASTPCT) - r0;
+        if (split && g == 1) FLC_CHECK_HIP(hipStreamWaitEvent(st, cx->ev[TG + 2], 0));
+        { ProfScope _ps("k_topk_filter", st);
+        // few rows: 2-chunk groups (twice the waves in flight for a lone row)
+        // (one-chunk items for a lone 10 M row measured slower: 26 -> 36 us)
+        // a lone compressVector row: the filter also writes the dense output's zeros
+        float* zout = c.lone_assign ? c.out : nullptr;
+        if (filter_group() == 2 || n * d < ((int64_t)64 << 20)) launch_filter<2>(c.rows, n, r0, rn, d, ws, st, few ? CS_SH : 1, zout);
+        else launch_filter<4>(c.rows, n, r0, rn, d, ws, st, few ? CS_SH : 1, zout); }
+        FLC_CHECK_LAUNCH("k_topk_filter");
+        if (TG > 1) {
+            FLC_CHECK_HIP(hipEventRecord(cx->ev[g], st));
+            FLC_CHECK_HIP(hipStreamWaitEvent(sside, cx->ev[g], 0));
+        }
+        { ProfScope _ps("k_cand_select", sside);
+        launch_select(c, r0, rn, c.gfold ? g == TG - 1 : (TG > 1 && g == TG - 1), sside); }
+        FLC_CHECK_LAUNCH("k_cand_select");
+        if (c.gfold) {
+            // the group's rows folded into the running tiles, on the side stream under the next
+            // group's filter (the last group's: exposed)
+            const bool lastg = g == TG - 1;
+            if (int rc = launch_group_fold(n, d, ws, c.w, c.wt, c.out, r0, r0 + rn, g == 0, lastg, lastg || TG == 1, sside))
+                return rc;
+        }
+    }
+    if (!c.lone_assign && !c.gfold) {
+        // rows the fast path failed (rare): exact selection of every group's failed rows in
+        // ONE launch after the last group's select (a workgroup per row, grid-stride, rows
+        // that did not fail return at once).  Per-group launches beside the next group's
+        // filter held whole CUs (1024-thread workgroups) while doing nothing: the filters
+        // beside them ran 40-110 us slower
+        ProfScope _ps("k_topk_exact_rows", sside);
+        const int eb = grid_stride_blocks(n, FLC_TK_EXACT_WG);
+        with_vec(c.vec, [&](auto v) {
+            hipLaunchKernelGGL((k_topk_exact_rows<decltype(v)::value>), dim3(eb), dim3(EX_NT), 0, sside, c.rows, n, (int64_t)0, n, d, K, ws);
+        });
+        FLC_CHECK_LAUNCH("k_topk_exact_rows");
+    }
+    if (TG > 1) {
+        FLC_CHECK_HIP(hipEventRecord(cx->ev[TG], sside));
+        FLC_CHECK_HIP(hipStreamWaitEvent(st, cx->ev[TG], 0));
+    }
     return FLC_OK;
 }
 
-// The compat RandK lists on their own (randk_shift.hip: the sparse shifted round rewrites the entry
-// values between the bucketing and the fold).  build: k_randk_coarse / k_randk_fine over `rows`
-// exactly as sel_run launches them; fold: k_chunk_accum over the lists as they then stand.
-size_t randk_lists_workspace(int64_t n, int64_t d, int64_t K) {
-    size_t b = 0;
-    carve_sel(nullptr, FLC_RANDK, n, d, K, &b);
-    return b;
-}
-
-static int randk_lists_launch(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d,
-                              SelWs ws, hipStream_t st) {
-    const int64_t K = prm->k, C = host_chunks(d);
-    const int64_t ldi = pat->idx_ld ? pat->idx_ld : K;
-    const int64_t spc = rk_spc(C), sb = (C + spc - 1) / spc;
-    { ProfScope _ps("k_randk_coarse", st);
-    if (spc == 1)
-        hipLaunchKernelGGL(k_randk_coarse<true>, dim3((unsigned)n), dim3(RK_T), 0, st, rows, n, d, K, *pat, ldi,
-                           prm->randk_scale, ws);
-    else
-        hipLaunchKernelGGL(k_randk_coarse<false>, dim3((unsigned)n), dim3(RK_T), 0, st, rows, n, d, K, *pat, ldi,
-                           prm->randk_scale, ws); }
-    FLC_CHECK_LAUNCH("k_randk_coarse");
-    if (spc > 1) {
-        ProfScope _ps("k_randk_fine", st);
-        hipLaunchKernelGGL(k_randk_fine, dim3((unsigned)sb, (unsigned)n), dim3(RK_FTHR), (size_t)spc * sizeof(uint32_t),
-                           st, rows, n, d, K, prm->randk_scale, ws);
-        FLC_CHECK_LAUNCH("k_randk_fine");
+// Dense K (K > D / 16: the candidate list would not be smaller than the row): every row takes the
+// exact multi-launch path
+static int topk_dense_k(const TkCall& c) {
+    const int64_t n = c.n, d = c.d, K = c.K;
+    const SelWs& ws = c.ws;
+    const hipStream_t st = c.st;
+    FLC_CHECK_HIP(hipMemsetAsync(ws.hist, 0, (size_t)n * HBINS * sizeof(uint32_t), st));
+    FLC_CHECK_HIP(hipMemsetAsync(ws.flags, 0, (size_t)n * sizeof(uint32_t), st));
+    const int64_t bpr = (host_chunks(d) + 3) / 4;
+    hipLaunchKernelGGL(k_build_worklist, dim3(1), dim3(1024), 0, st, n, K, d, ws, 1);
+    FLC_CHECK_LAUNCH("k_build_worklist");
+    const int64_t hb = (d + 65535) / 65536;
+    for (int p = 0; p < 3; ++p) {
+        { ProfScope _ps("k_radix_hist_full", st);
+        hipLaunchKernelGGL((k_radix_hist<true>), dim3(grid_stride_blocks(n * hb)), dim3(256), 0, st, c.rows, n, d, p, ws); }
+        FLC_CHECK_LAUNCH("k_radix_hist(full)");
+        hipLaunchKernelGGL((k_radix_select<true>), dim3(grid_stride_blocks(n, 1024)), dim3(256), 0, st, n, p, K, ws);
+        FLC_CHECK_LAUNCH("k_radix_select(full)");
     }
+    hipLaunchKernelGGL(k_tie_count, dim3(grid_stride_blocks(n * bpr, 4096)), dim3(256), 0, st, c.rows, n, d, ws);
+    FLC_CHECK_LAUNCH("k_tie_count");
+    hipLaunchKernelGGL(k_tie_scan, dim3(grid_stride_blocks(n, 1024)), dim3(256), 0, st, n, d, ws);
+    FLC_CHECK_LAUNCH("k_tie_scan");
+    const int gb = grid_stride_blocks(n * bpr, 8192);
+    { ProfScope _ps("k_topk_filter_exact", st);
+    with_vec(c.vec, [&](auto v) {
+        hipLaunchKernelGGL((k_topk_filter<true, decltype(v)::value>), dim3(gb), dim3(256), 0, st, c.rows, n, d, ws);
+    }); }
+    FLC_CHECK_LAUNCH("k_topk_filter(exact)");
     return FLC_OK;
 }
 
-int randk_lists_build(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d, void* wsp,
-                      RkLists* lists, hipStream_t st) {
-    SelWs ws = carve_sel(wsp, FLC_RANDK, n, d, prm->k, nullptr);
-    lists->tab = ws.tab;
-    lists->idx = ws.ent_idx;
-    lists->val = ws.ent_val;
-    lists->cap = ws.cap;
-    return randk_lists_launch(prm, pat, rows, n, d, ws, st);
+// From the rows' final lists to out.  Every row's list now holds exactly its admitted entries plus,
+// on the fast path, candidates below the exact threshold; k_chunk_accum admits key >= thr.
+static int topk_epilogue(const TkCall& c) {
+    if (c.lone_assign) {
+        // output zeros written by the filter; exact fallback (if the row failed) + scatter
+        ProfScope _ps("k_assign_finish", c.st);
+        with_vec(c.vec, [&](auto v) {
+            hipLaunchKernelGGL((k_assign_finish<decltype(v)::value>), dim3(CS_SH), dim3(EX_NT), 0, c.st, c.rows, c.d, c.K, c.ws, c.out);
+        });
+        FLC_CHECK_LAUNCH("k_assign_finish");
+        return FLC_OK;
+    }
+    if (c.gfold) return FLC_OK;                     // the last group's fold wrote out
+    if (c.assign && c.n == 1 && !assign_fold()) {
+        FLC_CHECK_HIP(hipMemsetAsync(c.out, 0, (size_t)c.d * sizeof(float), c.st));
+        launch_assign_scatter(c.ws, c.out, c.few, c.st);
+        FLC_CHECK_LAUNCH("k_assign_scatter");
+        return FLC_OK;
+    }
+    return launch_chunk_accum(c.n, c.d, c.ws, c.assign, c.w, c.wt, c.out, c.st);
 }
 
-int randk_lists_fold(int64_t n, int64_t d, int64_t K, void* wsp, const float* w, float wt, float* out, hipStream_t st) {
-    return launch_chunk_accum(n, d, carve_sel(wsp, FLC_RANDK, n, d, K, nullptr), false, w, wt, out, st);
-}
-
+// Runs the TopK / RandK pipeline for n rows and writes out (ASSIGN: n == 1 dense encode): the
+// argument checks, the carve and the tie rule, then one call per regime.
 // lists_only (topk_lists_build, TopK): everything up to the rows' final lists and admission state — no
 // lone-row path (assign false), no row-group folds, no final fold; the side stream is joined back to st
 static int sel_run_impl(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bool vec, int64_t n, int64_t d,
@@ -4075,252 +2858,27 @@ static int sel_run_impl(const flc_codec_params* prm, const flc_pattern* pat, Row
     carve_sel(nullptr, codec, n, d, K, &need);
     if (ws_bytes < need) { set_error("select: workspace %zu < %zu", ws_bytes, need); return FLC_ERR_WORKSPACE; }
     SelWs ws = carve_sel(wsp, codec, n, d, K, nullptr);
-    if (codec == FLC_TOPK) {
-        if (prm->tie != FLC_TIE_LOWEST && prm->tie != FLC_TIE_HIGHEST) { set_error("topk: unknown tie rule %d", prm->tie); return FLC_ERR_ARG; }
-        ws.tie_hi = prm->tie == FLC_TIE_HIGHEST ? 1u : 0u;
-    }
-    const int64_t C = host_chunks(d);
-    bool lone_assign = false, gfold = false;
-    // TopK, few rows: sharded candidate lists (k_topk_filter_fast) and the spread select (k_cs_pass)
-    const bool few = codec == FLC_TOPK && n <= CS_FEW && !cs_single() && sel_capacity(codec, d, K) >= (int64_t)CS_SH * GCAP;
     if (codec == FLC_RANDK) {
         if (int rc = randk_lists_launch(prm, pat, rows, n, d, ws, st)) return rc;
-    } else {  // TOPK
-        // a lone compressVector row up to RS_U * 4096 elements per CU (any K): in registers, one
-        // launch.  Not inside a stream capture (the call's sequence number and the cross-stream
-        // serialisation are host state a replayed graph would not redo): the list path there.
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (assign && n == 1 && !assign_fold() && lone_path() == 2) FLC_CHECK_HIP(hipStreamIsCapturing(st, &cap));
-        if (assign && n == 1 && !assign_fold() && lone_path() == 2 && cap == hipStreamCaptureStatusNone) {
-            const int64_t cus = rs_cus();
-            const int mult = std::max(1, g_rs_dbg_mult.load());              // (test hook: > 1 forces an aborted call)
-            const int64_t G = std::min<int64_t>(cus * mult, (d + RS_NT * 4 - 1) / (RS_NT * 4));
-            const int64_t e4 = G > 0 ? (d + G * RS_NT * 4 - 1) / (G * RS_NT * 4) : RS_U + 1;
-            if (e4 <= RS_U && d * 4 < ((int64_t)1 << 31)) {
-                const int64_t Gu = (d + e4 * RS_NT * 4 - 1) / (e4 * RS_NT * 4);   // no workgroup of padding only
-                const long long dspin = g_rs_dbg_spin.load();
-                const uint64_t spin = dspin > 0 ? (uint64_t)dspin : (uint64_t)FLC_RS_SPIN;
-                ProfScope _ps("k_lone_resident", st);
-                int dev = 0;
-                FLC_CHECK_HIP(hipGetDevice(&dev));
-                std::lock_guard<std::mutex> lk(g_rs_mu);
-                RsCtx& rc = g_rs_ctx[dev];
-                if (!rc.ctl) {
-                    FLC_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&rc.ctl), (size_t)RS_CTL * sizeof(uint32_t)));
-                    FLC_CHECK_HIP(hipMemsetAsync(rc.ctl, 0, (size_t)RS_CTL * sizeof(uint32_t), st));
-                    FLC_CHECK_HIP(hipEventCreateWithFlags(&rc.done, FLC_SYNC_EVENT_FLAGS));
-                }
-                if (rc.last && rc.last != st) {
-                    if (!FLC_RS_EVREC) FLC_CHECK_HIP(hipEventRecord(rc.done, rc.last));   // (probe builds)
-                    FLC_CHECK_HIP(hipStreamWaitEvent(st, rc.done, 0));
-                }
-                if (++rc.seq == 0u) rc.seq = 1u;                              // (0: no call; RS_GAVE's cleared value)
-                const int e4i = (int)e4;
-                if (FLC_RS_COOP) {
-                    RowSrc ra = rows;
-                    int64_t da = d, ka = K;
-                    SelWs wa = ws;
-                    float* oa = out;
-                    int ea = e4i;
-                    uint32_t* ca = rc.ctl;
-                    uint32_t sa = rc.seq;
-                    uint64_t pa = spin;
-                    uint32_t xa = rc.xcum;
-                    void* args[] = {&ra, &da, &ka, &wa, &oa, &ea, &ca, &sa, &pa, &xa};
-                    FLC_CHECK_HIP(hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&k_lone_resident<RS_U>), dim3((unsigned)Gu),
-                                                             dim3(RS_NT), args, 0, st));
-                } else {
-                    hipLaunchKernelGGL((k_lone_resident<RS_U>), dim3((unsigned)Gu), dim3(RS_NT), 0, st, rows, d, K, ws, out, e4i,
-                                       rc.ctl, rc.seq, spin, rc.xcum);
-                }
-                FLC_CHECK_LAUNCH("k_lone_resident");
-                rc.xcum += (uint32_t)Gu;                                      // (every workgroup counts out once)
-                if (FLC_RS_EVREC) FLC_CHECK_HIP(hipEventRecord(rc.done, st));
-                rc.last = st;
-                return FLC_OK;
-            }
-        }
-        const bool dense_k = K * 16 > d;   // large K: the candidate list would not be smaller than the row
-        // a lone compressVector (assign, one row) on the fast path: output zeros from the filter, the
-        // exact fallback and the scatter in one launch (k_assign_finish)
-        lone_assign = assign && n == 1 && few && !dense_k && !assign_fold();
-
-        if (dense_k) FLC_CHECK_HIP(hipMemsetAsync(ws.hist, 0, (size_t)n * HBINS * sizeof(uint32_t), st));
-        const int64_t bpr = (C + 3) / 4;
-        if (!dense_k) {
-            // per row group: filter (the full read), then the candidate select and the exact
-            // fallback of the group's rows; with TG > 1 groups the select + fallback of group g run
-            // on a side stream under the filter of group g + 1 (both per-row, other rows' lists)
-            const int TG = few ? 1 : tk_tail_groups(prm, n);
-            // many rows: each group's select does its own exact fallback and its rows are folded
-            // right after it (tiles carried in ws.part), under the next group's filter
-            gfold = FLC_TK_GFOLD && !few && !assign && !dense_k && !lists_only;
-            hipStream_t sside = st;
-            TkCtx* cx = nullptr;
-            std::unique_lock<std::mutex> lk;
-            if (TG > 1) {
-                int dev = 0;
-                FLC_CHECK_HIP(hipGetDevice(&dev));
-                lk = std::unique_lock<std::mutex>(g_tk_mu);
-                cx = &g_tk_ctx[dev];
-                if (!cx->side) {
-                    int lo = 0, hi = 0;
-                    FLC_CHECK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-                    FLC_CHECK_HIP(hipStreamCreateWithPriority(&cx->side, hipStreamNonBlocking, hi));
-                }
-                while ((int)cx->ev.size() < TG + 3) {
-                    hipEvent_t e;
-                    FLC_CHECK_HIP(hipEventCreateWithFlags(&e, FLC_SYNC_EVENT_FLAGS));
-                    cx->ev.push_back(e);
-                }
-                sside = cx->side;
-            }
-            // the sample: group 0's rows before its filter; with row groups the other rows' samples run
-            // on the side stream beside group 0's filter (after the work queued before this call), and
-            // group 1's filter waits for them — only group 0's share of the sample is exposed
-            const bool split = FLC_TK_SPLIT_SAMPLE && TG > 1;
-            const int64_t rs1 = split ? group_row(n, TG, 1, FLC_TK_LASTPCT) : n;
-            auto sample = [&](int64_t a, int64_t b, hipStream_t sx) {
-                if (b <= a) return;
-                ProfScope _ps("k_topk_sample", sx);
-                // 1024-thread workgroups for any row count (measured 0.098 -> 0.066 ms against 256 at C3)
-                hipLaunchKernelGGL((few ? k_topk_sample<1024, true> : k_topk_sample<1024, false>), dim3((unsigned)(b - a)), dim3(1024), 0, sx,
-                                   rows, n, d, K, ws, few ? 1 : 0, a);
-            };
-            if (split) {
-                FLC_CHECK_HIP(hipEventRecord(cx->ev[TG + 1], st));
-                FLC_CHECK_HIP(hipStreamWaitEvent(sside, cx->ev[TG + 1], 0));
-            }
-            sample(0, rs1, st);
-            FLC_CHECK_LAUNCH("k_topk_sample");
-            if (split) {
-                sample(rs1, n, sside);
-                FLC_CHECK_LAUNCH("k_topk_sample (side)");
-                FLC_CHECK_HIP(hipEventRecord(cx->ev[TG + 2], sside));
-            }
-            for (int g = 0; g < TG; ++g) {
-                const int64_t r0 = group_row(n, TG, g, FLC_TK_LASTPCT), rn = group_row(n, TG, g + 1, FLC_TK_LASTPCT) - r0;
-                if (split && g == 1) FLC_CHECK_HIP(hipStreamWaitEvent(st, cx->ev[TG + 2], 0));
-                { ProfScope _ps("k_topk_filter", st);
-                // few rows: 2-chunk groups (twice the waves in flight for a lone row)
-                // (one-chunk items for a lone 10 M row measured slower: 26 -> 36 us)
-                // a lone compressVector row: the filter also writes the dense output's zeros
-                float* zout = lone_assign ? out : nullptr;
-                if (filter_group() == 2 || n * d < ((int64_t)64 << 20)) launch_filter<2>(rows, n, r0, rn, d, ws, st, few ? CS_SH : 1, zout);
-                else launch_filter<4>(rows, n, r0, rn, d, ws, st, few ? CS_SH : 1, zout); }
-                FLC_CHECK_LAUNCH("k_topk_filter");
-                if (TG > 1) {
-                    FLC_CHECK_HIP(hipEventRecord(cx->ev[g], st));
-                    FLC_CHECK_HIP(hipStreamWaitEvent(sside, cx->ev[g], 0));
-                }
-                { ProfScope _ps("k_cand_select", sside);
-                // few rows (a lone compressVector): each list over 64 workgroups, one launch per
-                // digit (a finished row's workgroups exit at once); with list mode two launches
-                // settle a row whose first digit's bin holds <= CS_LCAP entries (~(4 sqrt(ks) + 8)
-                // D / 16 K spread over 256-512 bins: up to ~900 at D = 64 M), else 3 cover every
-                // shift; many rows: 512-thread workgroups (measured 0.289 -> 0.263 ms against 256 at C3)
-                if (few) {
-                    const int np = (FLC_CS_LIST && d <= FLC_CS_TWO_MAXD) ? 2 : 3;
-                    for (int p = 0; p < np; ++p)
-                        hipLaunchKernelGGL(k_cs_pass, dim3((unsigned)CS_SH, (unsigned)n), dim3(CS_NT), 0, st, K, ws,
-                                           p == np - 1 ? 1 : 0);
-                } else if (gfold) {
-                    // the select with the exact fallback in the same workgroup (every row final after
-                    // it), then the group's rows folded into the running tiles, both on the side stream
-                    // under the next group's filter (the last group's: exposed)
-                    const bool big = rn < 128 || g == TG - 1;
-                    const int nt = big ? 1024 : FLC_TK_SIDE_NT;
-                    const dim3 grid((unsigned)(big ? rn : grid_stride_blocks(rn, 8192)));
-                    if (big) {
-                        if (vec) hipLaunchKernelGGL((k_cand_select_x<1024, true>), grid, dim3(nt), 0, sside, rows, n, r0, rn, d, K, ws);
-                        else hipLaunchKernelGGL((k_cand_select_x<1024, false>), grid, dim3(nt), 0, sside, rows, n, r0, rn, d, K, ws);
-                    } else if (FLC_TK_SIDE_NT == 256) {
-                        if (vec) hipLaunchKernelGGL((k_cand_select_x<256, true>), grid, dim3(nt), 0, sside, rows, n, r0, rn, d, K, ws);
-                        else hipLaunchKernelGGL((k_cand_select_x<256, false>), grid, dim3(nt), 0, sside, rows, n, r0, rn, d, K, ws);
-                    } else {
-                        if (vec) hipLaunchKernelGGL((k_cand_select_x<512, true>), grid, dim3(nt), 0, sside, rows, n, r0, rn, d, K, ws);
-                        else hipLaunchKernelGGL((k_cand_select_x<512, false>), grid, dim3(nt), 0, sside, rows, n, r0, rn, d, K, ws);
-                    }
-                } else if (rn < 128 || (TG > 1 && g == TG - 1))
-                    // few rows, or the last tail group (its select is exposed, nothing runs beside it):
-                    // 1024-thread workgroups, twice the loads in flight per row
-                    hipLaunchKernelGGL(k_cand_select<1024>, dim3((unsigned)rn), dim3(1024), 0, sside, r0, rn, K, ws);
-                else if (FLC_TK_SIDE_NT == 256)
-                    // beside the next group's filter: one wave per SIMD (66 VGPRs) fits in the VGPRs the
-                    // filter's three waves per SIMD leave free, so the select co-resides with the
-                    // filter's blocks instead of displacing one (512-thread selects slowed the filter
-                    // they ran beside by ~8 %, round-4 trace)
-                    hipLaunchKernelGGL(k_cand_select<256>, dim3(grid_stride_blocks(rn, 8192)), dim3(256), 0, sside, r0, rn, K, ws);
-                else hipLaunchKernelGGL(k_cand_select<512>, dim3(grid_stride_blocks(rn, 8192)), dim3(512), 0, sside, r0, rn, K, ws); }
-                FLC_CHECK_LAUNCH("k_cand_select");
-                if (gfold) {
-                    const bool lastg = g == TG - 1;
-                    if (int rc = launch_group_fold(n, d, ws, w, wt, out, r0, r0 + rn, g == 0, lastg, lastg || TG == 1, sside))
-                        return rc;
-                }
-            }
-            if (!lone_assign && !gfold) {
-                // rows the fast path failed (rare): exact selection of every group's failed rows in
-                // ONE launch after the last group's select (a workgroup per row, grid-stride, rows
-                // that did not fail return at once).  Per-group launches beside the next group's
-                // filter held whole CUs (1024-thread workgroups) while doing nothing: the filters
-                // beside them ran 40-110 us slower
-                ProfScope _ps("k_topk_exact_rows", sside);
-                const int eb = grid_stride_blocks(n, FLC_TK_EXACT_WG);
-                if (vec) hipLaunchKernelGGL((k_topk_exact_rows<true>), dim3(eb), dim3(EX_NT), 0, sside, rows, n, (int64_t)0, n, d, K, ws);
-                else hipLaunchKernelGGL((k_topk_exact_rows<false>), dim3(eb), dim3(EX_NT), 0, sside, rows, n, (int64_t)0, n, d, K, ws);
-                FLC_CHECK_LAUNCH("k_topk_exact_rows");
-            }
-            if (TG > 1) {
-                FLC_CHECK_HIP(hipEventRecord(cx->ev[TG], sside));
-                FLC_CHECK_HIP(hipStreamWaitEvent(st, cx->ev[TG], 0));
-            }
-        } else {
-            FLC_CHECK_HIP(hipMemsetAsync(ws.flags, 0, (size_t)n * sizeof(uint32_t), st));
-        }
-        if (dense_k) {
-        // dense K: every row takes the exact multi-launch path
-        hipLaunchKernelGGL(k_build_worklist, dim3(1), dim3(1024), 0, st, n, K, d, ws, 1);
-        FLC_CHECK_LAUNCH("k_build_worklist");
-        const int64_t hb = (d + 65535) / 65536;
-        for (int p = 0; p < 3; ++p) {
-            { ProfScope _ps("k_radix_hist_full", st);
-hipLaunchKernelGGL((k_radix_hist<true>), dim3(grid_stride_blocks(n * hb)), dim3(256), 0, st, rows, n, d, p, ws); }
-            FLC_CHECK_LAUNCH("k_radix_hist(full)");
-            hipLaunchKernelGGL((k_radix_select<true>), dim3(grid_stride_blocks(n, 1024)), dim3(256), 0, st, n, p, K, ws);
-            FLC_CHECK_LAUNCH("k_radix_select(full)");
-        }
-        hipLaunchKernelGGL(k_tie_count, dim3(grid_stride_blocks(n * bpr, 4096)), dim3(256), 0, st, rows, n, d, ws);
-        FLC_CHECK_LAUNCH("k_tie_count");
-        hipLaunchKernelGGL(k_tie_scan, dim3(grid_stride_blocks(n, 1024)), dim3(256), 0, st, n, d, ws);
-        FLC_CHECK_LAUNCH("k_tie_scan");
-        int gb = grid_stride_blocks(n * bpr, 8192);
-        { ProfScope _ps("k_topk_filter_exact", st);
-if (vec) hipLaunchKernelGGL((k_topk_filter<true, true>), dim3(gb), dim3(256), 0, st, rows, n, d, ws);
-        else hipLaunchKernelGGL((k_topk_filter<true, false>), dim3(gb), dim3(256), 0, st, rows, n, d, ws); }
-        FLC_CHECK_LAUNCH("k_topk_filter(exact)");
-        }
+        return launch_chunk_accum(n, d, ws, assign, w, wt, out, st);
     }
-    // Every row's list now holds exactly its admitted entries plus, on the fast path, candidates
-    // below the exact threshold; k_chunk_accum admits key >= thr.
-    if (lists_only) return FLC_OK;
-    if (lone_assign) {
-        // output zeros written by the filter; exact fallback (if the row failed) + scatter
-        ProfScope _ps("k_assign_finish", st);
-        if (vec) hipLaunchKernelGGL((k_assign_finish<true>), dim3(CS_SH), dim3(EX_NT), 0, st, rows, d, K, ws, out);
-        else hipLaunchKernelGGL((k_assign_finish<false>), dim3(CS_SH), dim3(EX_NT), 0, st, rows, d, K, ws, out);
-        FLC_CHECK_LAUNCH("k_assign_finish");
-        return FLC_OK;
-    }
-    if (gfold) return FLC_OK;                       // the last group's fold wrote out
-    if (assign && n == 1 && codec == FLC_TOPK && !assign_fold()) {
-        FLC_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)d * sizeof(float), st));
-        const int sb = (int)std::max<int64_t>(1, std::min<int64_t>((sel_capacity(codec, d, K) + 255) / 256, 2048));
-        hipLaunchKernelGGL(k_assign_scatter, dim3(sb), dim3(256), 0, st, ws, out, few ? 1 : 0);
-        FLC_CHECK_LAUNCH("k_assign_scatter");
-        return FLC_OK;
-    }
-    return launch_chunk_accum(n, d, ws, assign, w, wt, out, st);
+    if (prm->tie != FLC_TIE_LOWEST && prm->tie != FLC_TIE_HIGHEST) { set_error("topk: unknown tie rule %d", prm->tie); return FLC_ERR_ARG; }
+    ws.tie_hi = tie_hi_of(prm);
+    TkCall c{prm, rows, vec, n, d, K, assign, w, wt, out, ws, st, false, false, false};
+    bool took = false;
+    if (int rc = topk_lone_resident(c, &took)) return rc;
+    if (took) return FLC_OK;
+    const bool dense_k = K * 16 > d;   // large K: the candidate list would not be smaller than the row
+    // TopK, few rows: sharded candidate lists (k_topk_filter_fast) and the spread select (k_cs_pass)
+    c.few = n <= CS_FEW && !cs_single() && sel_capacity(codec, d, K) >= (int64_t)CS_SH * GCAP;
+    // a lone compressVector (assign, one row) on the fast path: output zeros from the filter, the
+    // exact fallback and the scatter in one launch (k_assign_finish)
+    c.lone_assign = assign && n == 1 && c.few && !dense_k && !assign_fold();
+    // many rows: each group's select does its own exact fallback and its rows are folded
+    // right after it (tiles carried in ws.part), under the next group's filter
+    c.gfold = FLC_TK_GFOLD && !c.few && !assign && !dense_k && !lists_only;
+    if (int rc = dense_k ? topk_dense_k(c) : topk_fast_groups(c)) return rc;
+    return lists_only ? FLC_OK : topk_epilogue(c);
 }
 
 int sel_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, bool vec, int64_t n, int64_t d,
@@ -4338,21 +2896,14 @@ int topk_lists_build(const flc_codec_params* prm, RowSrc rows, bool vec, int64_t
     if (int rc = sel_run_impl(prm, nullptr, rows, vec, n, d, /*assign=*/false, nullptr, 1.f, nullptr, wsp, ws_bytes, st, true))
         return rc;
     const SelWs ws = carve_sel(wsp, FLC_TOPK, n, d, prm->k, nullptr);
-    lists->tab = ws.tab;
-    lists->ent_idx = ws.ent_idx;
-    lists->ent_val = ws.ent_val;
-    lists->cap = ws.cap;
-    lists->thr = ws.thr;
-    lists->flags = ws.flags;
-    lists->tiecut = ws.tiecut;
-    lists->tie_hi = prm->tie == FLC_TIE_HIGHEST ? 1u : 0u;
+    *lists = TkLists{ws.tab, ws.ent_idx, ws.ent_val, ws.cap, ws.thr, ws.flags, ws.tiecut, tie_hi_of(prm)};
     return FLC_OK;
 }
 
 int topk_lists_fold(const flc_codec_params* prm, int64_t n, int64_t d, void* wsp, const float* w, float wt, float* out,
                     hipStream_t st) {
     SelWs ws = carve_sel(wsp, FLC_TOPK, n, d, prm->k, nullptr);
-    ws.tie_hi = prm->tie == FLC_TIE_HIGHEST ? 1u : 0u;
+    ws.tie_hi = tie_hi_of(prm);
     return launch_chunk_accum(n, d, ws, false, w, wt, out, st);
 }
 
@@ -4432,40 +2983,7 @@ int sel_unpack_reduce(const flc_codec_params* prm, const void* base, int64_t ld_
     FLC_CHECK_LAUNCH("k_unpack_lists");
     hipLaunchKernelGGL(k_unpack_tab, dim3((unsigned)((C + 255) / 256), (unsigned)n), dim3(256), 0, st, n, d, ws);
     FLC_CHECK_LAUNCH("k_unpack_tab");
-    const int ab = grid_stride_blocks((C + 3) / 4, 4096);
-    { ProfScope _ps("k_chunk_accum", st);
-    hipLaunchKernelGGL((k_chunk_accum<false>), dim3(ab), dim3(256), 0, st, n, d, ws, w, wt, out); }
-    FLC_CHECK_LAUNCH("k_chunk_accum");
-    return FLC_OK;
-}
-
-// Dense single-vector RandK: out = 0; out[S] = scale * x[S]  (compressors.py:242-243)
-__global__ __launch_bounds__(256) void k_randk_dense(const float* __restrict__ x, int64_t K, const int64_t* __restrict__ idx,
-                                                     float scale, float* __restrict__ out) {
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < K; t += (int64_t)gridDim.x * 256) {
-        const int64_t j = idx[t];
-        out[j] = scale * x[j];
-    }
-}
-
-int randk_dense(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, float* out,
-                void* wsp, size_t ws_bytes, hipStream_t st) {
-    if (d == 0) return FLC_OK;
-    if (prm->k < 1 || prm->k > d) { set_error("randk: K outside [1, D]"); return FLC_ERR_ARG; }
-    FLC_CHECK_HIP(hipMemsetAsync(out, 0, (size_t)d * sizeof(float), st));
-    if (pat && pat->d_randk_idx) {
-        int g = (int)std::max<int64_t>(1, std::min<int64_t>((prm->k + 255) / 256, 1024));
-        hipLaunchKernelGGL(k_randk_dense, dim3(g), dim3(256), 0, st, x, prm->k, pat->d_randk_idx, prm->randk_scale, out);
-        FLC_CHECK_LAUNCH("k_randk_dense");
-        return FLC_OK;
-    }
-    if (ws_bytes < randk_device_workspace(1, d)) { set_error("randk: workspace too small"); return FLC_ERR_WORKSPACE; }
-    RkdWs ws = carve_rkd(wsp, 1, d, nullptr);
-    if (int rc = randk_counts(prm, pat, 1, d, ws, st)) return rc;
-    const int g = grid_stride_blocks((host_chunks(d) + 3) / 4, 4096);
-    hipLaunchKernelGGL(k_randk_scatter_dev, dim3(g), dim3(256), 0, st, x, d, ws.cnt, ws.ckey, prm->randk_scale, out);
-    FLC_CHECK_LAUNCH("k_randk_scatter_dev");
-    return FLC_OK;
+    return launch_chunk_accum_whole(n, d, ws, w, wt, out, st);
 }
 
 }  // namespace flc
