@@ -111,7 +111,8 @@ struct RowSrc {
     }
 };
 
-// Internal entry points of the codec families (reduce.hip, codecs.hip, select.hip with randk.hip and chunk_accum.hip).
+// Internal entry points of the codec families (reduce.hip, codecs.hip, the selection core:
+// select.hip with topk_filter.hip, topk_select.hip, lone_row.hip, randk.hip and chunk_accum.hip).
 int reduce_impl(RowSrc src, bool rows_vec_ok, int64_t n, int64_t d, const float* x, const float* w, float wt,
                 int mode, float* out, hipStream_t st);
 // norms_given / norm_mode: flc_encode_reduce_ex's selectors (0, FLC_NORMMODE_EXACT: flc_encode_reduce)
@@ -266,7 +267,7 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
 // shape C's fold of base + t over lists in the RkLists layout (k_randk_shift_lfold)
 int randk_shift_lfold_launch(const float* base, int64_t n, int64_t d, RkLists lists, const float* w, float wt, float* out,
                              hipStream_t st);
-// The many-row TopK selection by itself (select.hip): after topk_lists_build row r's entries of chunk
+// The many-row TopK selection by itself (select.hip's dispatcher up to the lists): after topk_lists_build row r's entries of chunk
 // c are ent_idx / ent_val[r * cap + tab[c * n + r].x + t], t < tab[c * n + r].y, and an entry is
 // admitted iff (mag_key(val), idx ^ txm) >= (T, cut) with T, cut taken from thr / flags / tiecut as
 // k_chunk_accum's load_meta takes them (flag TK_F_EXACT: every entry; TK_F_TIES: the tie cut).  A

@@ -274,7 +274,7 @@ __global__ __launch_bounds__(DS_SNT) void k_ds_sample(SRC rows, int64_t n, int64
 }
 
 // ------------------------------------------------------------------------------------------
-// Filter: a RING-deep buffer-load pipeline across chunks and items (select.hip's TopK filter
+// Filter: a RING-deep buffer-load pipeline across chunks and items (topk_filter.hip's TopK filter
 // structure), the dithering candidate test and the norm.  A work item is DS_FGS consecutive
 // 4096-element chunks of one row; its candidates are compacted (ballot / mbcnt) into wave-private
 // LDS, classified (sure / drop / ambiguous) and copied out coalesced into the item's FIXED regions

@@ -1,8 +1,9 @@
-// Private to the units of the selection core — select.hip (the TopK pipeline and the host end),
-// randk.hip, chunk_accum.hip — and included by nothing else: the workspace structs, the
-// block primitives, every FLC_* compile-time switch of those units (one definition for all of them,
-// also under XFLAGS) and the host launchers that cross units.  A kernel is defined in one unit
-// together with every host function that launches it; only host functions cross.
+// Private to the units of the selection core — select.hip (the host end), topk_filter.hip,
+// topk_select.hip, lone_row.hip, randk.hip, chunk_accum.hip — and included by nothing else: the
+// workspace structs, the block primitives, every FLC_* compile-time switch of those units (one
+// definition for all of them, also under XFLAGS), TkCall and the host launchers that cross units.
+// A kernel is defined in one unit together with every host function that launches it; only host
+// functions cross.
 //
 // Sparsifying codecs: TopK (compressors.py:330-335) and RandK (240-245), dense single-vector
 // encode and fused batch encode + reduce.
@@ -446,9 +447,41 @@ static inline void with_vec(bool vec, F f) {
     else f(std::false_type{});
 }
 
+// One sel_run call as its TopK regimes see it.  few: sharded candidate lists (k_topk_filter_fast) and
+// the spread select (k_cs_pass); lone_assign: a lone compressVector row on the few-row path, its
+// output zeroed by the filter and finished by k_assign_finish; gfold: many rows, each row group folded
+// right after its select (tiles carried in ws.part), the last group's fold writing out.
+struct TkCall {
+    const flc_codec_params* prm;
+    RowSrc rows;
+    bool vec;
+    int64_t n, d, K;
+    bool assign;
+    const float* w;
+    float wt;
+    float* out;
+    SelWs ws;
+    hipStream_t st;
+    bool few, lone_assign, gfold;
+};
+
 // select.hip
 int64_t sel_capacity(int codec, int64_t d, int64_t K);
 SelWs carve_sel(void* base, int codec, int64_t n, int64_t d, int64_t K, size_t* bytes);
+// topk_filter.hip: the sample of rows [a, b) on sx; the fast filter of rows [r0, r0 + rn) on c.st
+// (2- or 4-chunk groups, per-wave or workgroup items); the exact filter of every row (dense K)
+void launch_sample(const TkCall& c, int64_t a, int64_t b, hipStream_t sx);
+void launch_filter_rows(const TkCall& c, int64_t r0, int64_t rn);
+int launch_filter_exact(const TkCall& c);
+// topk_select.hip: the candidate select of rows [r0, r0 + rn) on sx; the one exact-rows launch of the
+// rows the fast path failed; dense K's worklist, radix passes and tie prefix over the full rows; a
+// lone row's exact fallback + scatter
+void launch_select(const TkCall& c, int64_t r0, int64_t rn, bool last_of_many, hipStream_t sx);
+int launch_exact_rows(const TkCall& c, hipStream_t sx);
+int launch_radix_full(const TkCall& c);
+int launch_assign_finish(const TkCall& c);
+// lone_row.hip: k_lone_resident for a row that fits the chip's registers (*took), serialised across streams
+int lone_resident_launch(RowSrc rows, int64_t d, int64_t K, SelWs ws, float* out, hipStream_t st, bool* took);
 // randk.hip: the compat bucketing of the rows' given indices into ws's lists; the device sampler's run
 int randk_lists_launch(const flc_codec_params* prm, const flc_pattern* pat, RowSrc rows, int64_t n, int64_t d, SelWs ws,
                        hipStream_t st);

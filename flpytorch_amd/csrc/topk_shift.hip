@@ -5,7 +5,8 @@
 //     m = base ? base[j] + t : t;   h' = shift_in[j] + shift_alpha * e
 // for all n rows in a constant number of launches instead of the general entry's row loop:
 //   k_shift_sub_rows      the n differences into a workspace matrix [n][ldd], one streaming launch
-//   topk_lists_build      select.hip's many-row selection over that matrix, unchanged, up to the rows'
+//   topk_lists_build      the selection core's many-row TopK (select.hip's dispatcher; kernels in
+//                         topk_filter.hip, topk_select.hip) over that matrix, unchanged, up to the rows'
 //                         final (index, value) lists and admission state
 //   k_topk_shift_lists    the sparse epilogue: every admitted entry becomes its message value t and, in
 //                         the in-place shapes, the thread that gathered b_i[j] stores the updated element;

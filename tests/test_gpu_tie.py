@@ -238,7 +238,7 @@ def test_compressvector_resident_not_coresident(ag, d, kind):
     xt = torch.from_numpy(x).cuda()
     g2 = min(2 * cus, -(-d // 4096))
     e4 = -(-d // (g2 * 4096))
-    gu = -(-d // (e4 * 4096))                                     # the forced grid (select.hip host code)
+    gu = -(-d // (e4 * 4096))                                     # the forced grid (lone_row.hip host code)
     for tie in ("lowest", "highest"):
         want = _bits(_enc([x], k, tie)[0])
         c = _comp(ag, f"topk:{k}", d, tie)
