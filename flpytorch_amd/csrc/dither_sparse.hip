@@ -72,9 +72,6 @@
 namespace flc {
 
 constexpr uint32_t DS_DENSE = 1u, DS_FAST = 4u;
-#ifndef FLC_DS_W2
-#define FLC_DS_W2 1
-#endif
 constexpr int DS_FGS = 2;                  // chunks per filter work item (8192 elements)
 constexpr int DS_NH = 2 * DS_FGS;          // fold tiles (half chunks) per item
 constexpr int DS_GCAP = 512;               // staged candidates per item (6.25 %; more -> row overflow)
@@ -95,23 +92,14 @@ constexpr float DS_QT = 254.98f;
 constexpr int DS_MAXS = 512;               // level table entries kept in LDS by the fold
 constexpr uint32_t DS_OVF = 0xFFFFFFFFu;   // itm: the item overflowed its staging capacity
 #ifndef FLC_DS_AP
-#define FLC_DS_AP 16                // 16: measured 0.673 -> 0.622 ms at C4 (32: same as 16)
+#define FLC_DS_AP 16
 #endif
-constexpr int DS_AP = FLC_DS_AP;           // rows of entry lists in flight in the fold
+constexpr int DS_AP = FLC_DS_AP;           // passed for k_ds_accum's AP
 // rows per block of the filter's item order: 16 measured as fast as one block of all rows at C4
 // (and 1, row-major, 1-2 % slower on the same box); a block never reads one row twice, so rows
 // that alias (C5's replayed pool) are still read from HBM once per client
 constexpr int64_t DS_RB = 16;
 constexpr int DS_RINGC = 4;                // compat filter ring (x + u: 24 B per lane per step)
-// Per-lane candidate staging (device-RNG filter): each lane appends its candidates to its own
-// column of the wave's staging, slot row min(count, DS_PLS) (row DS_PLS absorbs a lane's
-// overflow), so the per-element path has no cross-lane prefix (ballot / mbcnt) and no scalar
-// counter chain; the columns are compacted once per item.  A lane with more than DS_PLS
-// candidates in an item (Poisson(2.7) at C4: ~4e-3 of items) re-reads its elements afterwards.
-#ifndef FLC_DS_PL
-#define FLC_DS_PL 0
-#endif
-constexpr int DS_PLS = 10;
 #ifndef FLC_DS_STPOL
 // k_ds_filter's list copy-outs (sure and ambiguous entries) as nontemporal stores: bit-identical,
 // C4 9.736 -> 9.615 ms per step on one allocation (profiles/r05/ab_list_stnt.txt; the same for
@@ -282,7 +270,7 @@ __global__ __launch_bounds__(DS_SNT) void k_ds_sample(SRC rows, int64_t n, int64
 // in-order vmcnt queue of the load stream.  The tab gets the sure entries' (offset, count) per
 // 2048-element half chunk (the fold's tile).
 // ------------------------------------------------------------------------------------------
-// PROBE (tuning / A/B builds only, FLC_DS_PROBE or -DFLC_DS_PROBE_DEF; outputs NOT valid): 1 fp32
+// PROBE (-DFLC_TUNING builds only, FLC_DS_PROBE in the environment; outputs NOT valid): 1 fp32
 // norm; 2 no candidate staging; 3 loads + norm only; 4 the draw's group hash without its
 // multiplies; 5 exec-narrowed staging without a branch; 6 staging without the classification
 //
@@ -344,7 +332,7 @@ template <int RING, int GCAP, int PROBE = 0, bool COMPAT = false, bool TNS = fal
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FLC_DS_WPEC : FLC_DS_WPE))) void k_ds_filter(SRC rows, int64_t n, int64_t r0, int64_t rn, int64_t rb, int64_t d, DsWs ws, UniformSrc us) {
     constexpr int FGS = DS_FGS, NH = DS_NH;
     constexpr bool DIFF = std::is_same<SRC, DiffSrc>::value;
-    static_assert(!DIFF || (!COMPAT && !TNS && PROBE == 0 && !FLC_DS_PL), "two-operand source: the device-RNG, exact-norm filter only");
+    static_assert(!DIFF || (!COMPAT && !TNS && PROBE == 0), "two-operand source: the device-RNG, exact-norm filter only");
     static_assert(16 % RING == 0, "ring must divide the 16 loads of a chunk");
     static_assert(GCAP % 512 == 0 && (GCAP & (GCAP - 1)) == 0, "copy-out in whole 16-B wave slots; wrap mask");
     static_assert(!COMPAT || PROBE == 0, "probes: device-RNG filter only");
@@ -353,13 +341,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
     constexpr int DS_ITEM_STORES = 4 + GCAP / 128;   // partial, itm, tab, sure and ambiguous copy-outs
     // (entry word, x bits); 64 slots past GCAP take the writes of a wave-instruction that starts
     // at GCAP (its item has overflowed)
-    // per-lane staging (PL): DS_PLS + 1 slot rows of 64 lanes, compacted in place into the item's
-    // list; its sure entries (4 halves x DS_HCAP u16 = 1 KB) then go to entries [GCAP, GCAP + 128)
-    constexpr bool PL = FLC_DS_PL && !COMPAT && PROBE == 0;
-    constexpr int SROWS = PL ? (DS_PLS + 1) * 64 : GCAP + 64;
-    static_assert(!PL || (SROWS >= GCAP + 128 && DS_PLS * 64 >= GCAP / 2), "per-lane staging layout");
-    __shared__ __attribute__((aligned(16))) uint2 stage[4][SROWS];
-    __shared__ __attribute__((aligned(16))) uint16_t stage16[4][PL ? 8 : GCAP];
+    __shared__ __attribute__((aligned(16))) uint2 stage[4][GCAP + 64];
+    __shared__ __attribute__((aligned(16))) uint16_t stage16[4][GCAP];
     __shared__ float stagef[4][COMPAT ? GCAP + 64 : 1];     // compat: RD(u) of the staged
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -370,7 +353,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
     if (it >= items) return;
     const uint32_t lphi = (uint32_t)lane * 0x9E3779B1u;    // group index g = c*1024 + 64 L + lane
     uint2* sg = stage[wv];
-    uint16_t* s16 = PL ? reinterpret_cast<uint16_t*>(stage[wv] + GCAP) : stage16[wv];
+    uint16_t* s16 = stage16[wv];
     float* sgf = stagef[wv];
     // LDS byte address of the wave's staging buffer (wave-uniform)
     const uint32_t sla = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) uint2*)sg);
@@ -415,7 +398,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
         const int64_t gi = c / FGS;
         const int64_t nit = it + stride;
         uint32_t cnt = 0;
-        uint32_t lcnt = 0;                                   // PL: this lane's candidates in the item
         double a2 = 0.0;
         double ta[NTA];                                      // TNS: sums of squares per torch lane
 #pragma unroll
@@ -508,7 +490,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
                         // no range test: past the row end the loads return 0, and a zero candidate
                         // is dropped; NaN from 0 * inf (qc = inf) is not a candidate
                         const bool f = fmaf(fabsf(vq[q]), qc, hi) > DS_QT;
-                        const uint64_t m = PL ? 0ull : __ballot(f);
+                        const uint64_t m = __ballot(f);
                         // exec-masked store (a branch-free store of every element to a per-lane spill
                         // slot measured 9.2 -> 11.9 ms: the staging is LDS-issue sensitive)
                         if (PROBE == 5) {
@@ -523,16 +505,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
                                          "ds_write2_b32 %2, %3, %4 offset1:1\n\ts_mov_b64 exec, %0"
                                          : "=&s"(saved) : "s"(m), "v"(la), "v"(jb + (uint32_t)(L * 256 + q)), "v"(__float_as_uint(vq[q]))
                                          : "memory");
-                        } else if (PL) {
-                            // the lane's own column: slot row min(lcnt, DS_PLS), 512 B per row
-                            const uint32_t la = sla + (uint32_t)lane * 8u + min(lcnt, (uint32_t)DS_PLS) * 512u;
-                            if (f)
-                                asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" ::"v"(la), "v"(jb + (uint32_t)(L * 256 + q)),
-                                             "v"(__float_as_uint(vq[q])) : "memory");
-                            lcnt += f ? 1u : 0u;
-                            continue;
                         } else if (PROBE != 2 && f) {
-#if FLC_DS_W2
                             // slot = min(cnt, GCAP) + candidates in lower lanes (< GCAP + 64): exact
                             // while the item fits; past GCAP the item overflows (its row is folded
                             // dense) and the writes land in the spare slots.  The scalar part is folded
@@ -545,11 +518,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
                             const uint32_t la = sb + pre * 8u;
                             asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" ::"v"(la), "v"(jb + (uint32_t)(L * 256 + q)),
                                          "v"(__float_as_uint(vq[q])) : "memory");
-#else
-                            const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)m, cnt)) & (GCAP - 1);
-                            sg[pos] = make_uint2(jb + (uint32_t)(L * 256 + q), __float_as_uint(vq[q]));
-#endif
                         }
                         cnt += (uint32_t)__popcll(m);
                     }
@@ -583,54 +551,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
             a2 = tv;
         } else {
             a2 = wave_sum(a2);                               // fixed butterfly: deterministic
-        }
-        if constexpr (PL) {
-            // Compaction in place: slot row k of every lane with more than k candidates, in row
-            // order, lanes in order within a row.  An entry's new position never exceeds its slot
-            // (k * 64 + lane) and a row is read before any of it is written, so nothing unread is
-            // overwritten.  (The list order is free: k_ds_resolve / k_ds_accum do not depend on it.)
-            const uint32_t lc = min(lcnt, (uint32_t)DS_PLS);
-            for (uint32_t k = 0; k < (uint32_t)DS_PLS; ++k) {
-                const bool v = k < lc;
-                const uint64_t mk = __ballot(v);
-                if (mk == 0) break;
-                if (v) {
-                    const uint32_t pos = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
-                    const uint2 e = sg[k * 64 + lane];
-                    sg[pos] = e;
-                }
-                cnt += (uint32_t)__popcll(mk);
-            }
-            // Lanes past DS_PLS (rare): their candidates from #DS_PLS on were absorbed by the last
-            // row; re-read those lanes' elements of the item and append them (the loads wait
-            // behind the ring's, once)
-            const bool ovl = lcnt > (uint32_t)DS_PLS;
-            if (__ballot(ovl)) {
-                if (cnt + 0u <= (uint32_t)GCAP) {
-                    // one element per step, nothing unrolled: the ring (the next item's loads in
-                    // flight) stays live in registers across this path
-                    const int64_t cg = gi * FGS;
-                    uint32_t seen = 0;
-#pragma unroll 1
-                    for (int e = 0; e < FGS * 64; ++e) {
-                        const int sub = e >> 6, L = (e >> 2) & 15, q = e & 3;
-                        const auto rso = chunk_rsrc(row_a(rows, row), (cg + sub) * CHUNK, d);
-                        const float x = ovl ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rso, lane * 16 + q * 4, L * 1024, 0)) : 0.f;
-                        const uint32_t hg = gmix(lphi + (uint32_t)((cg + sub) * 1024 + L * 64) * 0x9E3779B1u + rk);
-                        const float hi = (float)((hg >> (8 * q)) & 0xFFu);
-                        const bool f = ovl && fmaf(fabsf(x), qc, hi) > DS_QT;
-                        const bool extra = f && seen >= (uint32_t)DS_PLS;
-                        seen += f ? 1u : 0u;
-                        const uint64_t me = __ballot(extra);
-                        const uint32_t pos = cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(me >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)me, 0u));
-                        if (extra && pos < (uint32_t)GCAP + 64u)
-                            sg[pos] = make_uint2((uint32_t)(sub * CHUNK + L * 256 + q) + (uint32_t)lane * 4u, __float_as_uint(x));
-                        cnt += (uint32_t)__popcll(me);
-                    }
-                } else {
-                    cnt = GCAP + 1;                          // the item overflows anyway
-                }
-            }
         }
         const bool fits = cnt <= GCAP;
         const uint32_t base = (uint32_t)gi * GCAP;
@@ -761,245 +681,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COMPAT ? FL
         row = nrow;
         c = nc;
     }
-}
-
-// ------------------------------------------------------------------------------------------
-// Filter v2 (device draws, the product path): the same single pass, with each item's
-// classification moved into the NEXT item's streaming loop.  Probes on one allocation (round 4):
-// the classification epilogue cost k_ds_filter 1.25 ms of 9.69 at C4 (without it 8.44; loads +
-// norm alone 8.36) — while a wave classifies it issues no loads, and the issue-bound epilogue
-// grows on boxes that run a lower sustained clock.  Here the staging is double-buffered: item i
-// is staged into buffer `par` while item i-1's candidates (buffer par ^ 1) are classified one
-// 64-entry batch at a time at 8 fixed points of the loop (between load issues), and item i-1's
-// fixed store sequence goes out at the end of item i.  Same entries, same lists, same bits.
-// ------------------------------------------------------------------------------------------
-#ifndef FLC_DS2_CAP
-#define FLC_DS2_CAP 384              // k_ds_filter2 staging capacity per item (4.7 %; C4 items hold ~2.3 %)
-#endif
-#ifndef FLC_DS2_WPE
-#define FLC_DS2_WPE 5                // LDS: 32 KB per block (FLC_DS2_CAP 384), 5 blocks per CU
-#endif
-template <int RING, int GCAP>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FLC_DS2_WPE))) void k_ds_filter2(RowSrc rows, int64_t n, int64_t r0, int64_t rn, int64_t rb, int64_t d, DsWs ws, UniformSrc) {
-    constexpr int FGS = DS_FGS, NH = DS_NH;
-    // GCAP: the staging capacity (candidates per item; more -> the row is folded dense), at most
-    // DS_GCAP, the stride of the items' ambiguous-entry regions
-    static_assert(FGS == 2 && NH == 4 && GCAP % 128 == 0 && GCAP <= DS_GCAP && DS_HCAP == 128, "batch points / copy-out layout");
-    static_assert(16 % RING == 0, "ring must divide the 16 loads of a chunk");
-    constexpr int NB = GCAP / 64;                          // classification batches of one item
-    constexpr int DS_ITEM_STORES = 4 + GCAP / 128;          // partial, itm, tab, sure and ambiguous copy-outs
-    __shared__ __attribute__((aligned(16))) uint2 stage[2][4][GCAP + 64];
-    __shared__ __attribute__((aligned(16))) uint16_t stage16[4][NH * DS_HCAP];
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t G = ws.G;
-    const int64_t items = rn * G;
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    int64_t it = (int64_t)blockIdx.x * 4 + wv;
-    if (it >= items) return;
-    const uint32_t lphi = (uint32_t)lane * 0x9E3779B1u;    // group index g = c*1024 + 64 L + lane
-    uint16_t* s16 = stage16[wv];
-    float4 ring[RING];
-    auto item_at = [&](int64_t t, int64_t& r, int64_t& g) {   // k_ds_filter's item order
-        const int64_t blk = t / (rb * G), rem = t - blk * rb * G;
-        const int64_t bn = min(rb, rn - blk * rb);
-        g = rem / bn;
-        r = r0 + blk * rb + (rem - g * bn);
-    };
-    int64_t row, gi0;
-    item_at(it, row, gi0);
-    int64_t c = gi0 * FGS;
-    auto rs = chunk_rsrc(rows.row_s(row), c * CHUNK, d);
-#pragma unroll
-    for (int L = 0; L < RING - 1; ++L) {
-        ring[L] = load_q(rs, lane, L);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    {
-        const auto nd = __builtin_amdgcn_make_buffer_rsrc(ws.enta, (short)0, 0, 0x00020000);
-#pragma unroll
-        for (int k = 0; k < DS_ITEM_STORES; ++k) __builtin_amdgcn_raw_buffer_store_b32(0u, nd, lane * 4, k * 256, 0);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // the previous item (pv): its row, item, candidate count, norm partial, classification scales
-    bool pv = false, pfits = true;
-    int64_t prow = 0, pgi = 0;
-    uint32_t pncl = 0, prk = 0;
-    double pa2 = 0.0;
-    float pq0 = 0.f, pq1 = 0.f;
-    uint32_t hs[NH], na = 0;                               // its classification counters
-#pragma unroll
-    for (int u = 0; u < NH; ++u) hs[u] = 0;
-    int par = 0;
-    // batch b of the previous item's candidates: sure entries to s16 (half h's at h * DS_HCAP),
-    // ambiguous ones compacted in place in its staging (a batch reads its 64 slots before it
-    // writes lower ones); k_ds_filter's classification, verbatim
-    auto classify = [&](int b) {
-        uint2* sgp = stage[par ^ 1][wv];
-        const uint32_t e = (uint32_t)(b * 64 + lane);
-        const bool v = e < pncl;
-        const uint2 en = v ? sgp[e] : make_uint2(0u, 0u);
-        const float x = __uint_as_float(en.y), ax = fabsf(x);
-        const uint32_t loc = en.x & 0x1FFFu;
-        const uint32_t j0 = (uint32_t)(pgi * (FGS * CHUNK));
-        const uint32_t hi8 = ds_hi8(j0 + loc, prk);
-        const uint32_t h24 = (hi8 << 16) | (fmix32(colbase(j0 + loc) + (prk ^ 0x27D4EB2Fu)) >> 16);   // h >> 8
-        const float hf = (float)h24 * 0x1p-24f, hfu = (float)(h24 + 1u) * 0x1p-24f;
-        const bool inl = ax * pq0 <= 1.0f - 0x1p-18f;
-        const bool nz = v && !(x == 0.f);
-        const bool sure = nz && inl && fmaf(ax, pq1, hf) >= 1.0f + 0x1p-20f;
-        const bool drop = !nz || (inl && fmaf(ax, pq0, hfu) < 1.0f - 0x1p-20f);
-        const bool amb = !sure && !drop;
-        const uint32_t u = loc >> 11;
-        uint32_t pin = 0;
-#pragma unroll
-        for (int h = 0; h < NH; ++h) {
-            const uint64_t mh = __ballot(sure && u == (uint32_t)h);
-            const uint32_t ph = __builtin_amdgcn_mbcnt_hi((uint32_t)(mh >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mh, hs[h]));
-            pin = u == (uint32_t)h ? ph : pin;
-            hs[h] += (uint32_t)__popcll(mh);
-        }
-        if (sure && pin < (uint32_t)DS_HCAP)
-            s16[u * DS_HCAP + pin] = (uint16_t)((loc & (HCHUNK - 1)) | ((en.y >> 31) << 11) | (1u << 12));
-        const uint64_t ma = __ballot(amb);
-        const uint32_t pa = __builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, na));
-        if (amb) sgp[pa] = make_uint2(loc | (hi8 << 13), en.y);     // k_ds_resolve's entry
-        na += (uint32_t)__popcll(ma);
-    };
-    // the previous item's stores: k_ds_filter's fixed sequence, every store a range-checked buffer
-    // store (no previous item: all dropped), so the vmcnt queue has the same shape every time
-    auto finish = [&]() {
-        bool ovf = !pfits;
-#pragma unroll
-        for (int u = 0; u < NH; ++u) ovf |= hs[u] > (uint32_t)DS_HCAP;
-        typedef unsigned int u2v __attribute__((ext_vector_type(2)));
-        typedef unsigned int u4v __attribute__((ext_vector_type(4)));
-        {
-            const auto od = __builtin_amdgcn_make_buffer_rsrc(ws.partial + prow * G + pgi, (short)0, pv ? 8 : 0, 0x00020000);
-            const uint64_t ab = __builtin_bit_cast(uint64_t, pa2);
-            const u2v v2 = {(unsigned)ab, (unsigned)(ab >> 32)};
-            __builtin_amdgcn_raw_buffer_store_b64(v2, od, 0, 0, 0);
-        }
-        {
-            const auto od = __builtin_amdgcn_make_buffer_rsrc(ws.itm + pgi * n + prow, (short)0, pv ? 4 : 0, 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b32(ovf ? DS_OVF : na, od, 0, 0, 0);
-        }
-        {
-            // halves past the row end land in the tab's padding rows (G * NH >= H)
-            const uint32_t u = (uint32_t)lane & (NH - 1);
-            uint32_t hc = 0;
-#pragma unroll
-            for (int v = 0; v < NH; ++v) hc = (uint32_t)v == u ? hs[v] : hc;
-            const auto od = __builtin_amdgcn_make_buffer_rsrc(ws.tabs + pgi * NH * n + prow, (short)0,
-                                                              pv ? (int)(((NH - 1) * n + 1) * 8) : 0, 0x00020000);
-            const u2v v2 = {0u, ovf ? 0u : hc};
-            __builtin_amdgcn_raw_buffer_store_b64(v2, od, u * (uint32_t)n * 8u, 0, 0);
-        }
-        {
-            const uint32_t u = (uint32_t)lane >> 4, k8 = ((uint32_t)lane & 15u) * 8u;
-            uint32_t hc = 0;
-#pragma unroll
-            for (int v = 0; v < NH; ++v) hc = (uint32_t)v == u ? hs[v] : hc;
-            const bool put = pv && !ovf && k8 < hc;
-            const uint32_t hstride = (uint32_t)n * (DS_HCAP * 2);               // bytes
-            const auto od = __builtin_amdgcn_make_buffer_rsrc(ws.ent16 + (pgi * NH * n + prow) * DS_HCAP, (short)0,
-                                                              (int)((NH - 1) * hstride + DS_HCAP * 2), 0x00020000);
-            const uint4 v = reinterpret_cast<const uint4*>(s16)[lane];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), od, put ? u * hstride + k8 * 2u : 0x7FFFFFF0u, 0, 0);
-        }
-        {
-            const uint32_t nrec = (pv && !ovf) ? ((na + 1u) & ~1u) * 8u : 0u;
-            const auto od = __builtin_amdgcn_make_buffer_rsrc(ws.enta + prow * ws.cap + pgi * DS_GCAP, (short)0, (int)nrec, 0x00020000);
-            const uint4* sq = reinterpret_cast<const uint4*>(stage[par ^ 1][wv]);
-#pragma unroll
-            for (int k = 0; k < GCAP / 128; ++k) {
-                const uint4 v = sq[k * 64 + lane];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), od, (k * 64 + lane) * 16, 0, 0);
-            }
-        }
-    };
-    while (it < items) {
-        const float qc = sload(ws.qc + row);
-        const uint32_t rk = sload(ws.rk + row);
-        const int64_t gi = c / FGS;
-        const int64_t nit = it + stride;
-        uint32_t cnt = 0;
-        double a2 = 0.0;
-        int64_t nrow = row, nc = c;
-        const uint32_t sla = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) uint2*)stage[par][wv]);
-        na = 0;
-#pragma unroll
-        for (int u = 0; u < NH; ++u) hs[u] = 0;
-#pragma unroll
-        for (int sub = 0; sub < FGS; ++sub, ++c) {
-            const int64_t j0 = c * CHUNK;
-            __amdgpu_buffer_rsrc_t rsn;
-            if (sub + 1 < FGS) {
-                rsn = chunk_rsrc(rows.row_s(row), j0 + CHUNK, d);
-            } else if (nit < items) {
-                int64_t ngi;
-                item_at(nit, nrow, ngi);
-                nc = ngi * FGS;
-                rsn = chunk_rsrc(rows.row_s(nrow), nc * CHUNK, d);
-            } else {
-                rsn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rows.row_s(row)), (short)0, 0, 0x00020000);
-            }
-            uint32_t jb = (uint32_t)lane * 4u + (uint32_t)sub * CHUNK;
-            asm volatile("" : "+v"(jb));
-            const uint32_t gb = lphi + (uint32_t)(c * 1024) * 0x9E3779B1u + rk;
-#pragma unroll
-            for (int L = 0; L < 16; ++L) {
-                const int P = L + RING - 1;
-                ring[P % RING] = P < 16 ? load_q(rs, lane, P) : load_q(rsn, lane, P - 16);
-                const float4 x = ring[L % RING];
-                const uint32_t hg = gmix(gb + (uint32_t)(L * 64) * 0x9E3779B1u);
-                const float vq[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    a2 = fma((double)vq[q], (double)vq[q], a2);
-                    const float hi = (float)((hg >> (8 * q)) & 0xFFu);
-                    const bool f = fmaf(fabsf(vq[q]), qc, hi) > DS_QT;
-                    const uint64_t m = __ballot(f);
-                    if (f) {
-                        const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                        uint32_t sb = sla + min(cnt, (uint32_t)GCAP) * 8u;
-                        asm volatile("" : "+s"(sb));
-                        const uint32_t la = sb + pre * 8u;
-                        asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" ::"v"(la), "v"(jb + (uint32_t)(L * 256 + q)),
-                                     "v"(__float_as_uint(vq[q])) : "memory");
-                    }
-                    cnt += (uint32_t)__popcll(m);
-                }
-                asm volatile("" : "+v"(a2));
-                // the previous item's batches, between load issues (8 points cover GCAP)
-                if ((L & 3) == 1) {
-                    const int b = sub * 4 + (L >> 2);
-                    if ((uint32_t)(b * 64) < pncl) classify(b);
-                }
-            }
-            rs = rsn;
-        }
-        a2 = wave_sum(a2);
-        finish();
-        prow = row; pgi = gi; pfits = cnt <= GCAP; pncl = pfits ? cnt : 0u; pa2 = a2; prk = rk;
-        pq0 = sload(ws.q0 + row); pq1 = sload(ws.q1 + row);
-        pv = true;
-        // the copy-out reads and the classification precede the next item's staging writes
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        par ^= 1;
-        it = nit;
-        row = nrow;
-        c = nc;
-    }
-    // the last item: classify, then its stores
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    na = 0;                                                  // (its staging: buffer par ^ 1)
-#pragma unroll
-    for (int u = 0; u < NH; ++u) hs[u] = 0;
-    for (int b = 0; b < NB; ++b)
-        if ((uint32_t)(b * 64) < pncl) classify(b);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    finish();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1272,8 +953,8 @@ __global__ __launch_bounds__(256) void k_ds_resolve(int64_t n, int64_t r0, int64
 // ------------------------------------------------------------------------------------------
 // Chunk-owner fold.  One wave per half chunk, fp32 LDS tile, rows in order; per row its list
 // (sure + resolved entries: copysign(levels[level], sign) * norm) — the first 64 entries from a
-// ring of AP rows in flight, the rest read in place — or, for DENSE rows, the half chunk of x
-// itself, encoded.  Contributions are W ? w_i * C(x)_j : C(x)_j.
+// 64-row batch's list windows, brought into LDS a batch ahead, the rest read in place — or, for
+// DENSE rows, the half chunk of x itself, encoded.  Contributions are W ? w_i * C(x)_j : C(x)_j.
 // ------------------------------------------------------------------------------------------
 struct DsMeta {
     uint32_t off, cnt;
@@ -1316,58 +997,30 @@ __device__ inline DsMeta ds_meta_raw(const DsWs& ws, int64_t c, int64_t n, int64
     return m;
 }
 
-#ifndef FLC_DS_MASKLD
-#define FLC_DS_MASKLD 0
-#endif
-#ifndef FLC_DS_L1REG
-#define FLC_DS_L1REG 0               // k_ds_accum (FLC_DS_WIDE): level-1 value from a register
-#endif
-#ifndef FLC_DS_LDSADD
-#define FLC_DS_LDSADD 0              // k_ds_accum (FLC_DS_WIDE): tile updates as LDS fp32 adds
-#endif
-#ifndef FLC_DS_WIDE
-#define FLC_DS_WIDE 1                // k_ds_accum (with FLC_DS_RAWRING): 64-row batches of list windows by LDS DMA
-                                     // (round 5: the fold 0.93 -> 0.70-0.73 ms per C4 step, step -0.05 ms, same
-                                     // allocation, profiles/r05/ab_c4_fold.txt)
-#endif
-#ifndef FLC_DS_RAWRING
-#define FLC_DS_RAWRING 1             // k_ds_accum: raw list loads, masked where folded (the fast loop below)
-#endif
 #ifndef FLC_DS_AW
-#define FLC_DS_AW 1                  // waves per fold workgroup (LDS: one 8 KB tile per wave)
+#define FLC_DS_AW 1                  // waves per fold workgroup (LDS: an 8 KB tile and 8 KB of list windows per wave)
 #endif
 constexpr int DS_AW = FLC_DS_AW;
-#ifndef FLC_DS_AWPE
-#define FLC_DS_AWPE 0                // k_ds_accum: minimum waves per SIMD the register allocation targets (0: compiler's choice)
-#endif
-#if FLC_DS_WIDE
 // the compiler's occupancy model of the 16 KB of LDS per wave gives up on any waves-per-EU target
 // (it then takes 400 registers): cap the registers explicitly (4 waves per SIMD: 128)
 #define FLC_DS_ACCUM_ATTR __attribute__((amdgpu_num_vgpr(128)))
-#elif FLC_DS_AWPE > 0
-#define FLC_DS_ACCUM_ATTR __attribute__((amdgpu_waves_per_eu(FLC_DS_AWPE)))
-#else
-#define FLC_DS_ACCUM_ATTR
-#endif
 
 // Folds rows [r0, r0 + rn) into the running sums: the first group starts the tiles at -0, the others
 // continue from `part` (the previous group's tiles); the last group resolves untouched columns
 // over ALL n rows and writes out = sums / wt, the others write their tiles back to `part`.
-// Small workgroups with only the tile in LDS (the dense rows' level table is ws.gtab): up to 19
-// waves per CU for this latency-bound walk (a 4-wave block with the table in LDS fit 3 per CU).
-// The row walk is a ring of AP rows' first 64 entries: row q's slot is refilled with row q + AP
-// as soon as q is folded, so a list load has AP - 1 rows of work in front of it.
+// Small workgroups with only the tile and the list windows in LDS (the dense rows' level table is
+// ws.gtab) for this latency-bound walk.
 // SRC = DiffSrc (the one-read shifted round): every place that reads a row — a dense row's
-// re-encode (in either ring form) and the sign-of-zero pass over the -0 columns — reads a - b.
+// re-encode and the sign-of-zero pass over the -0 columns — reads a - b.
+// AP is only a name now (once a register ring's depth): kept as part of the symbols the profiles and traces name.
 template <bool W, int AP, bool COMPAT, class SRC = RowSrc>
 __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC rows, int64_t n, int64_t r0, int64_t rn, int first, int last,
                                                   int64_t d, DsWs ws, const float* __restrict__ levels, int s,
                                                   const float* __restrict__ w, float wt, float* __restrict__ part,
                                                   float* __restrict__ out, UniformSrc us) {
-    static_assert(64 % AP == 0, "row groups tile the 64-row batch");
     constexpr uint32_t NONE = 0xFFFFFFFFu;
     __shared__ __attribute__((aligned(16))) float tile[DS_AW][HCHUNK];
-    __shared__ __attribute__((aligned(16))) uint16_t dstg[DS_AW][FLC_DS_WIDE ? 8 : 1][FLC_DS_WIDE ? 512 : 1];   // FLC_DS_WIDE: 8 KB per wave
+    __shared__ __attribute__((aligned(16))) uint16_t dstg[DS_AW][8][512];   // a 64-row batch's list windows: 8 KB per wave
     __shared__ float lvl[DS_MAXLEV + 1];
     if (threadIdx.x <= (unsigned)DS_MAXLEV) lvl[threadIdx.x] = (int)threadIdx.x <= s ? levels[threadIdx.x] : 0.f;
     __syncthreads();
@@ -1400,24 +1053,7 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC r
         } else {
             for (int i = lane; i < HCHUNK; i += 64) tl[i] = (first || i >= len) ? -0.f : part[hbase + i];
         }
-        DsMeta cur = ds_meta(ws, h, n, rend, r0 + lane, w), nxt;
-        uint32_t ra[AP];                        // ring: first 64 entries of rows q .. q + AP - 1
-        // a list's 64-entry window never leaves its item's half region (DS_HCAP >= 64): loaded
-        // whole, lanes past the count dropped; an empty list (rows past the end, dense rows) reads
-        // the array's first 64 entries instead
-        auto fetch = [&](const DsMeta& m, int q, int64_t row, int slot) {
-            const uint32_t cnt = __builtin_amdgcn_readlane(m.cnt, q);
-            const uint16_t* p = cnt ? ws.ent16 + (h * n + row) * DS_HCAP : ws.ent16;
-#if FLC_DS_MASKLD
-            // only the lanes of the list's entries load (the region is 256 B, a list ~80 B)
-            uint32_t v = NONE;
-            if ((uint32_t)lane < cnt) v = __builtin_nontemporal_load(p + lane);
-            ra[slot] = v;
-#else
-            const uint32_t v = p[lane];
-            ra[slot] = (uint32_t)lane < cnt ? v : NONE;
-#endif
-        };
+        DsMeta cur = ds_meta_raw(ws, h, n, rend, r0 + lane, w), nxt;
         // (LDS float atomic adds instead of the read-modify-write — one wave's LDS operations run
         // in issue order, so the row order would hold — measured 1.34 against 0.51 ms at C4)
         auto add = [&](uint32_t loc, float t) {
@@ -1431,31 +1067,16 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC r
             pn = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(m.pn), q));
             wi = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(m.w), q));
         };
-        // refill the slot of row q (this batch) with row q + AP (past the batch end: the next
-        // batch's meta; past n: empty lists)
-        auto refill = [&](int q, int64_t i0) {
-            if (q + AP < 64) fetch(cur, q + AP, i0 + q + AP, q % AP);
-            else fetch(nxt, q + AP - 64, i0 + q + AP, q % AP);   // q % AP: static once unrolled
-        };
-#if FLC_DS_RAWRING
-        // Raw ring: row q's slot holds the first 64 u16 of its region, loaded whatever its count
-        // (rows clamped to the array's last row) and masked with the count where the row is
-        // folded.  The refill address thus needs no row state, and no select sits between a load
-        // and its use: each row waits for its own load only (a static vmcnt(AP - 1)).  (The
-        // previous form masked at the load and took a general path inside the same loop: the
-        // compiler copied the ring at the back-edges and waited for the whole ring there.)
-        int64_t b = 0;
-#if FLC_DS_WIDE
-        cur = ds_meta_raw(ws, h, n, rend, r0 + lane, w);
-        const float lv1 = lvl[1];
         // Wide batches through LDS DMA: a 64-row batch's list windows (the first 128 B of each row's
-        // region) are 8 loads of 16 B per lane straight into the wave's 8 KB staging (lane l: row
-        // l / 8 of its 8-row slot, bytes 16 (l % 8) ..; no ring registers), issued a whole batch
-        // ahead.  The compiler waits for every outstanding load before the first staging read
-        // (vmcnt(0): it does not track LDS DMA per slot), so each batch reads all its 64 entries
-        // per lane first, then issues the next batch's 8 loads and its row state, then folds the
-        // 64 rows: each batch's loads have a whole batch of folding to arrive in (the 16-row
-        // register ring waited a memory latency every 16 rows).
+        // region, loaded whatever the row's count, rows clamped to the array's last row, and masked
+        // with the count where the row is folded: the load address needs no row state) are 8 loads
+        // of 16 B per lane straight into the wave's 8 KB staging (lane l: row l / 8 of its 8-row
+        // slot, bytes 16 (l % 8) ..), issued a whole batch ahead.  The compiler waits for every
+        // outstanding load before the first staging read (vmcnt(0): it does not track LDS DMA per
+        // slot), so each batch reads all its 64 entries per lane first, then issues the next
+        // batch's 8 loads and its row state, then folds the 64 rows: each batch's loads have a
+        // whole batch of folding to arrive in.
+        int64_t b = 0;
         auto dma = [&](int64_t row0, int sl) {
             const uint16_t* src = ws.ent16 + (h * n + min(row0 + (lane >> 3), n - 1)) * DS_HCAP + (lane & 7) * 8;
             __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)&dstg[wv][sl][0], 16, 0, 0);
@@ -1491,25 +1112,8 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC r
                     const uint32_t cnt = __builtin_amdgcn_readlane(cur.off, q) + __builtin_amdgcn_readlane(cur.cnt, q);
                     const uint32_t raw = (q & 1) ? (ent2[q >> 1] >> 16) : (ent2[q >> 1] & 0xFFFFu);
                     const uint32_t a = (uint32_t)lane < cnt ? raw : NONE;
-#if FLC_DS_L1REG
-                    // level 1 (every sure entry, most resolved ones) from a register: the row's chain
-                    // keeps one LDS round trip (the tile's) instead of two
-                    float lv = lv1;
-                    if (__builtin_expect(__ballot(a != NONE && ((a >> 12) & 15u) != 1u) != 0ull, 0)) lv = lvl[(a >> 12) & 15u];
-                    const float e = __uint_as_float(__float_as_uint(lv) | ((a & 0x800u) << 20)) * pn;
-#else
                     const float e = value(a, pn);
-#endif
-                    if (a != NONE) {
-                        const float t = W ? wi * e : e;
-#if FLC_DS_LDSADD
-                        // LDS fp32 add without return: one wave's LDS operations run in issue order, so
-                        // each column still takes its rows' terms in row order; no read in the chain
-                        if (!(t == 0.f)) atomicAdd(&tl[a & (HCHUNK - 1)], t);
-#else
-                        add(a & (HCHUNK - 1), t);
-#endif
-                    }
+                    if (a != NONE) add(a & (HCHUNK - 1), W ? wi * e : e);
                 }
             } else {
 #pragma unroll 1
@@ -1535,41 +1139,6 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC r
             }
             cur = nxt;
         }
-#else
-        const uint16_t* hb = ws.ent16 + h * n * DS_HCAP + lane;
-#pragma unroll
-        for (int q = 0; q < AP; ++q) ra[q] = hb[min(r0 + q, n - 1) * DS_HCAP];
-        // 64-row batches (the last one may be partial: its rows past the end have count 0) until
-        // one holds a dense row; from there the rows go one at a time below
-        for (; b < nb; ++b) {
-            const int64_t i0 = r0 + b * 64;
-            if (__ballot((cur.mode & DS_DENSE) != 0u) != 0ull) break;
-            nxt = ds_meta(ws, h, n, rend, i0 + 64 + lane, w);
-#pragma unroll 1
-            for (int qb = 0; qb < 64; qb += AP) {
-#pragma unroll
-                for (int u = 0; u < AP; ++u) {
-                    const int q = qb + u;
-                    float pn, wi;
-                    row_state(cur, q, pn, wi);
-                    const uint32_t cnt = __builtin_amdgcn_readlane(cur.cnt, q);
-                    const uint32_t a = (uint32_t)lane < cnt ? ra[u] : NONE;
-                    const float e = value(a, pn);
-                    if (a != NONE) add(a & (HCHUNK - 1), W ? wi * e : e);
-                    if (__builtin_expect(cnt > 64u, 0)) {             // rare: the rest of a long list
-                        const int64_t row = i0 + q;
-                        for (uint32_t k = 64u + lane; k < cnt; k += 64) {
-                            const uint32_t en = ws.ent16[(h * n + row) * DS_HCAP + k];
-                            const float ev = value(en, pn);
-                            add(en & (HCHUNK - 1), W ? wi * ev : ev);
-                        }
-                    }
-                    ra[u] = hb[min(i0 + q + AP, n - 1) * DS_HCAP];
-                }
-            }
-            cur = nxt;
-        }
-#endif
         // rows from the batch with a dense row on, one at a time (rare: a row outside its sample's
         // norm bounds, an overflowed item, a non-finite row or weight)
         for (int64_t row = r0 + b * 64; row < rend; ++row) {
@@ -1603,91 +1172,6 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC r
                 }
             }
         }
-#else
-#pragma unroll
-        for (int q = 0; q < AP; ++q) fetch(cur, q, r0 + q, q);
-        int64_t b = 0;
-        for (; b < nb; ++b) {
-            const int64_t i0 = r0 + b * 64;
-            nxt = ds_meta(ws, h, n, rend, i0 + 64 + lane, w);
-            // rows of this batch that need the general path: dense, or more than 64 entries here
-            const uint64_t slow = __ballot((i0 + lane < rend) && ((cur.mode & DS_DENSE) || cur.cnt > 64u));
-            if (slow == 0ull && i0 + 64 <= rend) {
-                // straight line: per row its contribution, the add, the slot's refill
-#pragma unroll 1
-                for (int qb = 0; qb < 64; qb += AP) {
-#pragma unroll
-                    for (int u = 0; u < AP; ++u) {
-                        const int q = qb + u;
-                        float pn, wi;
-                        row_state(cur, q, pn, wi);
-                        const uint32_t a = ra[u];
-                        const float e = value(a, pn);
-                        if (a != NONE) add(a & (HCHUNK - 1), W ? wi * e : e);
-                        refill(q, i0);
-                    }
-                }
-            } else {
-                const int nrow = (int)min((int64_t)64, rend - i0);
-#pragma unroll 1
-                for (int q = 0; q < 64; ++q) {
-                    const int u = q % AP;
-                    uint32_t a = NONE;
-#pragma unroll
-                    for (int z = 0; z < AP; ++z)
-                        if (z == u) a = ra[z];
-                    if (q < nrow) {
-                        const int64_t row = i0 + q;
-                        float pn, wi;
-                        row_state(cur, q, pn, wi);
-                        const uint32_t mode = __builtin_amdgcn_readlane(cur.mode, q);
-                        if (mode & DS_DENSE) {
-                            // dense row: every element of the half chunk, coalesced
-                            DsRow rr;
-                            rr.n = pn;
-                            rr.rn = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(cur.rpn), q));
-                            const uint32_t rk = __builtin_amdgcn_readlane(cur.rk, q);
-                            rr.rk2 = rk ^ 0x27D4EB2Fu;
-                            rr.fast = (mode & DS_FAST) != 0u;
-                            const auto rp = row_ref(rows, row);
-                            for (int k = 0; k < HCHUNK / 64; ++k) {
-                                const uint32_t e = (uint32_t)(k * 64 + lane);
-                                if (e < (uint32_t)len) {
-                                    const uint32_t j = hbase + e;
-                                    const float xv = rp[(int64_t)hbase + e];
-                                    const float ev = COMPAT ? ds_encode<true>(xv, j, 0u, us.u[row * us.uld + j], rr, tab, s, sf)
-                                                            : ds_encode<false>(xv, j, ds_hi8(j, rk), 0.0, rr, tab, s, sf);
-                                    add(e, W ? wi * ev : ev);
-                                }
-                            }
-                        } else {
-                            if (a != NONE) {
-                                const float e = value(a, pn);
-                                add(a & (HCHUNK - 1), W ? wi * e : e);
-                            }
-                            const uint32_t cnt = __builtin_amdgcn_readlane(cur.cnt, q);
-                            for (uint32_t e = 64u + lane; e < cnt; e += 64) {
-                                const uint32_t en = ws.ent16[(h * n + row) * DS_HCAP + e];
-                                const float ev = value(en, pn);
-                                add(en & (HCHUNK - 1), W ? wi * ev : ev);
-                            }
-                        }
-                    }
-                    // refill the slot with row q + AP (dynamic slot: the loop is not unrolled)
-                    const bool nb_ = q + AP >= 64;
-                    const int qq = nb_ ? q + AP - 64 : q + AP;
-                    const uint32_t cnt = __builtin_amdgcn_readlane(nb_ ? nxt.cnt : cur.cnt, qq);
-                    const int64_t rown = i0 + q + AP;
-                    const uint16_t* p = cnt ? ws.ent16 + (h * n + rown) * DS_HCAP : ws.ent16;
-                    const uint32_t v = (uint32_t)lane < cnt ? (uint32_t)p[lane] : NONE;
-#pragma unroll
-                    for (int z = 0; z < AP; ++z)
-                        if (z == u) ra[z] = v;
-                }
-            }
-            cur = nxt;
-        }
-#endif
         if (!last) {
             for (int64_t i = lane; i < len; i += 64) part[hbase + i] = tl[i];
             continue;
@@ -1719,9 +1203,6 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC r
 // Filter grid.  The product build always takes the default; a -DFLC_TUNING build reads the
 // A/B switches once per process (FLC_DS_GRID=res launches a resident-only grid; FLC_DS_GRIDPCT=p
 // caps it at p % of the resident blocks when row groups run).
-#ifndef FLC_DS_V2
-#define FLC_DS_V2 0                  // device-RNG filter: classification pipelined into the next item (k_ds_filter2)
-#endif
 #ifndef FLC_DS_LDSPAD
 #define FLC_DS_LDSPAD 5120           // row groups: extra LDS per filter block (bytes), room for the side tail
 #endif
@@ -1729,9 +1210,6 @@ __global__ __launch_bounds__(64 * DS_AW) FLC_DS_ACCUM_ATTR void k_ds_accum(SRC r
 #define FLC_DS_LASTPCT 100           // size of the last QSGD row group in % of the others (its tail is exposed)
 #endif
 static_assert(FLC_DS_LASTPCT >= 1 && FLC_DS_LASTPCT <= 100, "FLC_DS_LASTPCT: the last row group is 1..100 % of the others");
-#ifndef FLC_DS_RG_SIDE
-#define FLC_DS_RG_SIDE 1             // row groups: norm + resolve on the side stream too
-#endif
 #ifndef FLC_DS_RESGRID
 #define FLC_DS_RESGRID 0             // k_ds_filter: a resident grid (one round of blocks, grid-stride items)
 #endif
@@ -1744,9 +1222,6 @@ static_assert(FLC_DS_LASTPCT >= 1 && FLC_DS_LASTPCT <= 100, "FLC_DS_LASTPCT: the
 #ifndef FLC_DS_PROBE_SIDE
 #define FLC_DS_PROBE_SIDE 0          // A/B probes: 1 skip the side resolve, 2 the side fold, 3 both (outputs NOT valid)
 #endif
-#ifndef FLC_DS_PROBE_DEF
-#define FLC_DS_PROBE_DEF 0           // A/B variant builds only (a probe's outputs are NOT valid)
-#endif
 #ifndef FLC_DS_TNSUMS
 // torch-order norm mode: 1 = the filter emits the torch lanes' sums (the rows are read twice:
 // filter + k_tn_maps), 0 = the three-read composition (k_tn_sums reads them once more; the
@@ -1756,7 +1231,7 @@ static_assert(FLC_DS_LASTPCT >= 1 && FLC_DS_LASTPCT <= 100, "FLC_DS_LASTPCT: the
 struct DsVariant { bool resident; int gridpct; int probe; int64_t rb; int cring; bool tnsums; };
 static const DsVariant& ds_variant() {
     static const DsVariant v = [] {
-        DsVariant r{false, 100, FLC_DS_PROBE_DEF, DS_RB, DS_RINGC, FLC_DS_TNSUMS != 0};
+        DsVariant r{false, 100, 0, DS_RB, DS_RINGC, FLC_DS_TNSUMS != 0};
         if (const char* e = tuning_env("FLC_DS_TNSUMS")) r.tnsums = atoi(e) != 0;
         if (const char* e = tuning_env("FLC_DS_CRING")) r.cring = atoi(e);
         if (const char* e = tuning_env("FLC_DS_RB")) r.rb = std::max<int64_t>(1, atoll(e));
@@ -1766,6 +1241,35 @@ static const DsVariant& ds_variant() {
         return r;
     }();
     return v;
+}
+
+// The filter kernel of a call.  The product library carries five: device draws (ring 16) and the
+// caller's uniforms (ring DS_RINGC), each with and without the torch lanes' sums, and the
+// two-operand one.  The cost probes and the 8-deep compat ring are chosen by switches that only a
+// -DFLC_TUNING build reads, so only that build instantiates them.
+template <class SRC>
+using DsFilterKernel = void (*)(SRC, int64_t, int64_t, int64_t, int64_t, int64_t, DsWs, UniformSrc);
+template <class SRC>
+static DsFilterKernel<SRC> ds_filter_kernel(const DsVariant& v, bool compat, bool tns) {
+    if constexpr (std::is_same<SRC, DiffSrc>::value) {
+        return k_ds_filter<8, DS_GCAP, 0, false, false, DiffSrc>;          // 8 pairs: the 16-float4 ring's bytes
+    } else {
+#ifdef FLC_TUNING
+        if (compat && v.cring == 8) return tns ? k_ds_filter<8, DS_GCAP, 0, true, true> : k_ds_filter<8, DS_GCAP, 0, true>;
+        if (!compat && !tns) {
+            switch (v.probe) {
+            case 1: return k_ds_filter<16, DS_GCAP, 1>;
+            case 2: return k_ds_filter<16, DS_GCAP, 2>;
+            case 3: return k_ds_filter<16, DS_GCAP, 3>;
+            case 4: return k_ds_filter<16, DS_GCAP, 4>;
+            case 5: return k_ds_filter<16, DS_GCAP, 5>;
+            case 6: return k_ds_filter<16, DS_GCAP, 6>;
+            }
+        }
+#endif
+        if (compat) return tns ? k_ds_filter<DS_RINGC, DS_GCAP, 0, true, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true>;
+        return tns ? k_ds_filter<16, DS_GCAP, 0, false, true> : k_ds_filter<16, DS_GCAP>;
+    }
 }
 
 // tn (the torch-order norm mode): the filter's per-lane sums and torch_norm.hip's workspace
@@ -1818,7 +1322,7 @@ bool ds_eligible(const flc_codec_params* prm, const flc_pattern* pat, int64_t n,
     const int m = prm->flags & FLC_PATH_MASK;
     if (m) return m == FLC_PATH_SPARSE;
     const double share = 1.1 * (double)prm->s / sqrt((double)d) + 0.003;
-    return share * DS_FGS * CHUNK <= (FLC_DS_V2 ? FLC_DS2_CAP : DS_GCAP) / 1.4;
+    return share * DS_FGS * CHUNK <= DS_GCAP / 1.4;
 }
 
 size_t ds_workspace(const flc_codec_params* prm, int64_t n, int64_t d, int norm_mode) {
@@ -1838,13 +1342,6 @@ struct DsCtx {
 std::mutex g_ds_mu;
 std::map<int, DsCtx> g_ds_ctx;
 }  // namespace
-
-// Row groups whose norm + resolve overlap the next group's filter (one fold at the end): tuning
-// builds FLC_DS_TAILOV=g, else 1
-static int tail_groups(int64_t n) {
-    static const int g = [] { const char* e = tuning_env("FLC_DS_TAILOV"); return e ? std::max(1, atoi(e)) : 1; }();
-    return (int)std::max<int64_t>(1, std::min<int64_t>(g, n));
-}
 
 // Row groups of the pipeline: the caller's hint (FLC_ROW_GROUPS(g) in flags), else 2 for 128 rows
 // or more.  Group g's norm, resolve and fold run on the side stream under group g + 1's filter,
@@ -1889,19 +1386,7 @@ static int ds_run_t(const flc_codec_params* prm, const flc_pattern* pat, SRC row
     auto filter = [&](int64_t r0, int64_t rn, hipStream_t s2 = nullptr, bool beside = false) -> int {
         // s2: the row group's norm / resolve go to this stream (after an event on st), under the
         // next group's filter
-        auto kern = [&] {
-            if constexpr (DIFF) {
-                return k_ds_filter<8, DS_GCAP, 0, false, false, DiffSrc>;      // 8 pairs: the 16-float4 ring's bytes
-            } else {
-                return tns ? (!compat ? k_ds_filter<16, DS_GCAP, 0, false, true>
-                                      : v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true, true>)
-                     : compat ? (v.cring == 8 ? k_ds_filter<8, DS_GCAP, 0, true> : k_ds_filter<DS_RINGC, DS_GCAP, 0, true>)
-                     : v.probe == 1 ? k_ds_filter<16, DS_GCAP, 1> : v.probe == 2 ? k_ds_filter<16, DS_GCAP, 2>
-                     : v.probe == 3 ? k_ds_filter<16, DS_GCAP, 3> : v.probe == 4 ? k_ds_filter<16, DS_GCAP, 4>
-                     : v.probe == 5 ? k_ds_filter<16, DS_GCAP, 5> : v.probe == 6 ? k_ds_filter<16, DS_GCAP, 6>
-                     : FLC_DS_V2 ? k_ds_filter2<16, FLC_DS2_CAP> : k_ds_filter<16, DS_GCAP>;
-            }
-        }();
+        const auto kern = ds_filter_kernel<SRC>(v, compat, tns);
         int gw = (int)std::max<int64_t>(1, std::min<int64_t>((rn * ws.G + 3) / 4, 32768));
         // row groups (s2: the group's tail runs beside the next group's filter): the filter's
         // blocks reserve FLC_DS_LDSPAD more bytes of LDS, so one block fewer fits a CU and the
@@ -1980,13 +1465,12 @@ static int ds_run_t(const flc_codec_params* prm, const flc_pattern* pat, SRC row
         FLC_CHECK_LAUNCH("k_ds_sample");
         return FLC_OK;
     };
-    const int TO = tail_groups(n);
     // row groups (K >= 2): only group 0's sample before its filter; the other rows' samples run on
     // the side stream beside it and group 1's filter waits for them
     const bool split = FLC_DS_SPLIT_SAMPLE && K >= 2;
     if (!split)
         if (int rc = sample(0, n, st)) return rc;
-    if (K == 1 && TO <= 1) {
+    if (K == 1) {
         int rc = filter(0, n);
         if (rc) return rc;
         return accum(0, n, 1, 1, st);
@@ -2004,26 +1488,14 @@ static int ds_run_t(const flc_codec_params* prm, const flc_pattern* pat, SRC row
         FLC_CHECK_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
         FLC_CHECK_HIP(hipStreamCreateWithPriority(&cx.side, hipStreamNonBlocking, hi));
     }
-    while ((int)cx.ev.size() < std::max(K, TO) + 4) {
+    // events: [0, K) a group's filter, K the join, K + 2 and K + 3 the split sample
+    // (a stream's events are reused in order: a record after the wait that consumed it)
+    while ((int)cx.ev.size() < K + 4) {
         hipEvent_t e;
         FLC_CHECK_HIP(hipEventCreateWithFlags(&e, FLC_SYNC_EVENT_FLAGS));
         cx.ev.push_back(e);
     }
-    if (K == 1) {
-        // Tail overlap: row group g's norm and resolve (latency-bound, little memory traffic) run on
-        // the side stream under the filter of group g + 1; one fold of all rows at the end.
-        // (A stream's events are reused in order: a record after the wait that consumed it.)
-        for (int g = 0; g < TO; ++g) {
-            const int64_t r0 = n * g / TO, r1 = n * (g + 1) / TO;
-            filt_ev = cx.ev[g];
-            int rc = filter(r0, r1 - r0, cx.side);
-            if (rc) return rc;
-        }
-        FLC_CHECK_HIP(hipEventRecord(cx.ev[TO], cx.side));
-        FLC_CHECK_HIP(hipStreamWaitEvent(st, cx.ev[TO], 0));
-        return accum(0, n, 1, 1, st);
-    }
-    const int EV_S0 = std::max(K, TO) + 2, EV_S1 = EV_S0 + 1;
+    const int EV_S0 = K + 2, EV_S1 = EV_S0 + 1;
     if (split) {
         const int64_t rs1 = group_row(n, K, 1, FLC_DS_LASTPCT);
         FLC_CHECK_HIP(hipEventRecord(cx.ev[EV_S0], st));                   // after the work queued before
@@ -2035,19 +1507,10 @@ static int ds_run_t(const flc_codec_params* prm, const flc_pattern* pat, SRC row
     for (int g = 0; g < K; ++g) {
         const int64_t r0 = group_row(n, K, g, FLC_DS_LASTPCT), r1 = group_row(n, K, g + 1, FLC_DS_LASTPCT);
         if (split && g == 1) FLC_CHECK_HIP(hipStreamWaitEvent(st, cx.ev[EV_S1], 0));
-        int rc;
-        if (FLC_DS_RG_SIDE) {
-            // the group's whole tail (norm, resolve, fold) on the side stream, under the next
-            // group's filter
-            filt_ev = cx.ev[g];
-            rc = filter(r0, r1 - r0, cx.side, g < K - 1);
-        } else {
-            rc = filter(r0, r1 - r0);
-            if (!rc) {
-                FLC_CHECK_HIP(hipEventRecord(cx.ev[g], st));
-                FLC_CHECK_HIP(hipStreamWaitEvent(cx.side, cx.ev[g], 0));
-            }
-        }
+        // the group's whole tail (norm, resolve, fold) on the side stream, under the next
+        // group's filter
+        filt_ev = cx.ev[g];
+        int rc = filter(r0, r1 - r0, cx.side, g < K - 1);
         if (rc) return rc;
         if (!(g < K - 1 && (FLC_DS_PROBE_SIDE & 2)))         // probe builds only (outputs NOT valid)
             rc = accum(r0, r1 - r0, g == 0, g == K - 1, cx.side, g < K - 1);

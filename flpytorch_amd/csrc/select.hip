@@ -89,7 +89,7 @@ static int lone_path() {           // tuning runs: env FLC_LONE_PATH overrides
 // (measured at C3, same box, two runs each: 8.18 ms / step with 1 group, 8.15 with 2, 8.00-8.01
 // with 4, 8.04 with 8; profiles/r03/ab_tailov.txt); tuning builds FLC_TK_TAILOV=g.  (The same
 // overlap of the sparse QSGD norm + resolve lost at C4, 10.20 -> 10.27-10.44 ms: its filter split
-// in groups runs slower; it stays a tuning knob there, FLC_DS_TAILOV.)
+// in groups runs slower, and dither_sparse.hip no longer carries it.)
 static int tk_tail_groups(const flc_codec_params* prm, int64_t n) {
     static const int g = [] { const char* e = tuning_env("FLC_TK_TAILOV"); return e ? std::max(1, atoi(e)) : 4; }();
     const int hint = (prm->flags >> 8) & 0xFF;                       // FLC_ROW_GROUPS(g): the caller's

@@ -307,11 +307,11 @@ def test_sparse_dither_item_near_staging_capacity(ag, monkeypatch, big):
 
 @pytest.mark.parametrize("many", [9, 10, 11, 12, 40, 128])
 def test_sparse_dither_lane_overflow(ag, monkeypatch, many):
-    """Per-lane candidate staging (each lane of the filter's wave appends to its own column,
-    DS_PLS = 10 slots per item): `many` sure candidates among the 128 elements one lane reads in
-    an item (lane 5: elements 4*5 + 256 L + q of each chunk; lane 40 gets many // 2), the rest
-    small.  Past 10 the lane's extra candidates are re-read and appended after the compaction;
-    bit-exact vs the oracle either way (and with the pooled staging of other builds)."""
+    """Candidates concentrated in one lane of the filter's wave: `many` sure candidates among the
+    128 elements one lane reads in an item (lane 5: elements 4*5 + 256 L + q of each chunk; lane
+    40 gets many // 2), the rest small.  The sizes straddle 10, the per-lane capacity of a retired
+    staging layout that gave each lane its own column; the wave's pooled staging has no per-lane
+    limit.  Bit-exact vs the oracle."""
     n, d, client0, spec = 3, 16384, 7, "qsgd:127"
     g = np.random.default_rng(many)
     rows = (g.standard_normal((n, d)) * 1e-3).astype(np.float32)
