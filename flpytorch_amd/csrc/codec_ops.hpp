@@ -185,7 +185,10 @@ struct DitherOp {
         int g = (int)(y * sf);                                 // y >= 0; NaN -> 0
         g = g > s - 1 ? s - 1 : g;
         float4 t = tab[g];
-        const bool below = y < t.x, above = y > t.y;
+        // y ON the upper level belongs to the next interval (the reference's loop visits the
+        // intervals in order and the later one overwrites: compressors.py:284-291); there p = 1, so
+        // the two choices differ only for a draw >= 1, which the reference then sends one level up
+        const bool below = y < t.x, above = y >= t.y;
         if (below | above) {                                   // std levels RN(k/s): at most one off
             g = below ? (g > 0 ? g - 1 : 0) : (g < s - 1 ? g + 1 : g);
             t = tab[g];
@@ -197,8 +200,12 @@ struct DitherOp {
         const float p2 = (F || t.w != 0.f) ? div_fast(num, dd) : num / t.z;      // p * 2^32
         const bool down = draw_below<COMPAT>(urow, rk, j, cs, hg_of<COMPAT>(rk, j), COMPAT ? ldexpf(p2, -32) : 0.f, p2);
         const float lev = in ? (down ? t.x : t.y) : 0.f;
-        // (lev * sign(x)) * pnorm with out[x == 0] = 0 (compressors.py:294-296)
-        return (x == 0.f) ? 0.f : copysignf(lev, x) * dn.b;
+        // (lev * sign(x)) * pnorm with out[x == 0] = 0 (compressors.py:294-296).  The sign by compare,
+        // not copysignf: torch.sign(NaN) is 0, so a NaN element under a finite given norm is +0
+        // (lev is 0 there: NaN lies in no interval), whatever the NaN's sign bit.  The zero of
+        // x == 0 is multiplied by the norm like every level: 0 * 0 * pnorm is NaN under an inf or
+        // NaN norm
+        return ((x == 0.f) ? 0.f : (x < 0.f ? -lev : lev)) * dn.b;
     }
     // NE elements, written stage by stage (each step for all elements before the next) so the NE
     // dependency chains are interleaved in the instruction stream; one fix-up branch at the end.
@@ -219,7 +226,7 @@ struct DitherOp {
         }
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
-            fix[e] = (y[e] < t[e].x) | !(y[e] <= t[e].y);
+            fix[e] = (y[e] < t[e].x) | !(y[e] < t[e].y);          // (on the upper level: the next interval's)
             FastDiv dd;
             dd.b = t[e].z; dd.rb = t[e].w; dd.ok = true;
             const float num = y[e] - t[e].y;
@@ -234,7 +241,7 @@ struct DitherOp {
             const bool down = (COMPAT && uv) ? uv[e] < (double)ldexpf(p2[e], -32)
                                              : draw_below<COMPAT>(urow, rk, jv[e], cs[e], hg[e / 4], COMPAT ? ldexpf(p2[e], -32) : 0.f, p2[e]);
             const float lev = down ? t[e].x : t[e].y;
-            out[e] = (x[e] == 0.f) ? 0.f : copysignf(lev, x[e]) * dn.b;
+            out[e] = ((x[e] == 0.f) ? 0.f : (x[e] < 0.f ? -lev : lev)) * dn.b;
             any |= fix[e];
         }
         if (any) {

@@ -753,7 +753,7 @@ __device__ inline DsLev ds_level(float x, uint32_t j, uint32_t hi8, double ud, c
     int g = (int)(y * sf);                                        // y >= 0; NaN -> 0
     g = g > s - 1 ? s - 1 : g;
     float4 t = tab[g];
-    const bool off = (y < t.x) | (y > t.y);
+    const bool off = (y < t.x) | (y >= t.y);                      // on the upper level: the next interval's
     if (__builtin_expect(__ballot(off) != 0ull, 0)) {            // std levels RN(k/s): at most one off
         if (off) {
             g = (y < t.x) ? (g > 0 ? g - 1 : 0) : (g < s - 1 ? g + 1 : g);
@@ -795,7 +795,8 @@ template <bool COMPAT>
 __device__ inline float ds_encode(float x, uint32_t j, uint32_t hi8, double ud, const DsRow& r, const float4* tab, int s,
                                   float sf) {
     const DsLev l = ds_level<COMPAT>(x, j, hi8, ud, r, tab, s, sf);
-    return (x == 0.f) ? 0.f : copysignf(l.v, x) * r.n;
+    // the sign by compare and the zero times the norm, as DitherOp::apply
+    return ((x == 0.f) ? 0.f : (x < 0.f ? -l.v : l.v)) * r.n;
 }
 
 

@@ -142,7 +142,10 @@ int flc_reduce_matrix(const float* d_rows, int64_t ld, int64_t n, int64_t d, con
  * Single-vector encode — Compressor.compressVector(x) (compressors.py:218-371): dense fp32
  * output `d_out[d]` (zeros where the codec sends nothing).  `row` selects pattern row 0.
  *   d_pnorm_in : dithering only — device fp32 norm to use instead of computing one (the norm
- *                the server receives on the wire), or NULL
+ *                the server receives on the wire), or NULL.  A NaN element under a finite given
+ *                norm encodes to +0, the reference's bits (torch.sign(NaN) is 0), whatever the
+ *                NaN's sign; an element above the norm (y > 1) lies in no interval: +-0.  Under
+ *                an inf or NaN norm every element is NaN, zeros included (0 * 0 * pnorm)
  *   d_pnorm_out: dithering only — device fp32 where the norm used is written, or NULL
  * -------------------------------------------------------------------------------------- */
 size_t flc_encode_workspace_size(const flc_codec_params* prm, int64_t d);
@@ -446,9 +449,13 @@ int flc_dither_row_flags(int64_t n, int64_t d, const void* d_ws, size_t ws_bytes
  *                                                          padded — K' (A + B) values, count = K'
  *                                                          (decoded by the encode's own GEMM)
  * Level code 0 is +0; otherwise value = (levels[idx] * sign) * norm (compressors.py:294-296).
- * flc_unpack(flc_pack(x)) == flc_encode(x) bit for bit; flc_unpack_reduce(payloads) ==
- * flc_encode_reduce(rows).  flc_pack runs the encode (same patterns and draws as flc_encode)
- * and derives the codes from its output.  Payloads are 16-byte aligned; strided payload rows
+ * flc_unpack(flc_pack(x)) == flc_encode(x) bit for bit at every element that is not a NaN; a NaN
+ * element of flc_encode(x) decodes to a NaN (NAT16 and the level codes carry "a NaN", not its
+ * bits: 0x7FFF decodes to 0x7FC00000, and a level code's NaN is -0 * norm of a non-finite norm).
+ * flc_unpack_reduce(payloads) == flc_encode_reduce(rows) in the same sense.  flc_pack runs the
+ * encode (same patterns and draws as flc_encode) and derives the codes from its output (an
+ * element x == 0 under an inf or NaN norm is a NaN there, 0 * norm, not code 0).
+ * Payloads are 16-byte aligned; strided payload rows
  * (d_payloads + i * ld_bytes, ld_bytes >= flc_payload_bytes, a multiple of 16) or a device
  * array of payload pointers.
  * -------------------------------------------------------------------------------------- */

@@ -18,6 +18,9 @@ fp32 semantics reproduced (checked against tests/golden/ fixtures from the real 
     (compressors.py:288);  later level intervals overwrite earlier ones (290-291);
   * ``out * sign * pnorm`` is evaluated left to right in fp32 (296);
   * natural dithering returns ``y * sign * pnorm`` — the reference's own bug (326);
+  * ``torch.pow(2, e)`` is exact for integral e (``_pow2``; np.exp2 is not: 2^127 comes out one ulp
+    high) and ``torch.sign(NaN)`` is 0 (``_sign``; np.sign gives NaN) — pinned at subnormals, every
+    power of two, +-inf, NaN and given norms by tests/test_oracle_edges.py (tests/golden/edges.*);
   * torch's CPU ``norm`` sums in its own fp32 order (14 616 ulp from the exact value at
     D = 25 M); the oracle computes the norm exactly (float64 accumulation, one rounding) unless
     the caller passes a value — the reference's, or oracle/torch_norm.c's restatement of torch's
@@ -49,6 +52,24 @@ def _levels_nat(levels):
     for i in range(levels):
         v[i] = _F32(0.5 ** i)
     return v[::-1].copy()
+
+
+def _pow2(e):
+    """torch.pow(2, e) for an fp32 e that is integral, +-inf or NaN (compressors.py:255, 262-263):
+    the exact power of two, subnormal results and 2^128 = inf included; inf -> inf, -inf -> 0,
+    NaN -> NaN.  (np.exp2 is one ulp off at some integral exponents, e.g. 2^127.)"""
+    e = np.asarray(e, dtype=_F32)
+    fin = np.isfinite(e)
+    k = np.where(fin, np.clip(e, -200.0, 200.0), 0.0).astype(np.int32)
+    with np.errstate(all="ignore"):
+        p = np.ldexp(_F32(1), k).astype(_F32)
+    rest = np.where(np.isnan(e), _F32(np.nan), np.where(e > 0, _F32(np.inf), _F32(0))).astype(_F32)
+    return np.where(fin, p, rest).astype(_F32)
+
+
+def _sign(x):
+    """torch.sign: -1, 0 or 1, and 0 for NaN (np.sign gives NaN there)."""
+    return np.where(np.isnan(x), _F32(0), np.sign(x)).astype(_F32)
 
 
 class OracleCompressor:
@@ -133,13 +154,33 @@ class OracleCompressor:
             self.testp = rs.rand(self.D)
 
     def norm(self, x):
-        if self.p == math.inf:
-            return _F32(np.max(np.abs(x))) if x.size else _F32(0)
-        if self.p == 2:
-            return _F32(np.sqrt(np.sum(x.astype(np.float64) ** 2)))
-        if self.p == 1:
-            return _F32(np.sum(np.abs(x).astype(np.float64)))
-        return _F32(np.sum(np.abs(x).astype(np.float64) ** self.p) ** (1.0 / self.p))
+        with np.errstate(all="ignore"):              # (a norm may overflow fp32 to inf: that is its value)
+            if self.p == math.inf:
+                return _F32(np.max(np.abs(x))) if x.size else _F32(0)
+            if self.p == 2:
+                return _F32(np.sqrt(np.sum(x.astype(np.float64) ** 2)))
+            if self.p == 1:
+                return _F32(np.sum(np.abs(x).astype(np.float64)))
+            return _F32(np.sum(np.abs(x).astype(np.float64) ** self.p) ** (1.0 / self.p))
+
+    def probability(self, x, pnorm=None):
+        """The fp32 probability each element's draw is compared with (``testp < p``,
+        compressors.py:260 and 288; dithering: in the interval that decides the element, see
+        dither_levels).  Tests place uniforms at and next to it."""
+        x = np.asarray(x, dtype=_F32)
+        with np.errstate(all="ignore"):
+            if self.type == NATURAL:
+                ax = np.abs(x)
+                alpha = np.log2(ax)
+                return ((_pow2(np.ceil(alpha)) - ax) / _pow2(np.floor(alpha))).astype(_F32)
+            if self.type in (STD_DITHERING, NAT_DITHERING):
+                pn = self.norm(x) if pnorm is None else _F32(pnorm)
+                y = np.abs(x) / pn
+                lv = self.levels
+                S = len(lv) - 1
+                s = np.clip(np.searchsorted(lv, y, side="right").astype(np.int64) - 1, 0, S - 1)
+                return ((y - lv[s + 1]) / (lv[s] - lv[s + 1])).astype(_F32)
+        raise NotImplementedError(f"codec {self.type} draws no per-element uniform")
 
     # compressors.py:218-371
     def compress(self, x, pnorm=None):
@@ -161,11 +202,11 @@ class OracleCompressor:
                 need = self.K
             elif t == NATURAL:
                 out = np.zeros_like(x)
-                sign = np.sign(x)
+                sign = _sign(x)
                 ax = np.abs(x)
                 alpha = np.log2(ax)
                 lo, hi = np.floor(alpha), np.ceil(alpha)
-                p_lo, p_hi = np.exp2(lo), np.exp2(hi)
+                p_lo, p_hi = _pow2(lo), _pow2(hi)
                 pt = (p_hi - ax) / p_lo
                 down = self.testp < pt.astype(np.float64)
                 out[down] = (sign * p_lo)[down]
@@ -174,7 +215,7 @@ class OracleCompressor:
                 need = 9.0 / 32.0 * d
             elif t in (STD_DITHERING, NAT_DITHERING):
                 pn = self.norm(x) if pnorm is None else _F32(pnorm)
-                sign = np.sign(x)
+                sign = _sign(x)
                 y = np.abs(x) / pn
                 lv = self.levels
                 u = self.testp
