@@ -43,6 +43,7 @@ EXPORTS = [
     "flc_randk_shift_reduce_workspace_size", "flc_randk_shift_reduce",
     "flc_topk_shift_reduce_workspace_size", "flc_topk_shift_reduce",
     "flc_dither_shift_reduce_workspace_size", "flc_dither_shift_reduce", "flc_dither_row_flags",
+    "flc_frecon_reduce_workspace_size", "flc_frecon_reduce",
     "flc_payload_bytes", "flc_payload_format", "flc_payload_validate", "flc_pack_workspace_size", "flc_pack", "flc_unpack",
     "flc_unpack_reduce_workspace_size", "flc_unpack_reduce",
     "flc_pack_shift_workspace_size", "flc_pack_shift",
@@ -96,6 +97,27 @@ class FlcShiftRows(ctypes.Structure):
         ("shift_alpha", ctypes.c_float),
         ("d_shift_in", ctypes.c_void_p), ("ldin", ctypes.c_int64),
         ("d_shift_out", ctypes.c_void_p), ("ldout", ctypes.c_int64),
+    ]
+
+
+class FlcFreconRows(ctypes.Structure):
+    """flc_frecon_rows: the row operands of flc_frecon_reduce (gradients, shifts updated in place,
+    gradients at the previous iterate), row i of each at ptr + i * ld."""
+    _fields_ = [
+        ("d_a", ctypes.c_void_p), ("lda", ctypes.c_int64),
+        ("d_h", ctypes.c_void_p), ("ldh", ctypes.c_int64),
+        ("d_p", ctypes.c_void_p), ("ldp", ctypes.c_int64),
+        ("shift_alpha", ctypes.c_float),
+    ]
+
+
+class FlcFreconServer(ctypes.Structure):
+    """flc_frecon_server: the optional server tail of flc_frecon_reduce, every operand a [d] vector."""
+    _fields_ = [
+        ("d_g_server_prev", ctypes.c_void_p), ("d_h_prev", ctypes.c_void_p),
+        ("lambda_", ctypes.c_float), ("one_minus_lambda", ctypes.c_float),
+        ("d_result", ctypes.c_void_p),
+        ("alpha_update", ctypes.c_float), ("d_h_prev_out", ctypes.c_void_p),
     ]
 
 
@@ -209,6 +231,11 @@ def _bind(lib):
         lib.flc_dither_shift_reduce.argtypes = [P(FlcCodecParams), P(FlcPattern), P(FlcShiftRows), i64, i64, vp, f32,
                                                 vp, vp, vp, sz, vp]
         lib.flc_dither_row_flags.argtypes = [i64, i64, vp, sz, vp, vp]
+    if hasattr(lib, "flc_frecon_reduce"):           # (absent from A/B builds of older revisions)
+        lib.flc_frecon_reduce_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_frecon_reduce_workspace_size.restype = sz
+        lib.flc_frecon_reduce.argtypes = [P(FlcCodecParams), P(FlcPattern), P(FlcFreconRows), i64, i64, vp, f32,
+                                          vp, vp, vp, vp, P(FlcFreconServer), vp, sz, vp]
     lib.flc_payload_bytes.argtypes = [P(FlcCodecParams), i64]
     lib.flc_payload_bytes.restype = i64
     lib.flc_payload_format.argtypes = [P(FlcCodecParams)]
@@ -267,7 +294,7 @@ def _bind(lib):
                         "flc_encode_reduce_ex_workspace_size", "flc_encode_shift_workspace_size",
                         "flc_encode_shift_reduce_workspace_size", "flc_randk_shift_reduce_workspace_size",
                         "flc_topk_shift_reduce_workspace_size", "flc_dither_shift_reduce_workspace_size",
-                        "flc_payload_bytes", "flc_pack_workspace_size",
+                        "flc_frecon_reduce_workspace_size", "flc_payload_bytes", "flc_pack_workspace_size",
                         "flc_pack_shift_workspace_size", "flc_unpack_shift_reduce_workspace_size",
                         "flc_unpack_reduce_workspace_size", "flc_combine_workspace_size",
                         "flc_combine_blocks_workspace_size", "flc_device_randk_counts_workspace_size",

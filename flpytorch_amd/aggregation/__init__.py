@@ -7,11 +7,11 @@ classes whose reduction is the shared sequential fold (algorithms.py:1753-1768),
 """
 from .compressors import (Compressor, CompressorType, initCompressor, stream_choice, stream_rand,  # noqa: F401
                           stream_random, stream_randint31)
-from .fused import (PayloadReducer, ShiftPayloadReducer, ShiftUplinkReducer, UplinkReducer,  # noqa: F401
-                    select_row_flags)
+from .fused import (FreconUplinkReducer, PayloadReducer, ShiftPayloadReducer, ShiftUplinkReducer,  # noqa: F401
+                    UplinkReducer, select_row_flags)
 from .mixed import MixedUplink  # noqa: F401
-from .shift import (dianaStep, dianaStepWire, dianaUplink, ef21Step, ef21StepWire, ef21Uplink, marinaStep,  # noqa: F401
-                    marinaStepWire, marinaUplink)
+from .shift import (cofigStep, cofigUplink, dianaStep, dianaStepWire, dianaUplink, ef21Step, ef21StepWire,  # noqa: F401
+                    ef21Uplink, freconStep, freconUplink, marinaStep, marinaStepWire, marinaUplink)
 from .reduce import (make_server_gradient_frecon, reduce_client_models, reduce_rows,  # noqa: F401
                      serverGradientCOFIG, serverGradientDIANA, serverGradientGradSkip, serverGradientMaster,
                      serverGradientPlain)

@@ -470,6 +470,198 @@ class ShiftUplinkReducer:
         return out, msg_out, shift_out
 
 
+_ELEMENTWISE = (CompressorType.IDENTICAL, CompressorType.LAZY_COMPRESSOR, CompressorType.NATURAL_COMPRESSOR_FP32,
+                CompressorType.STANDARD_DITHERING_FP32, CompressorType.NATURAL_DITHERING_FP32)
+
+
+class FreconUplinkReducer:
+    """A FRECON round of N resident clients in one call (flc_frecon_reduce): both client messages
+    from one read of the gradients, under one pattern per client (algorithms.py:1104-1119),
+
+        u_i = C_i(G_i - H_i);   q_i = C_i(G_i - P_i);   H_i += alpha * u_i   (in place)
+        u_avg = (sum_i w_i u_i) / sum(w);   q_avg = (sum_i w_i q_i) / sum(w)
+
+    and, with ``server``, the server's combination (1124-1176, 1181):
+
+        result  = q_avg + (1 - lambda_) * g_server_prev + lambda_ * (u_avg + h_prev)
+        h_prev' = h_prev + alpha_update * u_avg
+
+    Every row and both folds carry the bits of N ``freconStep(in_place=True)`` calls and
+    ``reduce_rows`` of their messages.  The elementwise codecs (ident, lazy, natural, standard and
+    natural dithering) run the one-kernel entry; RandK, TopK and Rank-K are composed from
+    ``ShiftUplinkReducer`` — the in-place DIANA shape over ``(G, H)``, then the plain fold over
+    ``(G, P)`` with the same seed, ``client0`` and patterns — followed by the tail in torch
+    (``sparse`` / ``batched`` go to those two calls under their own rules; for an elementwise codec
+    they raise ``NotImplementedError`` like ``ShiftUplinkReducer``).  The compressor's wire
+    statistics advance as 2 N ``compressVector`` calls."""
+
+    def __init__(self, compressor: Compressor, device=None, seed=None):
+        _lib.require_gpu()
+        self.comp = compressor
+        self.device = _device(device)
+        self.seed = seed
+
+    def params(self):
+        prm, keep = self.comp.codec_params(self.device)
+        if self.seed is not None:
+            prm.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
+        return prm, keep
+
+    def workspace_bytes(self, n, d):
+        prm, _ = self.params()
+        return _lib.load().flc_frecon_reduce_workspace_size(ctypes.byref(prm), n, d)
+
+    def __call__(self, G, H, P, alpha, *, server=None, weights=None, divisor=None, client0=0, randk_idx=None,
+                 uniforms=None, lazy_u=None, out_u=None, out_q=None, pnorms_u_out=None, pnorms_q_out=None, stream=None,
+                 sparse=False, batched=False):
+        """G, H, P: [N, D] fp32 row-contiguous device matrices (the local gradients, the clients'
+        shifts — updated in place — and the gradients at the previous iterate).  ``server``: None or
+        a dict with ``lambda_``, ``g_server_prev`` and ``h_prev`` ([D] device vectors), optionally
+        ``alpha_update`` (then h_prev' is formed: into ``h_prev_out`` when given, which may be
+        ``h_prev`` itself, else into a new vector) and ``out`` for the result.  Patterns, ``weights``,
+        ``divisor``, ``client0`` and ``stream`` as in ``ShiftUplinkReducer``.  Returns
+        ``(u_avg, q_avg, result, h_prev_new)``, the last two None without ``server`` /
+        ``alpha_update``."""
+        args = (G, H, P, alpha, server, weights, divisor, client0, randk_idx, uniforms, lazy_u, out_u, out_q,
+                pnorms_u_out, pnorms_q_out, sparse, batched)
+        if stream is not None:
+            if stream.device != self.device:
+                raise ValueError(f"stream is on {stream.device}, the reducer runs on {self.device}")
+            with torch.cuda.stream(stream):
+                return self._run(*args)
+        return self._run(*args)
+
+    def _tail_operands(self, who, server, d):
+        for key in ("lambda_", "g_server_prev", "h_prev"):
+            if key not in server:
+                raise ValueError(f"{who}: server needs {key!r}")
+        unknown = set(server) - {"lambda_", "g_server_prev", "h_prev", "alpha_update", "h_prev_out", "out"}
+        if unknown:
+            raise ValueError(f"{who}: unknown server keys {sorted(unknown)}")
+        if server.get("h_prev_out") is not None and server.get("alpha_update") is None:
+            raise ValueError(f"{who}: h_prev_out given without alpha_update")
+        for key in ("g_server_prev", "h_prev", "h_prev_out", "out"):
+            v = server.get(key)
+            if v is None:
+                continue
+            if not torch.is_tensor(v) or not _is_fp32_device(v):
+                raise TypeError(f"{who}: server[{key!r}] must be an fp32 device tensor")
+            if v.dim() != 1 or v.numel() != d or not v.is_contiguous():
+                raise ValueError(f"{who}: server[{key!r}] must be a contiguous [{d}] vector")
+
+    def _run(self, G, H, P, alpha, server, weights, divisor, client0, randk_idx, uniforms, lazy_u, out_u, out_q,
+             pnorms_u_out, pnorms_q_out, sparse, batched):
+        lib = _lib.load()
+        who = "FreconUplinkReducer"
+        dev = self.device
+        for name, v in (("G", G), ("H", H), ("P", P), ("out_u", out_u), ("out_q", out_q)):
+            if v is not None and (not torch.is_tensor(v) or not _is_fp32_device(v)):
+                raise TypeError(f"{who}: {name} must be an fp32 device tensor")
+        if G.dim() != 2:
+            raise ValueError(f"{who}: G must be an [N, D] matrix")
+        n, d = G.shape
+        if server is not None:
+            self._tail_operands(who, server, d)
+        for name, v in (("out_u", out_u), ("out_q", out_q)):
+            if v is not None and (v.numel() != d or not v.is_contiguous()):
+                raise ValueError(f"{who}: {name} must be a contiguous [{d}] vector")
+        if self.comp.compressorType not in _ELEMENTWISE:
+            return self._composed(G, H, P, alpha, server, weights, divisor, client0, randk_idx, uniforms, lazy_u, out_u,
+                                  out_q, pnorms_u_out, pnorms_q_out, sparse, batched)
+        if sparse or batched:
+            raise NotImplementedError(f"{who}: sparse / batched are RandK's and TopK's rounds; this compressor is "
+                                      f"{self.comp.compressorType}")
+        if not hasattr(lib, "flc_frecon_reduce"):
+            raise NotImplementedError("this library build has no flc_frecon_reduce")
+
+        def rows(name, v):
+            return _row_matrix(who, name, v, n, d, like=" like G")
+        fr = _lib.FlcFreconRows()
+        fr.d_a, fr.lda = rows("G", G)
+        fr.d_h, fr.ldh = rows("H", H)
+        fr.d_p, fr.ldp = rows("P", P)
+        fr.shift_alpha = float(np.float32(alpha))
+        if out_u is None:
+            out_u = torch.empty(d, dtype=torch.float32, device=dev)
+        if out_q is None:
+            out_q = torch.empty(d, dtype=torch.float32, device=dev)
+        result = h_new = None
+        srv = None
+        if server is not None:
+            lam = float(server["lambda_"])
+            result = server.get("out")
+            if result is None:
+                result = torch.empty(d, dtype=torch.float32, device=dev)
+            srv = _lib.FlcFreconServer()
+            srv.d_g_server_prev = server["g_server_prev"].data_ptr()
+            srv.d_h_prev = server["h_prev"].data_ptr()
+            srv.lambda_ = float(np.float32(lam))
+            srv.one_minus_lambda = float(np.float32(1.0 - lam))           # the double difference, cast once
+            srv.d_result = result.data_ptr()
+            if server.get("alpha_update") is not None:
+                h_new = server.get("h_prev_out")
+                if h_new is None:
+                    h_new = torch.empty(d, dtype=torch.float32, device=dev)
+                srv.alpha_update = float(np.float32(server["alpha_update"]))
+                srv.d_h_prev_out = h_new.data_ptr()
+        if n == 0:                                                   # no clients (algorithms.py:2117-2118)
+            return out_u.zero_(), out_q.zero_(), (result.zero_() if result is not None else None), None
+        prm, keep = self.params()
+        pat = _lib.FlcPattern()
+        pat.client0 = int(client0)
+        t = self.comp.compressorType
+        lazy_host = None
+        if t == CompressorType.LAZY_COMPRESSOR and lazy_u is not None:
+            lazy_u = torch.as_tensor(lazy_u, dtype=torch.float64)
+            if lazy_u.numel() != n:
+                raise ValueError(f"lazy_u must hold {n} draws")
+            lazy_host = [float(x) for x in lazy_u.detach().cpu().reshape(-1).tolist()]
+            lazy_u = lazy_u.to(dev).contiguous()
+            keep.append(lazy_u)
+        if _pattern_draws(pat, t, randk_idx, uniforms, lazy_u) and self.seed is None and self.comp.device_rng is None:
+            raise ValueError("no compat pattern given and no device-RNG seed set")
+        w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
+        if d > 0:
+            vp = ctypes.c_void_p
+            ws = _lib.WORKSPACE.get(dev, lib.flc_frecon_reduce_workspace_size(ctypes.byref(prm), n, d))
+            with torch.cuda.device(dev):
+                rc = lib.flc_frecon_reduce(ctypes.byref(prm), ctypes.byref(pat), ctypes.byref(fr), n, d, vp(w_ptr),
+                                           ctypes.c_float(total),
+                                           vp(pnorms_u_out.data_ptr() if pnorms_u_out is not None else None),
+                                           vp(pnorms_q_out.data_ptr() if pnorms_q_out is not None else None),
+                                           vp(out_u.data_ptr()), vp(out_q.data_ptr()),
+                                           ctypes.byref(srv) if srv is not None else None,
+                                           vp(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
+            _lib.check(rc, "flc_frecon_reduce")
+        for i in range(n):                                            # u_i then q_i: 2 N compressVector calls
+            if lazy_host is not None:
+                self.comp.testp = lazy_host[i]
+            self.comp._account(d)
+            self.comp._account(d)
+        return out_u, out_q, result, h_new
+
+    def _composed(self, G, H, P, alpha, server, weights, divisor, client0, randk_idx, uniforms, lazy_u, out_u, out_q,
+                  pnorms_u_out, pnorms_q_out, sparse, batched):
+        """RandK / TopK / Rank-K: the two rounds of the existing reducer, then the tail in torch."""
+        red = ShiftUplinkReducer(self.comp, device=self.device, seed=self.seed)
+        kw = dict(weights=weights, divisor=divisor, client0=client0, randk_idx=randk_idx, uniforms=uniforms,
+                  lazy_u=lazy_u, sparse=sparse, batched=batched)
+        u, _, _ = red(G, H, alpha=alpha, shift=H, shift_out=H, out=out_u, pnorms_out=pnorms_u_out, **kw)
+        q, _, _ = red(G, P, out=out_q, pnorms_out=pnorms_q_out, **kw)
+        result = h_new = None
+        if server is not None:
+            lam = float(server["lambda_"])
+            h_prev = server["h_prev"]
+            result = q + (1.0 - lam) * server["g_server_prev"] + lam * (u + h_prev)     # algorithms.py:1171
+            if server.get("out") is not None:
+                result = server["out"].copy_(result)
+            if server.get("alpha_update") is not None:
+                h_new = h_prev + float(server["alpha_update"]) * u                       # algorithms.py:1181
+                if server.get("h_prev_out") is not None:
+                    h_new = server["h_prev_out"].copy_(h_new)
+        return u, q, result, h_new
+
+
 class PayloadReducer:
     """Server side of the wire format: out = (sum_i w_i * decode(payload_i)) / sum(w), folded in
     client order straight from the messages (flc_unpack_reduce) — the same bits as

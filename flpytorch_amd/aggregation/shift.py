@@ -31,6 +31,24 @@ def marinaStep(compressor, grad_cur, grad_prev, g_prev):
     return msg
 
 
+def cofigStep(compressor, grad_cur, h, alpha, in_place=False):
+    """COFIG's client step (algorithms.py:1265-1269): ``u_i = C(grad - h_i); h_i += alpha * u_i`` —
+    ``dianaStep`` under its own name.  Returns ``(u_i, h_new)``."""
+    return dianaStep(compressor, grad_cur, h, alpha, in_place=in_place)
+
+
+def freconStep(compressor, grad_cur, h, grad_prev, alpha, in_place=False):
+    """FRECON's client step (algorithms.py:1104-1119): ``u_i = C(grad - h_i); h_i += alpha * u_i`` and
+    ``q_i = C(grad - grad_prev)`` with ``grad_prev`` the gradient at the server's previous iterate,
+    both under the one pattern already generated — one ``dianaStep`` plus one
+    ``compressShift(grad_cur, grad_prev)``.  Returns ``(u_i, h_new, q_i)``; the wire statistics
+    advance twice, ``last_need_to_send_advance`` holding one message's count as after each of the
+    reference's two ``compressVector`` calls."""
+    u, h_new = dianaStep(compressor, grad_cur, h, alpha, in_place=in_place)
+    q, _ = compressor.compressShift(grad_cur, grad_prev)
+    return u, h_new, q
+
+
 # -- the same steps emitting the message the client sends (flc_pack_shift) -------------------------
 def dianaStepWire(compressor, grad_cur, h, alpha, in_place=False):
     """``dianaStep`` on the wire: returns ``(payload, h_new)`` — the payload decodes to ``m_i``
@@ -122,3 +140,36 @@ def marinaUplink(compressor, G_cur, G_prev_rows, g_prev, *, seed=None, **kw):
                                   "base yet; use the general round")
     out, _, _ = _uplink(compressor, G_cur, seed)(G_cur, G_prev_rows, base=g_prev, **kw)
     return out
+
+
+def cofigUplink(compressor, G, H, alpha, h_prev, *, seed=None, **kw):
+    """The COFIG round of N resident clients (algorithms.py:1265-1307): ``dianaUplink`` — ``H_i``
+    updated in place, the fold u of the messages — returned as the server returns it, ``u + h_prev``.
+    Needs no kernel of its own; ``kw`` as in ``dianaUplink``.  The server's own update,
+    ``h_prev += alpha_update * u``, wants u: pass ``out=`` to keep it."""
+    u = dianaUplink(compressor, G, H, alpha, seed=seed, **kw)
+    return u + h_prev
+
+
+def freconUplink(compressor, G, H, P, alpha, lambda_, g_server_prev, h_prev, alpha_update=None, *, seed=None,
+                 h_prev_out=None, **kw):
+    """The FRECON round of N resident clients (algorithms.py:1104-1176): per client
+    ``u_i = C_i(G_i - H_i)``, ``q_i = C_i(G_i - P_i)`` under one pattern, ``H_i += alpha * u_i`` in
+    place; both folds, and the server's
+    ``q_avg + (1 - lambda_) * g_server_prev + lambda_ * (u_avg + h_prev)`` is returned.  With
+    ``alpha_update`` the server shift is advanced too, ``h_prev + alpha_update * u_avg`` (1181), into
+    ``h_prev_out`` (which may be ``h_prev``; default: ``h_prev`` itself, in place).  Same bits as N
+    ``freconStep(in_place=True)`` calls, ``reduce_rows`` of their messages and the torch
+    expressions.  Elementwise codecs run ``flc_frecon_reduce`` (one kernel, ``G`` read once per
+    pass); RandK / TopK / Rank-K are composed from ``ShiftUplinkReducer``'s rounds (``sparse=True``
+    / ``batched=True`` under ``dianaUplink``'s rules).  ``kw``: ``FreconUplinkReducer.__call__``'s
+    weights / divisor / client0 / patterns / out_u / out_q / stream / sparse / batched."""
+    from .fused import FreconUplinkReducer
+    if seed is None and compressor.device_rng is not None:
+        seed = compressor.device_rng[0]
+    server = {"lambda_": lambda_, "g_server_prev": g_server_prev, "h_prev": h_prev}
+    if alpha_update is not None:
+        server["alpha_update"] = alpha_update
+        server["h_prev_out"] = h_prev if h_prev_out is None else h_prev_out
+    _, _, result, _ = FreconUplinkReducer(compressor, device=G.device, seed=seed)(G, H, P, alpha, server=server, **kw)
+    return result

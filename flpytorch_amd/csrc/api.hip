@@ -355,6 +355,61 @@ extern "C" int flc_encode_shift_reduce(const flc_codec_params* prm, const flc_pa
     return shift_reduce_run(prm, pat, sr, n, d, d_w, w_total, d_pnorms_out, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+extern "C" size_t flc_frecon_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (!prm || !frecon_elementwise(prm->codec) || n < 0 || d < 0) return 0;
+    return frecon_workspace(prm, n, d);
+}
+
+extern "C" int flc_frecon_reduce(const flc_codec_params* prm, const flc_pattern* pat, const flc_frecon_rows* rows, int64_t n,
+                                 int64_t d, const float* d_w, float w_total, float* d_pnorms_u_out, float* d_pnorms_q_out,
+                                 float* d_u_out, float* d_q_out, const flc_frecon_server* srv, void* d_ws, size_t ws_bytes,
+                                 void* stream) {
+    const char* me = "flc_frecon_reduce";
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (!frecon_elementwise(prm->codec)) {
+        set_error("%s: only the elementwise codecs have a two-message round (compose RandK / TopK / Rank-K from flc_encode_shift_reduce)", me);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    // the u message is the in-place DIANA round over (a, h): the shifted entries' shared checks see it as such
+    flc_shift_rows as_diana, sr;
+    memset(&as_diana, 0, sizeof(as_diana));
+    if (rows) {
+        as_diana.d_a = rows->d_a; as_diana.lda = rows->lda;
+        as_diana.d_b = as_diana.d_shift_in = as_diana.d_shift_out = rows->d_h;
+        as_diana.ldb = as_diana.ldin = as_diana.ldout = rows->ldh;
+    }
+    const float* some_out = srv ? srv->d_result : d_u_out;
+    bool empty;
+    if (int rc = shift_rows_prepare(me, nullptr, rows ? &as_diana : nullptr, n, d, some_out, &sr, &empty)) return rc;
+    if (empty) return FLC_OK;
+    if (!rows->d_p) { set_error("%s: need the p rows", me); return FLC_ERR_ARG; }
+    if (!srv && (!d_u_out || !d_q_out)) { set_error("%s: d_u_out and d_q_out are required without a server tail", me); return FLC_ERR_ARG; }
+    if (srv && (!srv->d_g_server_prev || !srv->d_h_prev || !srv->d_result)) {
+        set_error("%s: the server tail needs g_server_prev, h_prev and result", me);
+        return FLC_ERR_ARG;
+    }
+    if (int rc = outputs_overlap(me, {{"d_h", "ldh", rows->d_h, rows->ldh}}, nullptr, 0, n, d)) return rc;
+    if (srv) {
+        const OutRows ops[3] = {{"d_a", "lda", rows->d_a, rows->lda}, {"d_h", "ldh", rows->d_h, rows->ldh},
+                                {"d_p", "ldp", rows->d_p, rows->ldp}};
+        const OutRows outs[2] = {{"d_result", "", srv->d_result, 0}, {"d_h_prev_out", "", srv->d_h_prev_out, 0}};
+        for (const OutRows& o : outs) {
+            if (!o.p) continue;
+            const uintptr_t o0 = (uintptr_t)o.p, o1 = (uintptr_t)(o.p + d);
+            for (const OutRows& r : ops) {
+                uintptr_t lo, hi;
+                row_span(r.p, r.ld, n, d, &lo, &hi);
+                if (lo < o1 && o0 < hi) { set_error("%s: %s overlaps the %s rows", me, o.name, r.name); return FLC_ERR_ARG; }
+            }
+        }
+    }
+    if (int rc = frecon_precheck(prm, pat)) return rc;
+    if (ws_bytes < frecon_workspace(prm, n, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
+    if (frecon_workspace(prm, n, d) > 0 && !d_ws) { set_error("%s: null workspace", me); return FLC_ERR_ARG; }
+    return frecon_run(prm, pat, *rows, n, d, d_w, w_total, d_pnorms_u_out, d_pnorms_q_out, d_u_out, d_q_out, srv, d_ws,
+                      ws_bytes, (hipStream_t)stream);
+}
+
 extern "C" size_t flc_randk_shift_reduce_workspace_size(const flc_codec_params* prm, const flc_pattern* pat, int64_t n,
                                                         int64_t d) {
     if (!prm || prm->codec != FLC_RANDK || n < 0 || d < 0) return 0;

@@ -775,6 +775,277 @@ __global__ __launch_bounds__(256) void k_ew_shift_accum_scalar(flc_shift_rows sr
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// FRECON's two-message uplink over N rows (flc_frecon_reduce): k_ew_shift_accum's tile owner with a
+// third operand and a second sum.  Per row i, both messages from ONE read of a_i, h_i, p_i:
+//     u = C_i(a_i - h_i);  q = C_i(a_i - p_i) (same pattern row, same client key);  h_i' = h_i + alpha * u
+//     accu (+)= w_i * u;   accq (+)= w_i * q;   u_avg = accu / wt;  q_avg = accq / wt
+// opu and opq are the same op but for their RowTabs (dithering: each message's own norms,
+// reciprocals and fast-division flags; the row key is the same).  The element's encode is apply()
+// called once per message: the ops fold the draw into their decision (draw_below's top-byte
+// shortcut against the element's own threshold), so a draw shared across the two thresholds would
+// need a second form of every op; the draws' hashes are pure functions of (row key, column) and
+// are left to the compiler to share.  Every element of every row is read and written by one
+// thread, all of a row's loads before its store: h is updated in place.  The optional server tail
+// is applied to the two averages before the final stores, in the reference's op order.
+// ------------------------------------------------------------------------------------------
+struct FreconTail {
+    const float* gsp;       // g_server_prev; nullptr: no tail
+    const float* hp;        // h_prev
+    float lambda, oml;      // lambda, (float)(1 - lambda)
+    float* result;
+    float au;               // alpha_update
+    float* hp_out;          // nullptr or h_prev' (may be hp)
+};
+
+__device__ inline void frecon_tail1(const FreconTail& t, int64_t j, float ua, float qa) {
+    const float gs = t.gsp[j], hp = t.hp[j];
+    const float t1 = t.oml * gs;
+    const float t2 = qa + t1;
+    const float t3 = ua + hp;
+    const float t4 = t.lambda * t3;
+    t.result[j] = t2 + t4;
+    if (t.hp_out) t.hp_out[j] = hp + t.au * ua;
+}
+
+// tile shape: ONE float4 column per thread x 2 rows in flight (-DFLC_FRECON_COLS / _PF / _WAVES for A/B
+// builds).  k_ew_shift_accum's 2 x 2 carries three rings and two encodes here: QSGD with device draws
+// needs 173-174 VGPRs, 2 waves per SIMD.  On one shift matrix at N = 128, D = 25 M (timing only,
+// profiles/r14/frecon/tile_ab/) the QSGD round took 18.58 ms with 2 x 2, 17.58 with 2 x 2 held to 3
+// waves, 17.01 with 2 x 1, 16.26 with 1 x 4 and 15.81 with 1 x 2; natural 21.64 / 21.57 / 21.38 /
+// 21.00 / 21.15 ms, inside each other's repeats
+#ifndef FLC_FRECON_COLS
+#define FLC_FRECON_COLS 1
+#endif
+#ifndef FLC_FRECON_PF
+#define FLC_FRECON_PF 2
+#endif
+#ifdef FLC_FRECON_WAVES
+#define FLC_FRECON_BOUNDS __launch_bounds__(256, FLC_FRECON_WAVES)
+#else
+#define FLC_FRECON_BOUNDS __launch_bounds__(256)
+#endif
+
+template <class Op, int COLS, int PF, bool W>
+__global__ FLC_FRECON_BOUNDS void k_ew_frecon_accum(flc_frecon_rows fr, int64_t n, int64_t d, Op opu, Op opq,
+                                                         const float* __restrict__ levels, int s,
+                                                         const float* __restrict__ w, float wt, float* u_out,
+                                                         float* q_out, FreconTail tl) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem_tab[];
+    if (Op::TABLE) {
+        const bool tok = load_table(levels, s, smem_tab);
+        opu.set_table_ok(tok);
+        opq.set_table_ok(tok);
+    }
+    const int64_t groups = d / 4;
+    const int64_t tile_groups = (int64_t)blockDim.x * COLS;
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t t0 = (int64_t)blockIdx.x * tile_groups; t0 < groups; t0 += (int64_t)gridDim.x * tile_groups) {
+        int64_t gi[COLS];
+        bool ok[COLS];
+        uint32_t cs[COLS][4];
+#pragma unroll
+        for (int c = 0; c < COLS; ++c) {
+            gi[c] = t0 + threadIdx.x + c * 256;
+            ok[c] = gi[c] < groups;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) cs[c][q] = opu.col(gi[c] * 4 + q);
+        }
+        float4 ra[PF][COLS], rh[PF][COLS], rp[PF][COLS];
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            if (p < n) {
+                const float4* pa = reinterpret_cast<const float4*>(fr.d_a + p * fr.lda);
+                const float4* ph = reinterpret_cast<const float4*>(fr.d_h + p * fr.ldh);
+                const float4* pp = reinterpret_cast<const float4*>(fr.d_p + p * fr.ldp);
+#pragma unroll
+                for (int c = 0; c < COLS; ++c) {
+                    ra[p][c] = ok[c] ? ld_row4(pa + gi[c]) : zero4;
+                    rh[p][c] = ok[c] ? ld_row4(ph + gi[c]) : zero4;
+                    rp[p][c] = ok[c] ? ld_row4(pp + gi[c]) : zero4;
+                }
+            }
+        }
+        float4 accu[COLS], accq[COLS];
+        for (int64_t i0 = 0; i0 < n; i0 += PF) {
+#pragma unroll
+            for (int p = 0; p < PF; ++p) {
+                const int64_t i = i0 + p;
+                if (i < n) {
+                    opu.setup(i);
+                    opq.setup(i);
+                    const float wi = W ? w[i] : 1.f;
+                    float4 vu[COLS], vq[COLS];
+#pragma unroll
+                    for (int c = 0; c < COLS; ++c) {
+                        vu[c] = make_float4(ra[p][c].x - rh[p][c].x, ra[p][c].y - rh[p][c].y, ra[p][c].z - rh[p][c].z,
+                                            ra[p][c].w - rh[p][c].w);
+                        vq[c] = make_float4(ra[p][c].x - rp[p][c].x, ra[p][c].y - rp[p][c].y, ra[p][c].z - rp[p][c].z,
+                                            ra[p][c].w - rp[p][c].w);
+                    }
+                    float4 eu[COLS], eq[COLS];
+                    if (opu.row_fast()) apply_cols<true, COLS>(opu, vu, gi, cs, smem_tab, eu);
+                    else apply_cols<false, COLS>(opu, vu, gi, cs, smem_tab, eu);
+                    if (opq.row_fast()) apply_cols<true, COLS>(opq, vq, gi, cs, smem_tab, eq);
+                    else apply_cols<false, COLS>(opq, vq, gi, cs, smem_tab, eq);
+#pragma unroll
+                    for (int c = 0; c < COLS; ++c) {
+                        const float4 tu = W ? make_float4(wi * eu[c].x, wi * eu[c].y, wi * eu[c].z, wi * eu[c].w) : eu[c];
+                        const float4 tq = W ? make_float4(wi * eq[c].x, wi * eq[c].y, wi * eq[c].z, wi * eq[c].w) : eq[c];
+                        if (i == 0) { accu[c] = tu; accq[c] = tq; }
+                        else {
+                            accu[c].x = accu[c].x + tu.x; accu[c].y = accu[c].y + tu.y;
+                            accu[c].z = accu[c].z + tu.z; accu[c].w = accu[c].w + tu.w;
+                            accq[c].x = accq[c].x + tq.x; accq[c].y = accq[c].y + tq.y;
+                            accq[c].z = accq[c].z + tq.z; accq[c].w = accq[c].w + tq.w;
+                        }
+                        if (ok[c])
+                            reinterpret_cast<float4*>(fr.d_h + i * fr.ldh)[gi[c]] =
+                                make_float4(rh[p][c].x + fr.shift_alpha * eu[c].x, rh[p][c].y + fr.shift_alpha * eu[c].y,
+                                            rh[p][c].z + fr.shift_alpha * eu[c].z, rh[p][c].w + fr.shift_alpha * eu[c].w);
+                    }
+                    if (i + PF < n) {
+                        const float4* pa = reinterpret_cast<const float4*>(fr.d_a + (i + PF) * fr.lda);
+                        const float4* ph = reinterpret_cast<const float4*>(fr.d_h + (i + PF) * fr.ldh);
+                        const float4* pp = reinterpret_cast<const float4*>(fr.d_p + (i + PF) * fr.ldp);
+#pragma unroll
+                        for (int c = 0; c < COLS; ++c) {
+                            ra[p][c] = ok[c] ? ld_row4(pa + gi[c]) : zero4;
+                            rh[p][c] = ok[c] ? ld_row4(ph + gi[c]) : zero4;
+                            rp[p][c] = ok[c] ? ld_row4(pp + gi[c]) : zero4;
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < COLS; ++c) {
+            if (!ok[c]) continue;
+            const float ua[4] = {accu[c].x / wt, accu[c].y / wt, accu[c].z / wt, accu[c].w / wt};
+            const float qa[4] = {accq[c].x / wt, accq[c].y / wt, accq[c].z / wt, accq[c].w / wt};
+            if (tl.gsp) {
+                // the tail's loads before any of this group's stores (h_prev' may be written over h_prev)
+                const float4 gs = reinterpret_cast<const float4*>(tl.gsp)[gi[c]];
+                const float4 hp = reinterpret_cast<const float4*>(tl.hp)[gi[c]];
+                const float g4[4] = {gs.x, gs.y, gs.z, gs.w}, h4[4] = {hp.x, hp.y, hp.z, hp.w};
+                float r4[4], o4[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float t1 = tl.oml * g4[q];
+                    const float t2 = qa[q] + t1;
+                    const float t3 = ua[q] + h4[q];
+                    const float t4 = tl.lambda * t3;
+                    r4[q] = t2 + t4;
+                    o4[q] = h4[q] + tl.au * ua[q];
+                }
+                reinterpret_cast<float4*>(tl.result)[gi[c]] = make_float4(r4[0], r4[1], r4[2], r4[3]);
+                if (tl.hp_out) reinterpret_cast<float4*>(tl.hp_out)[gi[c]] = make_float4(o4[0], o4[1], o4[2], o4[3]);
+            }
+            if (u_out) reinterpret_cast<float4*>(u_out)[gi[c]] = make_float4(ua[0], ua[1], ua[2], ua[3]);
+            if (q_out) reinterpret_cast<float4*>(q_out)[gi[c]] = make_float4(qa[0], qa[1], qa[2], qa[3]);
+        }
+    }
+}
+
+// the same round one element at a time: unaligned operands, a leading dimension that is no multiple
+// of 4, and the d % 4 tail of the vector launch
+template <class Op>
+__global__ __launch_bounds__(256) void k_ew_frecon_accum_scalar(flc_frecon_rows fr, int64_t n, int64_t j0, int64_t d,
+                                                                Op opu, Op opq, const float* __restrict__ levels, int s,
+                                                                const float* __restrict__ w, float wt, float* u_out,
+                                                                float* q_out, FreconTail tl) {
+    extern __shared__ __attribute__((aligned(16))) float4 smem_tab[];
+    if (Op::TABLE) {
+        const bool tok = load_table(levels, s, smem_tab);
+        opu.set_table_ok(tok);
+        opq.set_table_ok(tok);
+    }
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t j = j0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < d; j += stride) {
+        const uint32_t cs = opu.col(j);
+        float accu = 0.f, accq = 0.f;
+        for (int64_t i = 0; i < n; ++i) {
+            opu.setup(i);
+            opq.setup(i);
+            const float a = fr.d_a[i * fr.lda + j], hv = fr.d_h[i * fr.ldh + j], pv = fr.d_p[i * fr.ldp + j];
+            const float eu = opu.template apply<false>(a - hv, j, cs, smem_tab);
+            const float eq = opq.template apply<false>(a - pv, j, cs, smem_tab);
+            const float tu = w ? w[i] * eu : eu, tq = w ? w[i] * eq : eq;
+            accu = (i == 0) ? tu : accu + tu;
+            accq = (i == 0) ? tq : accq + tq;
+            fr.d_h[i * fr.ldh + j] = hv + fr.shift_alpha * eu;
+        }
+        const float ua = accu / wt, qa = accq / wt;
+        if (tl.gsp) frecon_tail1(tl, j, ua, qa);
+        if (u_out) u_out[j] = ua;
+        if (q_out) q_out[j] = qa;
+    }
+}
+
+// The two norm sets of the FRECON round from ONE read of a, h and p: partial[row][part] of a - h
+// into pu / tu and of a - p into pq / tq, each accumulated exactly as k_norm_partials<.., DIFF> does
+// for its pair (the same elements per thread in the same order, the same fold), so the norms
+// k_norm_final makes of them carry launch_norms' bits for (a, h) and for (a, p).
+template <int NORM, bool VEC>
+__global__ __launch_bounds__(256) void k_norm_partials2(flc_frecon_rows fr, int64_t d, int64_t parts, int64_t plen,
+                                                        double* __restrict__ pu, uint32_t* __restrict__ tu,
+                                                        double* __restrict__ pq, uint32_t* __restrict__ tq) {
+    const int64_t row = blockIdx.y;
+    const float* ra = fr.d_a + row * fr.lda;
+    const float* rh = fr.d_h + row * fr.ldh;
+    const float* rp = fr.d_p + row * fr.ldp;
+    __shared__ double red[2][4];
+    __shared__ uint32_t redt[2][4];
+    for (int64_t part = blockIdx.x; part < parts; part += gridDim.x) {
+        const int64_t j0 = part * plen;
+        const int64_t j1 = min(d, j0 + plen);
+        double au = 0.0, aq = 0.0;
+        uint32_t tnu = 0, tnq = 0;
+        auto one = [&](int64_t j) {
+            const float a = ra[j];
+            const float vu = a - rh[j], vq = a - rp[j];
+            au = nacc<NORM>(au, vu); tnu |= is_tiny(vu);
+            aq = nacc<NORM>(aq, vq); tnq |= is_tiny(vq);
+        };
+        if (VEC) {
+            const int64_t g0 = j0 / 4, g1 = j1 / 4;   // j0 % 4 == 0 (plen % 4 == 0)
+            for (int64_t g = g0 + threadIdx.x; g < g1; g += 256) {
+                const float4 a = ld_row4(reinterpret_cast<const float4*>(ra) + g);
+                const float4 h = reinterpret_cast<const float4*>(rh)[g];
+                const float4 p = ld_row4(reinterpret_cast<const float4*>(rp) + g);
+                const float4 vu = make_float4(a.x - h.x, a.y - h.y, a.z - h.z, a.w - h.w);
+                const float4 vq = make_float4(a.x - p.x, a.y - p.y, a.z - p.z, a.w - p.w);
+                au = nacc<NORM>(au, vu.x); au = nacc<NORM>(au, vu.y); au = nacc<NORM>(au, vu.z); au = nacc<NORM>(au, vu.w);
+                aq = nacc<NORM>(aq, vq.x); aq = nacc<NORM>(aq, vq.y); aq = nacc<NORM>(aq, vq.z); aq = nacc<NORM>(aq, vq.w);
+                tnu |= is_tiny(vu.x) | is_tiny(vu.y) | is_tiny(vu.z) | is_tiny(vu.w);
+                tnq |= is_tiny(vq.x) | is_tiny(vq.y) | is_tiny(vq.z) | is_tiny(vq.w);
+            }
+            for (int64_t j = g1 * 4 + threadIdx.x; j < j1; j += 256) one(j);
+        } else {
+            for (int64_t j = j0 + threadIdx.x; j < j1; j += 256) one(j);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            au = ncomb<NORM>(au, __shfl_xor(au, o, WAVE));
+            aq = ncomb<NORM>(aq, __shfl_xor(aq, o, WAVE));
+            tnu |= __shfl_xor(tnu, o, WAVE);
+            tnq |= __shfl_xor(tnq, o, WAVE);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            red[0][threadIdx.x >> 6] = au; redt[0][threadIdx.x >> 6] = tnu;
+            red[1][threadIdx.x >> 6] = aq; redt[1][threadIdx.x >> 6] = tnq;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            pu[row * parts + part] = ncomb<NORM>(ncomb<NORM>(red[0][0], red[0][1]), ncomb<NORM>(red[0][2], red[0][3]));
+            tu[row * parts + part] = redt[0][0] | redt[0][1] | redt[0][2] | redt[0][3];
+            pq[row * parts + part] = ncomb<NORM>(ncomb<NORM>(red[1][0], red[1][1]), ncomb<NORM>(red[1][2], red[1][3]));
+            tq[row * parts + part] = redt[1][0] | redt[1][1] | redt[1][2] | redt[1][3];
+        }
+        __syncthreads();
+    }
+}
+
 // device-RNG row keys (natural codec; dithering gets them from k_norm_final)
 __global__ void k_row_keys(int64_t n, uint64_t seed, int64_t client0, uint32_t* __restrict__ rk) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
@@ -1134,6 +1405,149 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
         }
         default:
             set_error("ew_run: codec %d is not elementwise", codec);
+            return FLC_ERR_UNSUPPORTED;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// flc_frecon_reduce (elementwise codecs): the norm pass over both differences for dithering, then
+// k_ew_frecon_accum.  The vector launch needs every operand in use 16-byte aligned and ld % 4 == 0.
+// ------------------------------------------------------------------------------------------
+template <class Op>
+static int launch_frecon_accum(const flc_frecon_rows& fr, int64_t n, int64_t d, Op opu, Op opq, const float* levels, int s,
+                               const float* w, float wt, float* u_out, float* q_out, const FreconTail& tl,
+                               hipStream_t st) {
+    const size_t lds = Op::TABLE ? (size_t)s * sizeof(float4) : 0;
+    uintptr_t pal = (uintptr_t)fr.d_a | (uintptr_t)fr.d_h | (uintptr_t)fr.d_p | (uintptr_t)u_out | (uintptr_t)q_out;
+    const uint64_t lal = (uint64_t)fr.lda | (uint64_t)fr.ldh | (uint64_t)fr.ldp;
+    if (tl.gsp) pal |= (uintptr_t)tl.gsp | (uintptr_t)tl.hp | (uintptr_t)tl.result | (uintptr_t)tl.hp_out;
+    const bool vec = (pal & 15u) == 0 && (lal & 3u) == 0;
+    ProfScope _ps("k_ew_frecon_accum", st);
+    int64_t j0 = 0;
+    if (vec && d / 4 > 0) {
+        const int grid = grid_cap(d / 4, 256 * FLC_FRECON_COLS, 1 << 20);
+        if (w) hipLaunchKernelGGL((k_ew_frecon_accum<Op, FLC_FRECON_COLS, FLC_FRECON_PF, true>), dim3(grid), dim3(256), lds, st,
+                                  fr, n, d, opu, opq, levels, s, w, wt, u_out, q_out, tl);
+        else hipLaunchKernelGGL((k_ew_frecon_accum<Op, FLC_FRECON_COLS, FLC_FRECON_PF, false>), dim3(grid), dim3(256), lds, st,
+                                fr, n, d, opu, opq, levels, s, w, wt, u_out, q_out, tl);
+        FLC_CHECK_LAUNCH("k_ew_frecon_accum");
+        j0 = (d / 4) * 4;
+    }
+    if (j0 < d) {
+        const int grid = grid_cap(d - j0, 256, 4096);
+        hipLaunchKernelGGL((k_ew_frecon_accum_scalar<Op>), dim3(grid), dim3(256), lds, st, fr, n, j0, d, opu, opq, levels, s,
+                           w, wt, u_out, q_out, tl);
+        FLC_CHECK_LAUNCH("k_ew_frecon_accum_scalar");
+    }
+    return FLC_OK;
+}
+
+// one set of row tables per message (natural with device draws uses the first set's row keys only)
+size_t frecon_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (prm->codec == FLC_IDENT || prm->codec == FLC_LAZY) return 0;
+    size_t b = 0;
+    carve_ew(nullptr, n, d, &b);
+    return 2 * b;
+}
+
+bool frecon_elementwise(int codec) {
+    return codec == FLC_IDENT || codec == FLC_LAZY || codec == FLC_NATURAL || codec == FLC_STD_DITHERING ||
+           codec == FLC_NAT_DITHERING;
+}
+
+// the checks that need no device (before any launch): the codec's own parameters and pattern
+int frecon_precheck(const flc_codec_params* prm, const flc_pattern* pat) {
+    if (prm->codec == FLC_LAZY && (!pat || !pat->d_lazy_u)) { set_error("lazy: pattern needs d_lazy_u"); return FLC_ERR_ARG; }
+    if (prm->codec == FLC_STD_DITHERING || prm->codec == FLC_NAT_DITHERING) return check_dither(prm);
+    return FLC_OK;
+}
+
+int frecon_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_frecon_rows& fr, int64_t n, int64_t d,
+               const float* w, float wt, float* pnorms_u_out, float* pnorms_q_out, float* u_out, float* q_out,
+               const flc_frecon_server* srv, void* ws, size_t ws_bytes, hipStream_t st) {
+    (void)ws_bytes;
+    const int codec = prm->codec;
+    const bool compat = pat && pat->d_uniforms;
+    const int64_t client0 = pat ? pat->client0 : 0;
+    UniformSrc us{compat ? pat->d_uniforms : nullptr, (pat && pat->uniforms_ld) ? pat->uniforms_ld : d};
+    FreconTail tl{nullptr, nullptr, 0.f, 0.f, nullptr, 0.f, nullptr};
+    if (srv) tl = FreconTail{srv->d_g_server_prev, srv->d_h_prev, srv->lambda, srv->one_minus_lambda, srv->d_result,
+                             srv->alpha_update, srv->d_h_prev_out};
+    auto go = [&](auto opu, auto opq, const float* levels, int s) -> int {
+        return launch_frecon_accum(fr, n, d, opu, opq, levels, s, w, wt, u_out, q_out, tl, st);
+    };
+    size_t ew_bytes = 0;
+    EwWs eu = carve_ew(ws, n, d, &ew_bytes);
+    EwWs eq = carve_ew(ws ? static_cast<char*>(ws) + ew_bytes : nullptr, n, d, nullptr);
+    switch (codec) {
+        case FLC_IDENT: {
+            IdentOp op;
+            return go(op, op, nullptr, 0);
+        }
+        case FLC_LAZY: {
+            LazyOp op;
+            op.lazy_u = pat->d_lazy_u;
+            op.P = prm->lazy_p;
+            return go(op, op, nullptr, 0);
+        }
+        case FLC_NATURAL: {
+            if (compat) { NaturalOp<true> op; op.us = us; op.rks = nullptr; return go(op, op, nullptr, 0); }
+            hipLaunchKernelGGL(k_row_keys, dim3(grid_cap(n, 256, 64)), dim3(256), 0, st, n, prm->seed, client0, eu.rk);
+            FLC_CHECK_LAUNCH("k_row_keys");
+            NaturalOp<false> op;
+            op.us = us;
+            op.rks = eu.rk;
+            return go(op, op, nullptr, 0);
+        }
+        case FLC_STD_DITHERING:
+        case FLC_NAT_DITHERING: {
+            // each pair's norm pass vectorises exactly when flc_encode_shift_reduce's would for that pair
+            const bool vec_u = ((((uintptr_t)fr.d_a | (uintptr_t)fr.d_h) & 15u) == 0) && (((fr.lda | fr.ldh) & 3) == 0);
+            const bool vec_q = ((((uintptr_t)fr.d_a | (uintptr_t)fr.d_p) & 15u) == 0) && (((fr.lda | fr.ldp) & 3) == 0);
+            const RowSrc a{fr.d_a, fr.lda, nullptr};
+            if (vec_u != vec_q) {
+                // one pair aligned, the other not: the two single-pair passes, each in its own form
+                const RowSrc hs{fr.d_h, fr.ldh, nullptr}, ps{fr.d_p, fr.ldp, nullptr};
+                if (int rc = launch_norms(a, vec_u, n, d, prm->norm, eu.partial, eu.tinyp, eu.pn, eu.rpn, eu.fast, prm->seed,
+                                          client0, eu.rk, st, &hs)) return rc;
+                if (int rc = launch_norms(a, vec_q, n, d, prm->norm, eq.partial, eq.tinyp, eq.pn, eq.rpn, eq.fast, prm->seed,
+                                          client0, eq.rk, st, &ps)) return rc;
+            } else {
+                const int64_t parts = norm_parts(n, d), plen = norm_part_len(n, d);
+                dim3 grid((unsigned)std::min<int64_t>(parts, std::max<int64_t>(64, 4096 / std::max<int64_t>(n, 1))), (unsigned)n);
+#define FLC_NORM2_CASE(NK)                                                                          \
+    { ProfScope _ps("k_norm_partials2", st);                                                        \
+    if (vec_u) hipLaunchKernelGGL((k_norm_partials2<NK, true>), grid, dim3(256), 0, st, fr, d, parts, plen, eu.partial, eu.tinyp, eq.partial, eq.tinyp); \
+    else hipLaunchKernelGGL((k_norm_partials2<NK, false>), grid, dim3(256), 0, st, fr, d, parts, plen, eu.partial, eu.tinyp, eq.partial, eq.tinyp); } \
+    FLC_CHECK_LAUNCH("k_norm_partials2");                                                           \
+    hipLaunchKernelGGL((k_norm_final<NK>), dim3((unsigned)n), dim3(64), 0, st, eu.partial, eu.tinyp, parts, n, eu.pn, eu.rpn, \
+                       eu.fast, prm->seed, client0, eu.rk);                                         \
+    hipLaunchKernelGGL((k_norm_final<NK>), dim3((unsigned)n), dim3(64), 0, st, eq.partial, eq.tinyp, parts, n, eq.pn, eq.rpn, \
+                       eq.fast, prm->seed, client0, eq.rk);                                         \
+    FLC_CHECK_LAUNCH("k_norm_final");
+                if (prm->norm == FLC_NORM_L2) { FLC_NORM2_CASE(FLC_NORM_L2) }
+                else if (prm->norm == FLC_NORM_L1) { FLC_NORM2_CASE(FLC_NORM_L1) }
+                else { FLC_NORM2_CASE(FLC_NORM_LINF) }
+#undef FLC_NORM2_CASE
+            }
+            if (pnorms_u_out) FLC_CHECK_HIP(hipMemcpyAsync(pnorms_u_out, eu.pn, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (pnorms_q_out) FLC_CHECK_HIP(hipMemcpyAsync(pnorms_q_out, eq.pn, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
+            const RowTabs rtu{eu.pn, eu.rpn, eu.fast, eu.rk}, rtq{eq.pn, eq.rpn, eq.fast, eq.rk};
+            auto run = [&](auto opu) -> int {
+                opu.us = us; opu.s = prm->s; opu.sf = (float)prm->s; opu.tab_ok = false;
+                auto opq = opu;
+                opu.rt = rtu;
+                opq.rt = rtq;
+                return go(opu, opq, prm->d_levels, prm->s);
+            };
+            if (codec == FLC_STD_DITHERING) {
+                if (compat) return run(DitherOp<false, true>{});
+                return run(DitherOp<false, false>{});
+            }
+            return run(DitherOp<true, false>{});   // natural dithering output does not depend on the draws
+        }
+        default:
+            set_error("flc_frecon_reduce: codec %d is not elementwise", codec);
             return FLC_ERR_UNSUPPORTED;
     }
 }

@@ -151,6 +151,14 @@ size_t shift_workspace(const flc_codec_params* prm, int64_t d);
 size_t shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
                      const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+// FRECON's two-message round (flc_frecon_reduce, codecs.hip k_ew_frecon_accum): elementwise codecs
+// only; frecon_precheck is the codec's host-side parameter / pattern check, before any launch
+bool frecon_elementwise(int codec);
+size_t frecon_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
+int frecon_precheck(const flc_codec_params* prm, const flc_pattern* pat);
+int frecon_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_frecon_rows& fr, int64_t n, int64_t d,
+               const float* w, float wt, float* pnorms_u_out, float* pnorms_q_out, float* u_out, float* q_out,
+               const flc_frecon_server* srv, void* ws, size_t ws_bytes, hipStream_t st);
 int encode_row(const flc_codec_params* prm, const flc_pattern* pat, const float* d_x, int64_t d,
                const float* d_pnorm_in, float* d_pnorm_out, float* d_out, void* d_ws, size_t ws_bytes, hipStream_t st);
 size_t encode_row_workspace(const flc_codec_params* prm, int64_t d);

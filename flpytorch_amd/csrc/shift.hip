@@ -4,6 +4,8 @@
 // EF21   g_next = g_prev + C(g - g_prev) * (1 / (1 + w) | 1)     algorithms.py:1506-1517
 // MARINA g_next = g_prev + C(g - g_prev_x)                       algorithms.py:537, 691
 // FRECON / COFIG u_i = C(g - h_i), h_i += alpha u_i              algorithms.py:1104-1110, 1265-1269
+// (FRECON's second message q_i = C(g - g(x_prev)) and its round of n clients: codecs.hip
+// k_ew_frecon_accum, flc_frecon_reduce)
 //
 // Elementwise codecs (ident, lazy, natural, dithering) run one fused pass (codecs.hip k_ew_shift,
 // after the norm pass over a - b for dithering): a, b [, base, h_in] read once, msg [, h_out]

@@ -432,6 +432,62 @@ int flc_dither_shift_reduce(const flc_codec_params* prm, const flc_pattern* pat,
 int flc_dither_row_flags(int64_t n, int64_t d, const void* d_ws, size_t ws_bytes, uint32_t* d_flags, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * FRECON's two-message uplink — a FRECON round of n resident clients in one call (additive:
+ * flc_version() stays 104, detect the entry by its symbol).  The FRECON client sends two messages
+ * made from the same gradient under the same pattern (algorithms.py:1104-1119), the server folds
+ * both and combines them (1124-1176).  Per row i, under pattern row i and client client0 + i, every
+ * operation rounded separately in fp32:
+ *     u_i  = C_i(a_i - h_i);   q_i = C_i(a_i - p_i)   (the SAME draws: one generateCompressPattern)
+ *     h_i' = h_i + shift_alpha * u_i                   (in place over the h rows)
+ *     u_avg = (sum_i w_i * u_i) / w_total;   q_avg = (sum_i w_i * q_i) / w_total
+ * Both sums are folded in row order, the first term assigned, d_w == NULL meaning no multiply, one
+ * division by w_total at the end.  With a server tail (srv != NULL), in the reference's op order:
+ *     t1 = one_minus_lambda * g_server_prev;  t2 = q_avg + t1;  t3 = u_avg + h_prev;
+ *     t4 = lambda * t3;  d_result = t2 + t4;  d_h_prev_out = h_prev + alpha_update * u_avg
+ * (h_prev' from the OLD h_prev; d_h_prev_out may be d_h_prev, or NULL).  d_u_out / d_q_out receive
+ * the two averages: required without srv, optional (NULL) with it.
+ *
+ * The bits are the library's own: the h rows, u_avg, q_avg and both norm vectors are bit-identical
+ * to two flc_encode_shift_reduce calls with the same prm and pat — the in-place DIANA round over
+ * (a, h), then the plain fold (no base, no message, no shift) over (a, p).  Dithering encodes each
+ * message with the exactly rounded norm of its own difference; d_pnorms_u_out / d_pnorms_q_out:
+ * optional [n] norms used (dithering codecs only).
+ *
+ * One kernel reads a_i, h_i and p_i once per pass and keeps both sums in registers: 16 n d bytes
+ * (28 n d with dithering's norm pass, which reads the three operands once for both norm sets)
+ * against 20 n d + 16 n d (12 n d + 8 n d without norms) for the two calls.  The vector path needs
+ * every operand in use 16-byte aligned with ld % 4 == 0; anything else runs the scalar kernel
+ * (same bits).  Compat uniforms (d_uniforms) and device draws are both accepted.
+ *
+ * FLC_ERR_UNSUPPORTED before any launch: FLC_RANDK, FLC_TOPK, FLC_RANK_K (the caller composes the
+ * round from flc_encode_shift_reduce and its sparse / batched siblings) or an unknown codec; the
+ * size query then returns 0.  FLC_ERR_ARG: null prm-independent operands (rows, d_a, d_h, d_p, the
+ * outputs required above, any of srv's d_g_server_prev / d_h_prev / d_result) with n * d > 0,
+ * negative n or d, n > FLC_MAX_ROWS, h rows that overlap (|ldh| < d, n > 1), d_result or
+ * d_h_prev_out overlapping any row operand (a, h, p).  FLC_ERR_WORKSPACE: ws_bytes below the size
+ * query.  n == 0 or d == 0: FLC_OK, the device is not touched.  A refused call writes nothing.
+ * -------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* d_a; int64_t lda;   /* [n] rows g_i */
+    float*       d_h; int64_t ldh;   /* [n] rows h_i, updated IN PLACE: h_i + shift_alpha * u_i */
+    const float* d_p; int64_t ldp;   /* [n] rows: the gradient at x_prev */
+    float shift_alpha;
+} flc_frecon_rows;
+
+typedef struct {                      /* optional server tail, all [d] */
+    const float* d_g_server_prev; const float* d_h_prev;
+    float lambda, one_minus_lambda;   /* (float)lambda_ and (float)(1.0 - lambda_), the double difference cast once */
+    float* d_result;                  /* q_avg + one_minus_lambda * g_server_prev + lambda * (u_avg + h_prev) */
+    float alpha_update; float* d_h_prev_out;   /* NULL, or h_prev + alpha_update * u_avg; may be d_h_prev */
+} flc_frecon_server;
+
+size_t flc_frecon_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_frecon_reduce(const flc_codec_params* prm, const flc_pattern* pat, const flc_frecon_rows* rows, int64_t n,
+                      int64_t d, const float* d_w, float w_total, float* d_pnorms_u_out, float* d_pnorms_q_out,
+                      float* d_u_out, float* d_q_out, const flc_frecon_server* srv, void* d_ws, size_t ws_bytes,
+                      void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * Wire format: the message a client sends, and the server's decode +
  * reduce straight from the N messages.  The reference counts these bits
  * (last_need_to_send_advance, compressors.py:223-224, 367-368) but moves the dense decoded

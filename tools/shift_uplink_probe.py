@@ -61,6 +61,15 @@ interleaved in one process on one allocation; after every repeat the payloads, t
 and the folds are compared (bytes / int32).  Byte models: client 21 d (QSGD; natural 14 d: no norm pass,
 2-byte codes) against 41 d (30 d); server (c + 8) N d + 4 d against (c + 28) N d with c code bytes per
 element.  Writes <out-dir>/<spec>_client.jsonl and <spec>_server.jsonl (default profiles/r13/shift_wire).
+
+--frecon (elementwise specs, default qsgd:127,natural; device draws): the FRECON round with its server tail,
+  one_call     FreconUplinkReducer(G, H, P, alpha, server=...)                flc_frecon_reduce
+  composition  ShiftUplinkReducer twice (in-place DIANA over (G, H), the plain fold over (G, P)) and the
+               server's expressions in torch (about seven D-sized ops)
+each on its own copy of H and of h_prev, interleaved in one process on one allocation; after every repeat
+the results, the H matrices and the two h_prev vectors are compared as int32.  Byte models (N D terms):
+QSGD 28 N D against 36 N D, natural 16 N D against 20 N D.  Writes <out-dir>/<spec>.jsonl (default
+profiles/r14/frecon).  --fused-libs adds "one_call@<tag>" legs as above (timing only, the bit check off).
 """
 import argparse
 import json
@@ -530,6 +539,127 @@ def main_wire(a):
         del P
 
 
+def main_frecon(a):
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d = a.n, a.d
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev).manual_seed(1000)
+
+    def filled(rows=n):
+        t = torch.empty((rows, d), dtype=torch.float32, device=dev)
+        for i in range(0, rows, 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    G, H0, P = filled(), filled(), filled()
+    Hf, Hc = torch.empty_like(H0), torch.empty_like(H0)
+    gsp, hp0 = filled(1)[0], filled(1)[0]
+    variants = ("one_call", "composition")
+    res = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in variants}
+    hp = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in variants}
+    cu, cq = (torch.empty(d, dtype=torch.float32, device=dev) for _ in range(2))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    kernels = ("k_ew_frecon_accum", "k_norm_partials2", "k_ew_shift_accum", "k_norm_partials")
+    lam, alpha_update = 0.5, 0.25
+    extra = {t: _lib.open_variant(t) for t in a.fused_libs.split(",") if t}
+    for spec in a.specs.split(","):
+        comp_f, comp_c = (ag.initCompressor(spec, d) for _ in range(2))
+        alpha = 1.0 / (1.0 + comp_f.getW())
+        red_f = ag.FreconUplinkReducer(comp_f, device=dev, seed=SEED)
+        red_c = ag.ShiftUplinkReducer(comp_c, device=dev, seed=SEED)
+        Hf.copy_(H0)
+        Hc.copy_(H0)
+        for v in variants:
+            hp[v].copy_(hp0)
+
+        def run_one_call():
+            red_f(G, Hf, P, alpha, server={"lambda_": lam, "g_server_prev": gsp, "h_prev": hp["one_call"],
+                                           "alpha_update": alpha_update, "h_prev_out": hp["one_call"],
+                                           "out": res["one_call"]})
+
+        def run_composition():
+            # what the library offered before: two fused rounds, then the server's expressions in torch
+            red_c(G, Hc, alpha=alpha, shift=Hc, shift_out=Hc, out=cu)
+            red_c(G, P, out=cq)
+            h = hp["composition"]
+            torch.add(cq + (1.0 - lam) * gsp, lam * (cu + h), out=res["composition"])
+            torch.add(h, alpha_update * cu, out=h)
+        runs = {"one_call": run_one_call, "composition": run_composition}
+
+        def run_variant(lib):
+            def f():
+                with _lib.use(lib):
+                    run_one_call()
+            return f
+        for t, lib in extra.items():               # (timing only: they advance one_call's H and h_prev as well)
+            runs["one_call@" + t] = run_variant(lib)
+        dither = not spec.startswith("natural")
+        # algorithmic bytes (issue's models): the N D terms plus the [D] vectors of the tail
+        model = {"one_call": (28 if dither else 16) * n * d, "composition": (36 if dither else 20) * n * d}
+        for t in extra:
+            model["one_call@" + t] = model["one_call"]
+        for f in runs.values():                        # warm: code objects, workspaces, the allocator's blocks
+            f()
+        torch.cuda.synchronize()
+
+        def agree():
+            return bool(extra) or (torch.equal(res["one_call"].view(torch.int32), res["composition"].view(torch.int32))
+                    and torch.equal(hp["one_call"].view(torch.int32), hp["composition"].view(torch.int32))
+                    and torch.equal(Hf.view(torch.int32), Hc.view(torch.int32)))
+        if not agree():
+            raise SystemExit(f"{spec}: the one-call round and the composition differ after the warm-up round")
+        ms = {v: [] for v in runs}
+        path = os.path.join(a.out_dir, spec.replace(":", "_").replace(".", "_") + ".jsonl")
+        with open(path, "w") as fh:
+            def emit(rec):
+                line = json.dumps(rec)
+                fh.write(line + "\n")
+                fh.flush()
+                print(line, flush=True)
+            for r in range(a.repeats):
+                for v, f in runs.items():
+                    e0.record()
+                    for _ in range(a.steps):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    t = e0.elapsed_time(e1) / a.steps
+                    ms[v].append(t)
+                    emit({"spec": spec, "n": n, "d": d, "repeat": r, "variant": v, "ms_per_call": round(t, 4),
+                          "model_bytes": model[v], "GBps": round(model[v] / t / 1e6, 1)})
+                if not agree():
+                    raise SystemExit(f"{spec}: the one-call round and the composition differ after repeat {r}")
+            kms = {}
+            for v, f in runs.items():                  # the kernels' own times, one call each, outside the timed repeats
+                _lib.profile_enable(True)
+                for kn in kernels:
+                    _lib.profile_collect(kn)
+                f()
+                torch.cuda.synchronize()
+                _lib.profile_enable(False)
+                kms[v] = {kn: [round(t, 4), c] for kn in kernels for t, c in [_lib.profile_collect(kn)] if c}
+            if not agree():
+                raise SystemExit(f"{spec}: the one-call round and the composition differ after the timer pass")
+            med = {v: statistics.median(ms[v]) for v in runs}
+            emit({"spec": spec, "n": n, "d": d, "summary": True, "repeats": a.repeats, "steps": a.steps,
+                  "median_ms": {v: round(med[v], 4) for v in runs},
+                  "min_ms": {v: round(min(ms[v]), 4) for v in runs},
+                  "max_ms": {v: round(max(ms[v]), 4) for v in runs},
+                  "model_bytes": model,
+                  "GBps_of_model_at_median": {v: round(model[v] / med[v] / 1e6, 1) for v in runs},
+                  "composition_over_one_call": round(med["composition"] / med["one_call"], 3),
+                  "byte_model_composition_over_one_call": round(model["composition"] / model["one_call"], 3),
+                  "one_call_faster_beyond_spread": max(ms["one_call"]) < min(ms["composition"]),
+                  "bits_equal_every_repeat": not extra,
+                  "kernel_ms_and_records_one_call": kms})
+        print("wrote", path, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--specs", default="natural,qsgd:127")
@@ -543,6 +673,7 @@ def main():
     ap.add_argument("--topk", action="store_true", help="TopK specs: flc_topk_shift_reduce against the general entry")
     ap.add_argument("--one-read", action="store_true", help="QSGD specs: flc_dither_shift_reduce against the general entry")
     ap.add_argument("--wire", action="store_true", help="flc_pack_shift / flc_unpack_shift_reduce against their compositions")
+    ap.add_argument("--frecon", action="store_true", help="flc_frecon_reduce against two fused rounds plus the tail in torch")
     ap.add_argument("--shapes", default="diana,ef21", help="--topk / --one-read: the in-place rounds to time")
     a = ap.parse_args()
     if a.topk and a.out_dir == ap.get_default("out_dir"):
@@ -555,6 +686,10 @@ def main():
         a.out_dir = os.path.join(ROOT, "profiles", "r13", "shift_wire")
     if a.wire and a.specs == ap.get_default("specs"):
         a.specs = "qsgd:127,natural"
+    if a.frecon and a.out_dir == ap.get_default("out_dir"):
+        a.out_dir = os.path.join(ROOT, "profiles", "r14", "frecon")
+    if a.frecon and a.specs == ap.get_default("specs"):
+        a.specs = "qsgd:127,natural"
     if a.repeats < 1 or a.steps < 1 or a.n < 1 or a.d < 1:
         ap.error("--repeats, --steps, --n and --d are positive")
     if a.sparse:
@@ -565,6 +700,8 @@ def main():
         return main_one_read(a)
     if a.wire:
         return main_wire(a)
+    if a.frecon:
+        return main_frecon(a)
     import torch
 
     from flpytorch_amd import _lib
