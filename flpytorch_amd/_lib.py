@@ -23,6 +23,8 @@ FLC_REDUCE_PLAIN, FLC_REDUCE_REL_X = 0, 1
 # execution hints (flc_codec_params.flags): how, never what — every choice gives the same bits
 FLC_PATH_AUTO, FLC_PATH_SPARSE, FLC_PATH_DENSE = 0, 1, 2
 FLC_TIE_LOWEST, FLC_TIE_HIGHEST = 0, 1
+# flc_row_map.indexed: which per-row operands of a sampled round are state matrices addressed by client id
+FLC_IDX_B, FLC_IDX_BASE, FLC_IDX_MSG, FLC_IDX_SHIFT_IN, FLC_IDX_SHIFT_OUT = 1, 2, 4, 8, 16
 # which p = 2 norm the fused dithering uplink encodes with (flc_encode_reduce_ex): a what, not a how
 FLC_NORMMODE_EXACT, FLC_NORMMODE_TORCH_CPU = 0, 1
 ABI_VERSION = 104
@@ -42,6 +44,9 @@ EXPORTS = [
     "flc_encode_shift_reduce_workspace_size", "flc_encode_shift_reduce",
     "flc_randk_shift_reduce_workspace_size", "flc_randk_shift_reduce",
     "flc_topk_shift_reduce_workspace_size", "flc_topk_shift_reduce",
+    "flc_encode_shift_reduce_sampled_workspace_size", "flc_encode_shift_reduce_sampled",
+    "flc_randk_shift_reduce_sampled_workspace_size", "flc_randk_shift_reduce_sampled",
+    "flc_topk_shift_reduce_sampled_workspace_size", "flc_topk_shift_reduce_sampled",
     "flc_dither_shift_reduce_workspace_size", "flc_dither_shift_reduce", "flc_dither_row_flags",
     "flc_frecon_reduce_workspace_size", "flc_frecon_reduce",
     "flc_payload_bytes", "flc_payload_format", "flc_payload_validate", "flc_pack_workspace_size", "flc_pack", "flc_unpack",
@@ -97,6 +102,15 @@ class FlcShiftRows(ctypes.Structure):
         ("shift_alpha", ctypes.c_float),
         ("d_shift_in", ctypes.c_void_p), ("ldin", ctypes.c_int64),
         ("d_shift_out", ctypes.c_void_p), ("ldout", ctypes.c_int64),
+    ]
+
+
+class FlcRowMap(ctypes.Structure):
+    """flc_row_map: the participants of a sampled round (the _sampled entries) — participant i is
+    client ids[i] of n_total, an operand whose bit is set in ``indexed`` has its row at ptr + ids[i] * ld."""
+    _fields_ = [
+        ("h_ids", ctypes.c_void_p), ("d_ids", ctypes.c_void_p),
+        ("n_total", ctypes.c_int64), ("indexed", ctypes.c_uint32),
     ]
 
 
@@ -225,6 +239,19 @@ def _bind(lib):
         lib.flc_topk_shift_reduce_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
         lib.flc_topk_shift_reduce_workspace_size.restype = sz
         lib.flc_topk_shift_reduce.argtypes = [P(FlcCodecParams), P(FlcShiftRows), i64, i64, vp, f32, vp, vp, sz, vp]
+    if hasattr(lib, "flc_encode_shift_reduce_sampled"):   # (absent from A/B builds of older revisions)
+        lib.flc_encode_shift_reduce_sampled_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_encode_shift_reduce_sampled_workspace_size.restype = sz
+        lib.flc_encode_shift_reduce_sampled.argtypes = [P(FlcCodecParams), P(FlcPattern), P(FlcShiftRows), P(FlcRowMap),
+                                                        i64, i64, vp, f32, vp, vp, vp, sz, vp]
+        lib.flc_randk_shift_reduce_sampled_workspace_size.argtypes = [P(FlcCodecParams), P(FlcPattern), i64, i64]
+        lib.flc_randk_shift_reduce_sampled_workspace_size.restype = sz
+        lib.flc_randk_shift_reduce_sampled.argtypes = [P(FlcCodecParams), P(FlcPattern), P(FlcShiftRows), P(FlcRowMap),
+                                                       i64, i64, vp, f32, vp, vp, sz, vp]
+        lib.flc_topk_shift_reduce_sampled_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_topk_shift_reduce_sampled_workspace_size.restype = sz
+        lib.flc_topk_shift_reduce_sampled.argtypes = [P(FlcCodecParams), P(FlcShiftRows), P(FlcRowMap), i64, i64, vp, f32,
+                                                      vp, vp, sz, vp]
     if hasattr(lib, "flc_dither_shift_reduce"):     # (absent from A/B builds of older revisions)
         lib.flc_dither_shift_reduce_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
         lib.flc_dither_shift_reduce_workspace_size.restype = sz
@@ -294,6 +321,8 @@ def _bind(lib):
                         "flc_encode_reduce_ex_workspace_size", "flc_encode_shift_workspace_size",
                         "flc_encode_shift_reduce_workspace_size", "flc_randk_shift_reduce_workspace_size",
                         "flc_topk_shift_reduce_workspace_size", "flc_dither_shift_reduce_workspace_size",
+                        "flc_encode_shift_reduce_sampled_workspace_size", "flc_randk_shift_reduce_sampled_workspace_size",
+                        "flc_topk_shift_reduce_sampled_workspace_size",
                         "flc_frecon_reduce_workspace_size", "flc_payload_bytes", "flc_pack_workspace_size",
                         "flc_pack_shift_workspace_size", "flc_unpack_shift_reduce_workspace_size",
                         "flc_unpack_reduce_workspace_size", "flc_combine_workspace_size",

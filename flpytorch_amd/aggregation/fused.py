@@ -276,10 +276,27 @@ def _shift_mode(sparse, batched, one_read):
     return "one_read" if one_read else "batched" if batched else "sparse" if sparse else None
 
 
-def _shift_workspace_size(lib, mode, prm, pat, n, d):
+def _shift_workspace_size(lib, mode, prm, pat, n, d, sampled=False):
     entry, _, size_pat, _ = _SHIFT_MODES[mode]
     args = (ctypes.byref(prm), ctypes.byref(pat), n, d) if size_pat else (ctypes.byref(prm), n, d)
-    return getattr(lib, entry + "_workspace_size")(*args)
+    return getattr(lib, entry + ("_sampled" if sampled else "") + "_workspace_size")(*args)
+
+
+# ShiftUplinkReducer's per-row operands other than a, by keyword, with their flc_row_map.indexed bits
+_IDX_BITS = {"b": _lib.FLC_IDX_B, "base": _lib.FLC_IDX_BASE, "msg_out": _lib.FLC_IDX_MSG, "shift": _lib.FLC_IDX_SHIFT_IN,
+             "shift_out": _lib.FLC_IDX_SHIFT_OUT}
+
+
+def _client_ids(who, clients, n):
+    """The participants of a sampled round as a list of distinct non-negative ints, one per row of a."""
+    ids = [int(c) for c in (clients.tolist() if hasattr(clients, "tolist") else clients)]
+    if len(ids) != n:
+        raise ValueError(f"{who}: clients must name one client per row of a ({n}), got {len(ids)}")
+    if any(c < 0 or c > 0x7FFFFFFF for c in ids):
+        raise ValueError(f"{who}: client ids must be in [0, 2^31)")
+    if len(set(ids)) != len(ids):
+        raise ValueError(f"{who}: a client takes part in a round once (duplicate ids in clients)")
+    return ids
 
 
 class ShiftUplinkReducer:
@@ -311,7 +328,15 @@ class ShiftUplinkReducer:
     epilogue and a list fold — a constant number of launches instead of N lone selections.  Same
     four shapes, same contract and same bits as ``sparse=True`` states them for RandK (unselected
     elements of the in-place operand are not written); any other compressor or shape raises
-    ``NotImplementedError``."""
+    ``NotImplementedError``.
+
+    ``clients=[...]`` runs a SAMPLED round (partial participation; the ``_sampled`` entries): ``a`` holds
+    the [n, D] gradients of the n participants, in order, and participant i is client ``clients[i]`` of
+    the ``N_total`` resident ones.  An operand named in ``indexed`` is an [N_total, D] state matrix whose
+    row for participant i is row ``clients[i]``; the others stay [n, D] in participant order, like the
+    patterns, ``weights`` and ``pnorms_out``.  Draws are those of client ``client0 + clients[i]``, so a
+    client's row does not depend on who else takes part, and rows of an indexed operand outside
+    ``clients`` are neither read nor written."""
 
     def __init__(self, compressor: Compressor, device=None, seed=None):
         _lib.require_gpu()
@@ -325,18 +350,21 @@ class ShiftUplinkReducer:
             prm.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
         return prm, keep
 
-    def workspace_bytes(self, n, d, sparse=False, compat=False, batched=False, one_read=False):
+    def workspace_bytes(self, n, d, sparse=False, compat=False, batched=False, one_read=False, sampled=False):
         """``sparse``: flc_randk_shift_reduce's workspace (``compat``: with numpy-stream index rows);
         ``batched``: flc_topk_shift_reduce's (the selection state, then the [n, d] difference matrix);
-        ``one_read``: flc_dither_shift_reduce's (the sparse QSGD pipeline's state, no [n, d] matrix)."""
+        ``one_read``: flc_dither_shift_reduce's (the sparse QSGD pipeline's state, no [n, d] matrix);
+        ``sampled``: the ``clients=`` form of the general, ``sparse`` or ``batched`` round (n participants)."""
+        if sampled and one_read:
+            raise NotImplementedError("ShiftUplinkReducer: the one-read QSGD round has no sampled form")
         prm, _ = self.params()
         pat = _lib.FlcPattern()
         pat.d_randk_idx = 1 if compat else None                 # (the size query only tells the modes apart)
-        return _shift_workspace_size(_lib.load(), _shift_mode(sparse, batched, one_read), prm, pat, n, d)
+        return _shift_workspace_size(_lib.load(), _shift_mode(sparse, batched, one_read), prm, pat, n, d, sampled)
 
     def __call__(self, a, b, *, scale=1.0, base=None, msg_out=None, alpha=None, shift=None, shift_out=None, out=None,
                  weights=None, divisor=None, client0=0, randk_idx=None, uniforms=None, lazy_u=None, pnorms_out=None,
-                 stream=None, sparse=False, randk_counts=None, batched=False, one_read=False):
+                 stream=None, sparse=False, randk_counts=None, batched=False, one_read=False, clients=None, indexed=None):
         """a, b: [N, D] fp32 row-contiguous device matrices (local gradients; shifts / previous
         estimators / previous gradients).  ``base``: None, [N, D], or ONE [D] vector for every row
         (MARINA's g_prev).  ``msg_out``: None (the messages are not stored) or [N, D]; it may be ``b``
@@ -361,7 +389,19 @@ class ShiftUplinkReducer:
         ``pnorms_out`` is supported.  ``NotImplementedError`` for another compressor, before any operand
         is looked at, or when the library refuses the call (MARINA's shared base, a dense path hint, a
         candidate share past the staging capacity) — no silent fallback; together with ``sparse``,
-        ``batched``, ``uniforms`` or ``randk_counts`` it is a ``ValueError``."""
+        ``batched``, ``uniforms`` or ``randk_counts`` it is a ``ValueError``.
+        ``clients``: a host sequence of n distinct client ids, the class docstring's sampled round
+        (``ValueError`` for a duplicate or an id outside the state matrices).  ``indexed``: a tuple of
+        names from ("b", "base", "msg_out", "shift", "shift_out"), the operands that are [N_total, D]
+        state matrices; by default every per-row operand passed other than ``a``, except a shared [D]
+        base.  An indexed ``shift`` needs ``shift_out`` (the state is updated in place, or into a given
+        matrix).  ``client0`` still offsets the key; ``sparse`` / ``batched`` route to their sampled
+        entries; ``one_read`` or ``randk_counts`` with ``clients`` raise ``NotImplementedError``."""
+        if clients is None and indexed is not None:
+            raise ValueError("ShiftUplinkReducer: indexed names operands of a sampled round (clients=...)")
+        if clients is not None and (one_read or randk_counts is not None):
+            raise NotImplementedError("ShiftUplinkReducer: a sampled round (clients=...) has no one_read form and takes no "
+                                      "randk_counts (they are keyed by position, not by client id)")
         if one_read:
             if sparse or batched or uniforms is not None or randk_counts is not None:
                 raise ValueError("ShiftUplinkReducer: one_read=True takes no sparse, batched, uniforms or randk_counts "
@@ -382,7 +422,7 @@ class ShiftUplinkReducer:
         if randk_counts is not None and not sparse:
             raise ValueError("ShiftUplinkReducer: randk_counts is read by the sparse round only (sparse=True)")
         args = (a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx, uniforms,
-                lazy_u, pnorms_out, sparse, randk_counts, batched, one_read)
+                lazy_u, pnorms_out, sparse, randk_counts, batched, one_read, clients, indexed)
         if stream is not None:
             if stream.device != self.device:
                 raise ValueError(f"stream is on {stream.device}, the reducer runs on {self.device}")
@@ -391,14 +431,20 @@ class ShiftUplinkReducer:
         return self._run(*args)
 
     def _run(self, a, b, scale, base, msg_out, alpha, shift, shift_out, out, weights, divisor, client0, randk_idx,
-             uniforms, lazy_u, pnorms_out, sparse=False, randk_counts=None, batched=False, one_read=False):
+             uniforms, lazy_u, pnorms_out, sparse=False, randk_counts=None, batched=False, one_read=False, clients=None,
+             indexed=None):
         lib = _lib.load()
         who = "ShiftUplinkReducer"
         mode = _shift_mode(sparse, batched, one_read)
         entry, takes_pat, _, takes_pnorms = _SHIFT_MODES[mode]
+        sampled = clients is not None
+        if sampled:
+            entry += "_sampled"
         for name in ("flc_encode_shift_reduce", entry):
             if not hasattr(lib, name):
                 raise NotImplementedError(f"this library build has no {name}")
+        if sampled and alpha is not None and shift_out is None and (indexed is None or "shift" in indexed):
+            raise ValueError(f"{who}: an indexed shift is updated in place or into a given matrix (pass shift_out)")
         if mode and alpha is not None and shift_out is None:
             raise NotImplementedError(f"{who}: {mode}=True updates the shift in place (shift_out = shift = b)")
         dev = self.device
@@ -409,8 +455,31 @@ class ShiftUplinkReducer:
         if a.dim() != 2:
             raise ValueError(f"{who}: a must be an [N, D] matrix")
         n, d = a.shape
+        ids, idx_names, n_total = None, (), n
+        if sampled:
+            ids = _client_ids(who, clients, n)
+            given = {"b": b, "base": base, "msg_out": msg_out, "shift": shift, "shift_out": shift_out}
+            if indexed is None:
+                idx_names = tuple(k for k, v in given.items() if v is not None and not (k == "base" and v.dim() == 1))
+            else:
+                idx_names = tuple(indexed)
+                for k in idx_names:
+                    if k not in _IDX_BITS:
+                        raise ValueError(f"{who}: indexed names {sorted(_IDX_BITS)}, got {k!r}")
+                    if given[k] is None:
+                        raise ValueError(f"{who}: indexed operand {k} is not given")
+                    if k == "base" and base.dim() == 1:
+                        raise ValueError(f"{who}: a shared [D] base is never indexed")
+            totals = {int(given[k].shape[0]) for k in idx_names if given[k].dim() == 2}
+            if len(totals) > 1:
+                raise ValueError(f"{who}: the indexed operands must all be [N_total, {d}] (got row counts {sorted(totals)})")
+            n_total = totals.pop() if totals else (max(ids) + 1 if ids else 1)
+            if ids and max(ids) >= n_total:
+                raise ValueError(f"{who}: client id {max(ids)} outside the [{n_total}, {d}] state matrices")
 
         def rows(name, v):
+            if name in idx_names:
+                return _row_matrix(who, name, v, n_total, d, like=" (an indexed state matrix)")
             return _row_matrix(who, name, v, n, d, like=" like a")
         sr = _lib.FlcShiftRows()
         sr.d_a, sr.lda = rows("a", a)
@@ -455,9 +524,17 @@ class ShiftUplinkReducer:
             _pattern_counts(pat, randk_counts, n, d)
         if d > 0:
             vp = ctypes.c_void_p
-            ws = _lib.WORKSPACE.get(dev, _shift_workspace_size(lib, mode, prm, pat, n, d))
-            args = [ctypes.byref(prm)] + ([ctypes.byref(pat)] if takes_pat else []) + \
-                   [ctypes.byref(sr), n, d, vp(w_ptr), ctypes.c_float(total)]
+            ws = _lib.WORKSPACE.get(dev, _shift_workspace_size(lib, mode, prm, pat, n, d, sampled))
+            args = [ctypes.byref(prm)] + ([ctypes.byref(pat)] if takes_pat else []) + [ctypes.byref(sr)]
+            if sampled:
+                h_ids = np.asarray(ids, dtype=np.int32)
+                d_ids = torch.from_numpy(h_ids).to(dev)
+                keep += [h_ids, d_ids]
+                rmap = _lib.FlcRowMap()
+                rmap.h_ids, rmap.d_ids, rmap.n_total = h_ids.ctypes.data, d_ids.data_ptr(), n_total
+                rmap.indexed = sum(_IDX_BITS[k] for k in set(idx_names))
+                args.append(ctypes.byref(rmap))
+            args += [n, d, vp(w_ptr), ctypes.c_float(total)]
             if takes_pnorms:
                 args.append(vp(pnorms_out.data_ptr() if pnorms_out is not None else None))
             with torch.cuda.device(dev):
@@ -513,7 +590,7 @@ class FreconUplinkReducer:
 
     def __call__(self, G, H, P, alpha, *, server=None, weights=None, divisor=None, client0=0, randk_idx=None,
                  uniforms=None, lazy_u=None, out_u=None, out_q=None, pnorms_u_out=None, pnorms_q_out=None, stream=None,
-                 sparse=False, batched=False):
+                 sparse=False, batched=False, clients=None):
         """G, H, P: [N, D] fp32 row-contiguous device matrices (the local gradients, the clients'
         shifts — updated in place — and the gradients at the previous iterate).  ``server``: None or
         a dict with ``lambda_``, ``g_server_prev`` and ``h_prev`` ([D] device vectors), optionally
@@ -521,7 +598,10 @@ class FreconUplinkReducer:
         ``h_prev`` itself, else into a new vector) and ``out`` for the result.  Patterns, ``weights``,
         ``divisor``, ``client0`` and ``stream`` as in ``ShiftUplinkReducer``.  Returns
         ``(u_avg, q_avg, result, h_prev_new)``, the last two None without ``server`` /
-        ``alpha_update``."""
+        ``alpha_update``.  ``clients`` (a sampled round) raises ``NotImplementedError``: flc_frecon_reduce
+        has no sampled form."""
+        if clients is not None:
+            raise NotImplementedError("FreconUplinkReducer: the two-message round has no sampled form (clients=...)")
         args = (G, H, P, alpha, server, weights, divisor, client0, randk_idx, uniforms, lazy_u, out_u, out_q,
                 pnorms_u_out, pnorms_q_out, sparse, batched)
         if stream is not None:

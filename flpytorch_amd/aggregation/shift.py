@@ -109,7 +109,13 @@ def dianaUplink(compressor, G, H, alpha, *, seed=None, **kw):
     ``NotImplementedError``) runs the round through ``flc_dither_shift_reduce``: ``G`` and ``H`` are read
     once by the sparse QSGD pipeline over ``G_i - H_i`` and ``H_i`` is written only where
     ``C_i(G_i - H_i)`` is nonzero.  The same contract with "selected" read as "encoded value nonzero";
-    ``ef21Uplink`` takes it too."""
+    ``ef21Uplink`` takes it too.
+
+    ``clients=[...]`` (partial participation): ``H`` is the [N_total, D] state of all resident clients and
+    ``G`` the [n, D] gradients of the n participants, in order; only the rows ``H[clients[i]]`` are read
+    and updated, under the draws of client ``client0 + clients[i]``.  Same bits as n in-place client
+    steps on those rows; ``sparse`` / ``batched`` keep their contract, ``one_read`` raises
+    ``NotImplementedError``.  ``ef21Uplink`` and ``cofigUplink`` take it the same way."""
     out, _, _ = _uplink(compressor, G, seed)(G, H, alpha=alpha, shift=H, shift_out=H, **kw)
     return out
 
@@ -134,10 +140,14 @@ def marinaUplink(compressor, G_cur, G_prev_rows, g_prev, *, seed=None, **kw):
     with ONE shared ``g_prev`` [D] vector; no message is stored.  ``sparse=True`` (RandK only): no row is
     read outside its index set; the fold is bit-identical to the general call's without condition.
     ``batched=True`` (TopK only): the round through ``flc_topk_shift_reduce``, bit-identical as well.
-    ``one_read=True`` raises ``NotImplementedError``: the one-read QSGD round does not take a shared base yet."""
+    ``one_read=True`` raises ``NotImplementedError``: the one-read QSGD round does not take a shared base yet.
+    ``clients=[...]`` (PP-MARINA's compressed round): both gradient matrices are fresh per round and stay
+    [n, D] in participant order; nothing is indexed, only the draws are keyed by ``client0 + clients[i]``."""
     if kw.get("one_read"):
         raise NotImplementedError("marinaUplink: one_read=True (flc_dither_shift_reduce) does not take MARINA's shared "
                                   "base yet; use the general round")
+    if kw.get("clients") is not None:
+        kw.setdefault("indexed", ())
     out, _, _ = _uplink(compressor, G_cur, seed)(G_cur, G_prev_rows, base=g_prev, **kw)
     return out
 
@@ -163,8 +173,12 @@ def freconUplink(compressor, G, H, P, alpha, lambda_, g_server_prev, h_prev, alp
     expressions.  Elementwise codecs run ``flc_frecon_reduce`` (one kernel, ``G`` read once per
     pass); RandK / TopK / Rank-K are composed from ``ShiftUplinkReducer``'s rounds (``sparse=True``
     / ``batched=True`` under ``dianaUplink``'s rules).  ``kw``: ``FreconUplinkReducer.__call__``'s
-    weights / divisor / client0 / patterns / out_u / out_q / stream / sparse / batched."""
+    weights / divisor / client0 / patterns / out_u / out_q / stream / sparse / batched.  ``clients=`` raises
+    ``NotImplementedError``: flc_frecon_reduce has no sampled form."""
     from .fused import FreconUplinkReducer
+    if kw.get("clients") is not None:
+        raise NotImplementedError("freconUplink: the two-message round has no sampled form (clients=...)")
+    kw.pop("clients", None)
     if seed is None and compressor.device_rng is not None:
         seed = compressor.device_rng[0]
     server = {"lambda_": lambda_, "g_server_prev": g_server_prev, "h_prev": h_prev}

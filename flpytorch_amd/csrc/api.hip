@@ -144,6 +144,62 @@ static int outputs_overlap(const char* me, std::initializer_list<OutRows> outs, 
     return FLC_OK;
 }
 
+// The row map of a _sampled entry against the round's normalised operands sr (shift_rows_prepare),
+// everything decided on the host before any launch.  *m: the copy the round hosts work on, the bits
+// of absent operands (and of a shift_in nobody stores from) cleared.
+static int row_map_check(const char* me, const flc_row_map* map, const flc_shift_rows& sr, int64_t n, int64_t d,
+                         flc_row_map* m) {
+    if (!map || !map->h_ids || !map->d_ids) { set_error("%s: need map, h_ids and d_ids", me); return FLC_ERR_ARG; }
+    *m = *map;
+    const uint32_t all = FLC_IDX_B | FLC_IDX_BASE | FLC_IDX_MSG | FLC_IDX_SHIFT_IN | FLC_IDX_SHIFT_OUT;
+    if (m->indexed & ~all) { set_error("%s: unknown bits 0x%x in map->indexed", me, (unsigned)(m->indexed & ~all)); return FLC_ERR_ARG; }
+    if (m->n_total < 1 || m->n_total > (int64_t)INT32_MAX) { set_error("%s: n_total=%lld", me, (long long)m->n_total); return FLC_ERR_ARG; }
+    if ((m->indexed & FLC_IDX_BASE) && sr.d_base && sr.ldbase == 0) {
+        set_error("%s: FLC_IDX_BASE with a shared base (ldbase == 0)", me);
+        return FLC_ERR_ARG;
+    }
+    if (!sr.d_base) m->indexed &= ~(uint32_t)FLC_IDX_BASE;
+    if (!sr.d_msg) m->indexed &= ~(uint32_t)FLC_IDX_MSG;
+    if (!sr.d_shift_out) m->indexed &= ~(uint32_t)(FLC_IDX_SHIFT_IN | FLC_IDX_SHIFT_OUT);
+    for (int64_t i = 0; i < n; ++i)
+        if (m->h_ids[i] < 0 || (int64_t)m->h_ids[i] >= m->n_total) {
+            set_error("%s: ids[%lld]=%d outside [0, n_total=%lld)", me, (long long)i, (int)m->h_ids[i], (long long)m->n_total);
+            return FLC_ERR_ARG;
+        }
+    struct Op { const char* name; const float* p; int64_t ld; uint32_t bit; };
+    const Op outs[2] = {{"d_msg", sr.d_msg, sr.ldmsg, FLC_IDX_MSG}, {"d_shift_out", sr.d_shift_out, sr.ldout, FLC_IDX_SHIFT_OUT}};
+    const Op ins[3] = {{"d_b", sr.d_b, sr.ldb, FLC_IDX_B}, {"d_base", sr.d_base, sr.ldbase, FLC_IDX_BASE},
+                       {"d_shift_in", sr.d_shift_in, sr.ldin, FLC_IDX_SHIFT_IN}};
+    if (m->indexed & (FLC_IDX_MSG | FLC_IDX_SHIFT_OUT)) {       // two participants would store into one row
+        std::vector<int32_t> s(m->h_ids, m->h_ids + n);
+        std::sort(s.begin(), s.end());
+        for (int64_t i = 1; i < n; ++i)
+            if (s[i] == s[i - 1]) { set_error("%s: id %d twice with an indexed output", me, (int)s[i]); return FLC_ERR_ARG; }
+    }
+    for (const Op& o : outs) {
+        if (!o.p) continue;
+        if ((m->indexed & o.bit) && m->n_total > 1 && (o.ld < 0 ? -o.ld : o.ld) < d) {
+            set_error("%s: the indexed %s rows overlap (|ld| < d)", me, o.name);
+            return FLC_ERR_ARG;
+        }
+        for (const Op& in : ins)
+            if (in.p == o.p && in.ld == o.ld && !(m->indexed & in.bit) != !(m->indexed & o.bit)) {
+                set_error("%s: %s is %s in place, but only one of them is indexed", me, o.name, in.name);
+                return FLC_ERR_ARG;
+            }
+    }
+    return FLC_OK;
+}
+
+// an output matrix's row count for the overlap checks: n_total where it is indexed
+static int sampled_outputs_overlap(const char* me, const flc_shift_rows& sr, const flc_row_map& m, int64_t n, int64_t d) {
+    if (int rc = outputs_overlap(me, {{"d_msg", "ldmsg", sr.d_msg, sr.ldmsg}}, sr.d_base, sr.ldbase,
+                                 (m.indexed & FLC_IDX_MSG) ? m.n_total : n, d))
+        return rc;
+    return outputs_overlap(me, {{"d_shift_out", "ldout", sr.d_shift_out, sr.ldout}}, sr.d_base, sr.ldbase,
+                           (m.indexed & FLC_IDX_SHIFT_OUT) ? m.n_total : n, d);
+}
+
 }  // namespace flc
 
 using namespace flc;
@@ -449,6 +505,77 @@ extern "C" int flc_topk_shift_reduce(const flc_codec_params* prm, const flc_shif
     if (int rc = shift_rows_prepare(me, prm, rows, n, d, d_out, &sr, &empty)) return rc;
     if (empty) return FLC_OK;
     return topk_shift_run(prm, sr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+// ---- partial participation: the three rounds over sampled client rows (flc_row_map) ----------------
+extern "C" size_t flc_encode_shift_reduce_sampled_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (!prm || !known(prm->codec) || n < 0 || d < 0) return 0;
+    return shift_reduce_workspace(prm, n, d);       // the ids are the caller's: nothing is added
+}
+
+extern "C" int flc_encode_shift_reduce_sampled(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
+                                               const flc_row_map* map, int64_t n, int64_t d, const float* d_w, float w_total,
+                                               float* d_pnorms_out, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_encode_shift_reduce_sampled";
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (int rc = bad_params(prm, me)) return rc;
+    flc_shift_rows sr;
+    bool empty;
+    if (int rc = shift_rows_prepare(me, nullptr, rows, n, d, d_out, &sr, &empty)) return rc;
+    if (empty) return FLC_OK;
+    flc_row_map m;
+    if (int rc = row_map_check(me, map, sr, n, d, &m)) return rc;
+    if (int rc = sampled_outputs_overlap(me, sr, m, n, d)) return rc;
+    return shift_reduce_run(prm, pat, sr, n, d, d_w, w_total, d_pnorms_out, d_out, d_ws, ws_bytes, (hipStream_t)stream, &m);
+}
+
+extern "C" size_t flc_randk_shift_reduce_sampled_workspace_size(const flc_codec_params* prm, const flc_pattern* pat, int64_t n,
+                                                                int64_t d) {
+    if (!prm || prm->codec != FLC_RANDK || n < 0 || d < 0) return 0;
+    return randk_shift_workspace(prm, pat && pat->d_randk_idx, n, d, /*sampled=*/true);
+}
+
+extern "C" int flc_randk_shift_reduce_sampled(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
+                                              const flc_row_map* map, int64_t n, int64_t d, const float* d_w, float w_total,
+                                              float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_randk_shift_reduce_sampled";
+    if (!prm || prm->codec != FLC_RANDK) {
+        set_error("%s: only FLC_RANDK has a sparse shifted round (use flc_encode_shift_reduce_sampled)", me);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    flc_shift_rows sr;
+    bool empty;
+    if (int rc = shift_rows_prepare(me, nullptr, rows, n, d, d_out, &sr, &empty)) return rc;
+    if (empty) return FLC_OK;
+    flc_row_map m;
+    if (int rc = row_map_check(me, map, sr, n, d, &m)) return rc;
+    if (pat && pat->d_randk_counts) {
+        set_error("%s: d_randk_counts are keyed by position, not by client id (the entry computes its counts)", me);
+        return FLC_ERR_ARG;
+    }
+    return randk_shift_run(prm, pat, sr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream, &m);
+}
+
+extern "C" size_t flc_topk_shift_reduce_sampled_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (!prm || prm->codec != FLC_TOPK || n < 0 || d < 0) return 0;
+    return topk_shift_workspace(prm, n, d, /*sampled=*/true);
+}
+
+extern "C" int flc_topk_shift_reduce_sampled(const flc_codec_params* prm, const flc_shift_rows* rows, const flc_row_map* map,
+                                             int64_t n, int64_t d, const float* d_w, float w_total, float* d_out,
+                                             void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_topk_shift_reduce_sampled";
+    if (!prm || prm->codec != FLC_TOPK) {
+        set_error("%s: only FLC_TOPK has a batched shifted round (use flc_encode_shift_reduce_sampled)", me);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    flc_shift_rows sr;
+    bool empty;
+    if (int rc = shift_rows_prepare(me, prm, rows, n, d, d_out, &sr, &empty)) return rc;
+    if (empty) return FLC_OK;
+    flc_row_map m;
+    if (int rc = row_map_check(me, map, sr, n, d, &m)) return rc;
+    return topk_shift_run(prm, sr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream, &m);
 }
 
 extern "C" size_t flc_dither_shift_reduce_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {

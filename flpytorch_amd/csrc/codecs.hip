@@ -53,14 +53,15 @@ __device__ inline double ncomb(double a, double b) {
 // nonzero |v| below 2^-80: the row cannot use the unguarded fast division (div_fast)
 __device__ inline uint32_t is_tiny(float v) { const float a = fabsf(v); return (a != 0.f && a < 0x1p-80f) ? 1u : 0u; }
 
-// DIFF: row i is the fp32 difference src.row(i) - subs.row(i) (the shift codecs' C(a_i - b_i))
-template <int NORM, bool VEC, bool DIFF, bool KEEP = false>
+// DIFF: row i is the fp32 difference src.row(i) - subs.row(i) (the shift codecs' C(a_i - b_i));
+// M (a sampled round whose b rows are indexed): the subtracted row is the participant's client row
+template <int NORM, bool VEC, bool DIFF, bool KEEP = false, class M = MapNone>
 __global__ __launch_bounds__(256) void k_norm_partials(RowSrc src, RowSrc subs, int64_t d,
                                                        int64_t parts, int64_t plen, double* __restrict__ partial,
-                                                       uint32_t* __restrict__ tinyp) {
+                                                       uint32_t* __restrict__ tinyp, M map) {
     const int64_t row = blockIdx.y;
     const float* r = src.row(row);
-    const float* sub = DIFF ? subs.row(row) : nullptr;
+    const float* sub = DIFF ? subs.row(M::ON ? map.at_s(row, FLC_IDX_B) : row) : nullptr;
     auto ld1 = [&](int64_t j) -> float { return DIFF ? r[j] - sub[j] : r[j]; };
     __shared__ double red[4];
     __shared__ uint32_t redt[4];
@@ -116,13 +117,13 @@ __global__ __launch_bounds__(256) void k_norm_partials(RowSrc src, RowSrc subs, 
 
 // Per row: the norm, RN(1/norm), rowfast = 1 when the encode may divide by the norm with the
 // unguarded div_fast (norm inside [2^-40, 2^80], no nonzero element below 2^-80), and the
-// device-RNG row key.
-template <int NORM>
+// device-RNG row key (M: of the participant's client id).
+template <int NORM, class M = MapNone>
 __global__ __launch_bounds__(64) void k_norm_final(const double* __restrict__ partial,
                                                    const uint32_t* __restrict__ tinyp, int64_t parts,
                                                    int64_t n, float* __restrict__ pn, float* __restrict__ rpn,
                                                    uint32_t* __restrict__ rowfast, uint64_t seed, int64_t client0,
-                                                   uint32_t* __restrict__ rk) {
+                                                   uint32_t* __restrict__ rk, M map) {
     const int64_t row = blockIdx.x;
     if (row >= n) return;
     double a = 0.0;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(64) void k_norm_final(const double* __restrict__ pa
         pn[row] = v;
         rpn[row] = 1.0f / v;
         rowfast[row] = (!tiny && v >= 0x1p-40f && v <= 0x1p80f) ? 1u : 0u;
-        rk[row] = rowkey(client_key(seed, client0 + row));
+        rk[row] = rowkey(client_key(seed, client0 + (M::ON ? map.id_s(row) : row)));
     }
 }
 
@@ -162,7 +163,7 @@ int64_t norm_parts(int64_t n, int64_t d) { const int64_t l = norm_part_len(n, d)
 
 int launch_norms(RowSrc src, bool vec, int64_t n, int64_t d, int norm, double* partial, uint32_t* tinyp,
                  float* pn, float* rpn, uint32_t* rowfast, uint64_t seed, int64_t client0, uint32_t* rk,
-                 hipStream_t st, const RowSrc* subp) {
+                 hipStream_t st, const RowSrc* subp, const flc_row_map* map) {
     const bool sub = subp != nullptr;   // the rows subtracted before the norm (vec: they are aligned too)
     const RowSrc subs = sub ? *subp : RowSrc{nullptr, 0, nullptr};
     const int64_t parts = norm_parts(n, d), plen = norm_part_len(n, d);
@@ -175,15 +176,22 @@ int launch_norms(RowSrc src, bool vec, int64_t n, int64_t d, int norm, double* p
     }
     // blocks per row: up to 64 for many rows, more when the rows are few (all parts in flight)
     dim3 grid((unsigned)std::min<int64_t>(parts, std::max<int64_t>(64, 4096 / std::max<int64_t>(n, 1))), (unsigned)n);
+    const bool msub = sub && map_has(map, FLC_IDX_B);   // a sampled round: the subtracted rows by client id
+    const MapIds mi = map ? map_ids(map) : MapIds{nullptr, 0u};
+    const MapNone mn{};
 #define FLC_NORM_CASE(NK)                                                                           \
     { ProfScope _ps("k_norm_partials", st);                                                         \
-    if (sub && vec) hipLaunchKernelGGL((k_norm_partials<NK, true, true>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp); \
-    else if (sub) hipLaunchKernelGGL((k_norm_partials<NK, false, true>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp); \
-    else if (vec) hipLaunchKernelGGL((k_norm_partials<NK, true, false>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp); \
-    else hipLaunchKernelGGL((k_norm_partials<NK, false, false>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp); } \
+    if (msub && vec) hipLaunchKernelGGL((k_norm_partials<NK, true, true, false, MapIds>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp, mi); \
+    else if (msub) hipLaunchKernelGGL((k_norm_partials<NK, false, true, false, MapIds>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp, mi); \
+    else if (sub && vec) hipLaunchKernelGGL((k_norm_partials<NK, true, true>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp, mn); \
+    else if (sub) hipLaunchKernelGGL((k_norm_partials<NK, false, true>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp, mn); \
+    else if (vec) hipLaunchKernelGGL((k_norm_partials<NK, true, false>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp, mn); \
+    else hipLaunchKernelGGL((k_norm_partials<NK, false, false>), grid, dim3(256), 0, st, src, subs, d, parts, plen, partial, tinyp, mn); } \
     FLC_CHECK_LAUNCH("k_norm_partials");                                                            \
-    hipLaunchKernelGGL((k_norm_final<NK>), dim3((unsigned)n), dim3(64), 0, st, partial, tinyp, parts, n, pn, rpn,   \
-                       rowfast, seed, client0, rk);                                                 \
+    if (map) hipLaunchKernelGGL((k_norm_final<NK, MapIds>), dim3((unsigned)n), dim3(64), 0, st, partial, tinyp, parts, n, pn, rpn, \
+                                rowfast, seed, client0, rk, mi);                                    \
+    else hipLaunchKernelGGL((k_norm_final<NK>), dim3((unsigned)n), dim3(64), 0, st, partial, tinyp, parts, n, pn, rpn,   \
+                            rowfast, seed, client0, rk, mn);                                        \
     FLC_CHECK_LAUNCH("k_norm_final");
     if (norm == FLC_NORM_L2) { FLC_NORM_CASE(FLC_NORM_L2) }
     else if (norm == FLC_NORM_L1) { FLC_NORM_CASE(FLC_NORM_L1) }
@@ -651,10 +659,14 @@ __device__ inline float4 shift_msg4(float4 e, float scale, bool has_base, float4
     return has_base ? make_float4(bs.x + t.x, bs.y + t.y, bs.z + t.z, bs.w + t.w) : t;
 }
 
-template <class Op, int COLS, int PF, bool W>
+// M = MapIds (flc_encode_shift_reduce_sampled): participant i's row of an indexed operand is its
+// client's, ids[i] — wave-uniform, read through the scalar cache TWO ring turns ahead (rnext), behind
+// the refill's vector loads: the prefetch of row i + PF finds its id in a register and does not wait for
+// a scalar load's round trip in front of the row's vector loads.
+template <class Op, int COLS, int PF, bool W, class M = MapNone>
 __global__ __launch_bounds__(256) void k_ew_shift_accum(flc_shift_rows sr, int base_mode, int hin_b, int64_t n,
                                                         int64_t d, Op op, const float* __restrict__ levels, int s,
-                                                        const float* __restrict__ w, float wt, float* out) {
+                                                        const float* __restrict__ w, float wt, float* out, M map) {
     extern __shared__ __attribute__((aligned(16))) float4 smem_tab[];
     if (Op::TABLE) op.set_table_ok(load_table(levels, s, smem_tab));
     const int64_t groups = d / 4;
@@ -674,11 +686,18 @@ __global__ __launch_bounds__(256) void k_ew_shift_accum(flc_shift_rows sr, int b
             shared_bs[c] = (base_mode == BASE_SHARED && ok[c]) ? reinterpret_cast<const float4*>(sr.d_base)[gi[c]] : zero4;
         }
         float4 ra[PF][COLS], rb[PF][COLS];
+        int64_t rid[PF];             // M::ON: the client id of the row in ring slot p ...
+        int32_t rnext[PF];           // ... and of the slot's next row, as loaded (widened a turn later: no wait here)
 #pragma unroll
         for (int p = 0; p < PF; ++p) {
             if (p < n) {
+                if (M::ON) {
+                    rid[p] = map.id_s(p);
+                    rnext[p] = map.raw_s(min((int64_t)p + PF, n - 1));
+                }
+                const int64_t rowb = map.has(FLC_IDX_B) ? rid[p] : (int64_t)p;
                 const float4* pa = reinterpret_cast<const float4*>(sr.d_a + p * sr.lda);
-                const float4* pb = reinterpret_cast<const float4*>(sr.d_b + p * sr.ldb);
+                const float4* pb = reinterpret_cast<const float4*>(sr.d_b + rowb * sr.ldb);
 #pragma unroll
                 for (int c = 0; c < COLS; ++c) {
                     ra[p][c] = ok[c] ? ld_row4(pa + gi[c]) : zero4;
@@ -694,16 +713,22 @@ __global__ __launch_bounds__(256) void k_ew_shift_accum(flc_shift_rows sr, int b
                 if (i < n) {
                     op.setup(i);
                     const float wi = W ? w[i] : 1.f;
+                    // the row of each operand: the participant's, or its client's where the operand is indexed
+                    const int64_t ci = M::ON ? rid[p] : i;
+                    const int64_t i_base = map.has(FLC_IDX_BASE) ? ci : i;
+                    const int64_t i_msg = map.has(FLC_IDX_MSG) ? ci : i;
+                    const int64_t i_hin = map.has(FLC_IDX_SHIFT_IN) ? ci : i;
+                    const int64_t i_hout = map.has(FLC_IDX_SHIFT_OUT) ? ci : i;
                     // the row's remaining loads (operands that are not the b rows), before any store
                     float4 bs[COLS], hv[COLS], v[COLS];
 #pragma unroll
                     for (int c = 0; c < COLS; ++c) {
                         bs[c] = base_mode == BASE_B ? rb[p][c] : shared_bs[c];
                         if (base_mode == BASE_ROWS)
-                            bs[c] = ok[c] ? reinterpret_cast<const float4*>(sr.d_base + i * sr.ldbase)[gi[c]] : zero4;
+                            bs[c] = ok[c] ? reinterpret_cast<const float4*>(sr.d_base + i_base * sr.ldbase)[gi[c]] : zero4;
                         hv[c] = rb[p][c];
                         if (sr.d_shift_out && !hin_b)
-                            hv[c] = ok[c] ? reinterpret_cast<const float4*>(sr.d_shift_in + i * sr.ldin)[gi[c]] : zero4;
+                            hv[c] = ok[c] ? reinterpret_cast<const float4*>(sr.d_shift_in + i_hin * sr.ldin)[gi[c]] : zero4;
                         v[c] = make_float4(ra[p][c].x - rb[p][c].x, ra[p][c].y - rb[p][c].y, ra[p][c].z - rb[p][c].z,
                                            ra[p][c].w - rb[p][c].w);
                     }
@@ -721,20 +746,23 @@ __global__ __launch_bounds__(256) void k_ew_shift_accum(flc_shift_rows sr, int b
                             acc[c].x = acc[c].x + t.x; acc[c].y = acc[c].y + t.y;
                             acc[c].z = acc[c].z + t.z; acc[c].w = acc[c].w + t.w;
                         }
-                        if (sr.d_msg && ok[c]) reinterpret_cast<float4*>(sr.d_msg + i * sr.ldmsg)[gi[c]] = m;
+                        if (sr.d_msg && ok[c]) reinterpret_cast<float4*>(sr.d_msg + i_msg * sr.ldmsg)[gi[c]] = m;
                         if (sr.d_shift_out && ok[c])
-                            reinterpret_cast<float4*>(sr.d_shift_out + i * sr.ldout)[gi[c]] =
+                            reinterpret_cast<float4*>(sr.d_shift_out + i_hout * sr.ldout)[gi[c]] =
                                 make_float4(hv[c].x + sr.shift_alpha * e[c].x, hv[c].y + sr.shift_alpha * e[c].y,
                                             hv[c].z + sr.shift_alpha * e[c].z, hv[c].w + sr.shift_alpha * e[c].w);
                     }
                     if (i + PF < n) {
+                        if (M::ON) rid[p] = rnext[p];
+                        const int64_t rowb = map.has(FLC_IDX_B) ? rid[p] : i + PF;
                         const float4* pa = reinterpret_cast<const float4*>(sr.d_a + (i + PF) * sr.lda);
-                        const float4* pb = reinterpret_cast<const float4*>(sr.d_b + (i + PF) * sr.ldb);
+                        const float4* pb = reinterpret_cast<const float4*>(sr.d_b + rowb * sr.ldb);
 #pragma unroll
                         for (int c = 0; c < COLS; ++c) {
                             ra[p][c] = ok[c] ? ld_row4(pa + gi[c]) : zero4;
                             rb[p][c] = ok[c] ? ld_row4(pb + gi[c]) : zero4;
                         }
+                        if (M::ON) rnext[p] = map.raw_s(min(i + 2 * PF, n - 1));   // (behind the row's vector loads)
                     }
                 }
             }
@@ -749,10 +777,10 @@ __global__ __launch_bounds__(256) void k_ew_shift_accum(flc_shift_rows sr, int b
 
 // the same fold one element at a time: unaligned rows, a leading dimension that is no multiple of
 // 4, and the d % 4 tail of the vector launch
-template <class Op>
+template <class Op, class M = MapNone>
 __global__ __launch_bounds__(256) void k_ew_shift_accum_scalar(flc_shift_rows sr, int64_t n, int64_t j0, int64_t d, Op op,
                                                                const float* __restrict__ levels, int s,
-                                                               const float* __restrict__ w, float wt, float* out) {
+                                                               const float* __restrict__ w, float wt, float* out, M map) {
     extern __shared__ __attribute__((aligned(16))) float4 smem_tab[];
     if (Op::TABLE) op.set_table_ok(load_table(levels, s, smem_tab));
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -761,15 +789,17 @@ __global__ __launch_bounds__(256) void k_ew_shift_accum_scalar(flc_shift_rows sr
         float acc = 0.f;
         for (int64_t i = 0; i < n; ++i) {
             op.setup(i);
-            const float bs = sr.d_base ? sr.d_base[i * sr.ldbase + j] : 0.f;
-            const float hv = sr.d_shift_out ? sr.d_shift_in[i * sr.ldin + j] : 0.f;
-            const float e = op.template apply<false>(sr.d_a[i * sr.lda + j] - sr.d_b[i * sr.ldb + j], j, cs, smem_tab);
+            const int64_t i_b = map.at_s(i, FLC_IDX_B), i_base = map.at_s(i, FLC_IDX_BASE), i_msg = map.at_s(i, FLC_IDX_MSG);
+            const int64_t i_hin = map.at_s(i, FLC_IDX_SHIFT_IN), i_hout = map.at_s(i, FLC_IDX_SHIFT_OUT);
+            const float bs = sr.d_base ? sr.d_base[i_base * sr.ldbase + j] : 0.f;
+            const float hv = sr.d_shift_out ? sr.d_shift_in[i_hin * sr.ldin + j] : 0.f;
+            const float e = op.template apply<false>(sr.d_a[i * sr.lda + j] - sr.d_b[i_b * sr.ldb + j], j, cs, smem_tab);
             const float t = e * sr.msg_scale;
             const float m = sr.d_base ? bs + t : t;
             const float wm = w ? w[i] * m : m;
             acc = (i == 0) ? wm : acc + wm;
-            if (sr.d_msg) sr.d_msg[i * sr.ldmsg + j] = m;
-            if (sr.d_shift_out) sr.d_shift_out[i * sr.ldout + j] = hv + sr.shift_alpha * e;
+            if (sr.d_msg) sr.d_msg[i_msg * sr.ldmsg + j] = m;
+            if (sr.d_shift_out) sr.d_shift_out[i_hout * sr.ldout + j] = hv + sr.shift_alpha * e;
         }
         out[j] = acc / wt;
     }
@@ -1046,15 +1076,24 @@ __global__ __launch_bounds__(256) void k_norm_partials2(flc_frecon_rows fr, int6
     }
 }
 
-// device-RNG row keys (natural codec; dithering gets them from k_norm_final)
-__global__ void k_row_keys(int64_t n, uint64_t seed, int64_t client0, uint32_t* __restrict__ rk) {
+// device-RNG row keys (natural codec; dithering gets them from k_norm_final); M: of the participants'
+// client ids (one id per thread: a vector load)
+template <class M = MapNone>
+__global__ void k_row_keys(int64_t n, uint64_t seed, int64_t client0, uint32_t* __restrict__ rk, M map) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
-        rk[r] = rowkey(client_key(seed, client0 + r));
+        rk[r] = rowkey(client_key(seed, client0 + (M::ON ? map.id(r) : r)));
 }
 
 static int grid_cap(int64_t work, int64_t per_block, int64_t cap) {
     int64_t b = (work + per_block - 1) / per_block;
     return (int)std::max<int64_t>(1, std::min<int64_t>(b, cap));
+}
+
+static int launch_row_keys(int64_t n, uint64_t seed, int64_t client0, uint32_t* rk, const flc_row_map* map, hipStream_t st) {
+    if (map) hipLaunchKernelGGL(k_row_keys<MapIds>, dim3(grid_cap(n, 256, 64)), dim3(256), 0, st, n, seed, client0, rk, map_ids(map));
+    else hipLaunchKernelGGL(k_row_keys<MapNone>, dim3(grid_cap(n, 256, 64)), dim3(256), 0, st, n, seed, client0, rk, MapNone{});
+    FLC_CHECK_LAUNCH("k_row_keys");
+    return FLC_OK;
 }
 
 template <class Op>
@@ -1164,7 +1203,7 @@ static int launch_accum(RowSrc src, bool vec, int64_t n, int64_t d, Op op, const
 // dimension that is a multiple of 4 (a shared base has none); one profile record per call.
 template <class Op>
 static int launch_shift_accum(const flc_shift_rows& sr, int64_t n, int64_t d, Op op, const float* levels, int s,
-                              const float* w, float wt, float* out, hipStream_t st) {
+                              const float* w, float wt, float* out, hipStream_t st, const flc_row_map* map) {
     if (d == 0) return FLC_OK;
     const size_t lds = Op::TABLE ? (size_t)s * sizeof(float4) : 0;
     uintptr_t pal = (uintptr_t)sr.d_a | (uintptr_t)sr.d_b | (uintptr_t)out;   // pointers: low 4 bits clear
@@ -1177,23 +1216,34 @@ static int launch_shift_accum(const flc_shift_rows& sr, int64_t n, int64_t d, Op
     }
     const bool vec = (pal & 15u) == 0 && (lal & 3u) == 0;
     int base_mode = BASE_NONE;
-    if (sr.d_base) base_mode = sr.ldbase == 0 ? BASE_SHARED : (sr.d_base == sr.d_b && sr.ldbase == sr.ldb) ? BASE_B : BASE_ROWS;
-    const int hin_b = sr.d_shift_out && sr.d_shift_in == sr.d_b && sr.ldin == sr.ldb;
+    // (a sampled round: an operand is "the b rows" only when it is addressed the way they are)
+    const bool base_as_b = map_has(map, FLC_IDX_BASE) == map_has(map, FLC_IDX_B);
+    const bool hin_as_b = map_has(map, FLC_IDX_SHIFT_IN) == map_has(map, FLC_IDX_B);
+    if (sr.d_base) base_mode = sr.ldbase == 0 ? BASE_SHARED : (sr.d_base == sr.d_b && sr.ldbase == sr.ldb && base_as_b) ? BASE_B : BASE_ROWS;
+    const int hin_b = sr.d_shift_out && sr.d_shift_in == sr.d_b && sr.ldin == sr.ldb && hin_as_b;
+    const MapIds mi = map ? map_ids(map) : MapIds{nullptr, 0u};
+    const MapNone mn{};
     ProfScope _ps("k_ew_shift_accum", st);
     int64_t j0 = 0;
     if (vec && d / 4 > 0) {
         const int grid = grid_cap(d / 4, 256 * FLC_SHIFT_COLS, 1 << 20);
-        if (w) hipLaunchKernelGGL((k_ew_shift_accum<Op, FLC_SHIFT_COLS, FLC_SHIFT_PF, true>), dim3(grid), dim3(256), lds, st, sr, base_mode, hin_b,
-                                  n, d, op, levels, s, w, wt, out);
+        if (map && w) hipLaunchKernelGGL((k_ew_shift_accum<Op, FLC_SHIFT_COLS, FLC_SHIFT_PF, true, MapIds>), dim3(grid), dim3(256), lds, st, sr, base_mode, hin_b,
+                                         n, d, op, levels, s, w, wt, out, mi);
+        else if (map) hipLaunchKernelGGL((k_ew_shift_accum<Op, FLC_SHIFT_COLS, FLC_SHIFT_PF, false, MapIds>), dim3(grid), dim3(256), lds, st, sr, base_mode, hin_b,
+                                         n, d, op, levels, s, w, wt, out, mi);
+        else if (w) hipLaunchKernelGGL((k_ew_shift_accum<Op, FLC_SHIFT_COLS, FLC_SHIFT_PF, true>), dim3(grid), dim3(256), lds, st, sr, base_mode, hin_b,
+                                       n, d, op, levels, s, w, wt, out, mn);
         else hipLaunchKernelGGL((k_ew_shift_accum<Op, FLC_SHIFT_COLS, FLC_SHIFT_PF, false>), dim3(grid), dim3(256), lds, st, sr, base_mode, hin_b,
-                                n, d, op, levels, s, w, wt, out);
+                                n, d, op, levels, s, w, wt, out, mn);
         FLC_CHECK_LAUNCH("k_ew_shift_accum");
         j0 = (d / 4) * 4;
     }
     if (j0 < d) {
         const int grid = grid_cap(d - j0, 256, 4096);
-        hipLaunchKernelGGL((k_ew_shift_accum_scalar<Op>), dim3(grid), dim3(256), lds, st, sr, n, j0, d, op, levels, s, w,
-                           wt, out);
+        if (map) hipLaunchKernelGGL((k_ew_shift_accum_scalar<Op, MapIds>), dim3(grid), dim3(256), lds, st, sr, n, j0, d, op, levels, s, w,
+                                    wt, out, mi);
+        else hipLaunchKernelGGL((k_ew_shift_accum_scalar<Op>), dim3(grid), dim3(256), lds, st, sr, n, j0, d, op, levels, s, w,
+                                wt, out, mn);
         FLC_CHECK_LAUNCH("k_ew_shift_accum_scalar");
     }
     return FLC_OK;
@@ -1282,7 +1332,7 @@ static int launch_lone_dither(const flc_codec_params* prm, const UniformSrc& us,
         constexpr bool CM = decltype(cm)::value;
         { ProfScope _ps("k_norm_partials", st);
         hipLaunchKernelGGL((k_norm_partials<NK, true, false, (bool)FLC_LONE_KEEP>), pg, dim3(256), 0, st, src, RowSrc{nullptr, 0, nullptr}, d, parts, LONE_PLEN,
-                           e.partial, e.tinyp); }
+                           e.partial, e.tinyp, MapNone{}); }
         FLC_CHECK_LAUNCH("k_norm_partials");
         DitherOp<false, CM> op;
         op.us = us;
@@ -1310,17 +1360,18 @@ static int launch_lone_dither(const flc_codec_params* prm, const UniformSrc& us,
 int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool vec, int64_t n, int64_t d,
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt,
            void* ws, size_t ws_bytes, hipStream_t st, const ShiftArgs* sh, const CodeArgs* ca, int norm_mode,
-           const flc_shift_rows* sr) {
+           const flc_shift_rows* sr, const flc_row_map* map) {
     // sr: the shifted fold over n rows (flc_encode_shift_reduce): src holds the a rows, the dense
     // two-pass form only (the sparse QSGD pass reads plain rows, not differences)
     if (sr && (dense || sh || ca || pnorm_in || norm_mode != FLC_NORMMODE_EXACT)) { set_error("ew_run: the shifted fold takes no other form"); return FLC_ERR_ARG; }
+    if (map && !sr) { set_error("ew_run: a row map goes with the shifted fold"); return FLC_ERR_ARG; }
     if ((sh || ca) && (!dense || n != 1)) { set_error("ew_run: the shift / code forms are one dense row"); return FLC_ERR_ARG; }
     const int codec = prm->codec;
     const bool compat = pat && pat->d_uniforms;
     const int64_t client0 = pat ? pat->client0 : 0;
     UniformSrc us{compat ? pat->d_uniforms : nullptr, (pat && pat->uniforms_ld) ? pat->uniforms_ld : d};
     auto go = [&](auto op, const float* levels, int s) -> int {
-        if (sr) return launch_shift_accum(*sr, n, d, op, levels, s, w, wt, out, st);
+        if (sr) return launch_shift_accum(*sr, n, d, op, levels, s, w, wt, out, st, map);
         if (sh && ca) return launch_shift_code(src.base, d, op, levels, s, *sh, *ca, st);
         if (sh) return launch_shift(src.base, d, op, levels, s, *sh, st);
         if (ca) return launch_code(src.base, d, op, levels, s, *ca, st);
@@ -1356,8 +1407,7 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
         }
         case FLC_NATURAL: {
             if (compat) { NaturalOp<true> op; op.us = us; op.rks = nullptr; return go(op, nullptr, 0); }
-            hipLaunchKernelGGL(k_row_keys, dim3(grid_cap(n, 256, 64)), dim3(256), 0, st, n, prm->seed, client0, e.rk);
-            FLC_CHECK_LAUNCH("k_row_keys");
+            if (int rc = launch_row_keys(n, prm->seed, client0, e.rk, map, st)) return rc;
             NaturalOp<false> op;
             op.us = us;
             op.rks = e.rk;
@@ -1381,12 +1431,11 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
                 // the shift forms take the norm of a_i - b_i (one row, or the shifted fold's n rows)
                 const RowSrc subs{sr ? sr->d_b : sh ? sh->b : nullptr, sr ? sr->ldb : d, nullptr};
                 rc = launch_norms(src, vec, n, d, prm->norm, e.partial, e.tinyp, e.pn, e.rpn, e.fast, prm->seed,
-                                  client0, e.rk, st, (sr || sh) ? &subs : nullptr);
+                                  client0, e.rk, st, (sr || sh) ? &subs : nullptr, map);
                 if (rc) return rc;
                 rt = RowTabs{e.pn, e.rpn, e.fast, e.rk};
             } else if (!compat) {
-                hipLaunchKernelGGL(k_row_keys, dim3(grid_cap(n, 256, 64)), dim3(256), 0, st, n, prm->seed, client0, e.rk);
-                FLC_CHECK_LAUNCH("k_row_keys");
+                if ((rc = launch_row_keys(n, prm->seed, client0, e.rk, map, st))) return rc;
             }
             if (pnorm_out && pnorm_out != rt.pn)
                 FLC_CHECK_HIP(hipMemcpyAsync(pnorm_out, rt.pn, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -1492,8 +1541,7 @@ int frecon_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_fr
         }
         case FLC_NATURAL: {
             if (compat) { NaturalOp<true> op; op.us = us; op.rks = nullptr; return go(op, op, nullptr, 0); }
-            hipLaunchKernelGGL(k_row_keys, dim3(grid_cap(n, 256, 64)), dim3(256), 0, st, n, prm->seed, client0, eu.rk);
-            FLC_CHECK_LAUNCH("k_row_keys");
+            if (int rc = launch_row_keys(n, prm->seed, client0, eu.rk, nullptr, st)) return rc;
             NaturalOp<false> op;
             op.us = us;
             op.rks = eu.rk;
@@ -1509,9 +1557,9 @@ int frecon_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_fr
                 // one pair aligned, the other not: the two single-pair passes, each in its own form
                 const RowSrc hs{fr.d_h, fr.ldh, nullptr}, ps{fr.d_p, fr.ldp, nullptr};
                 if (int rc = launch_norms(a, vec_u, n, d, prm->norm, eu.partial, eu.tinyp, eu.pn, eu.rpn, eu.fast, prm->seed,
-                                          client0, eu.rk, st, &hs)) return rc;
+                                          client0, eu.rk, st, &hs, nullptr)) return rc;
                 if (int rc = launch_norms(a, vec_q, n, d, prm->norm, eq.partial, eq.tinyp, eq.pn, eq.rpn, eq.fast, prm->seed,
-                                          client0, eq.rk, st, &ps)) return rc;
+                                          client0, eq.rk, st, &ps, nullptr)) return rc;
             } else {
                 const int64_t parts = norm_parts(n, d), plen = norm_part_len(n, d);
                 dim3 grid((unsigned)std::min<int64_t>(parts, std::max<int64_t>(64, 4096 / std::max<int64_t>(n, 1))), (unsigned)n);
@@ -1521,9 +1569,9 @@ int frecon_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_fr
     else hipLaunchKernelGGL((k_norm_partials2<NK, false>), grid, dim3(256), 0, st, fr, d, parts, plen, eu.partial, eu.tinyp, eq.partial, eq.tinyp); } \
     FLC_CHECK_LAUNCH("k_norm_partials2");                                                           \
     hipLaunchKernelGGL((k_norm_final<NK>), dim3((unsigned)n), dim3(64), 0, st, eu.partial, eu.tinyp, parts, n, eu.pn, eu.rpn, \
-                       eu.fast, prm->seed, client0, eu.rk);                                         \
+                       eu.fast, prm->seed, client0, eu.rk, MapNone{});                                       \
     hipLaunchKernelGGL((k_norm_final<NK>), dim3((unsigned)n), dim3(64), 0, st, eq.partial, eq.tinyp, parts, n, eq.pn, eq.rpn, \
-                       eq.fast, prm->seed, client0, eq.rk);                                         \
+                       eq.fast, prm->seed, client0, eq.rk, MapNone{});                                       \
     FLC_CHECK_LAUNCH("k_norm_final");
                 if (prm->norm == FLC_NORM_L2) { FLC_NORM2_CASE(FLC_NORM_L2) }
                 else if (prm->norm == FLC_NORM_L1) { FLC_NORM2_CASE(FLC_NORM_L1) }

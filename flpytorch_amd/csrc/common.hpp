@@ -111,6 +111,36 @@ struct RowSrc {
     }
 };
 
+// Partial participation (the _sampled entries, flc_row_map): participant i of a round is client
+// ids[i] of n_total resident ones.  The kernels of the shifted rounds take the mapping as a template
+// argument: MapNone is the contiguous round (participant i is row i and client client0 + i, nothing
+// is loaded), MapIds reads the id.  id_s / at_s: a wave-uniform i, read through the scalar cache like
+// RowSrc::row_s; at / at_s: the row of an operand whose FLC_IDX_ bit is `bit`.
+struct MapNone {
+    static constexpr bool ON = false;
+    __device__ inline bool has(uint32_t) const { return false; }
+    __device__ inline int64_t id(int64_t i) const { return i; }
+    __device__ inline int64_t id_s(int64_t i) const { return i; }
+    __device__ inline int32_t raw_s(int64_t i) const { return (int32_t)i; }
+    __device__ inline int64_t at(int64_t i, uint32_t) const { return i; }
+    __device__ inline int64_t at_s(int64_t i, uint32_t) const { return i; }
+};
+struct MapIds {
+    static constexpr bool ON = true;
+    const int32_t* ids;
+    uint32_t indexed;
+    __device__ inline bool has(uint32_t bit) const { return (indexed & bit) != 0; }
+    __device__ inline int64_t id(int64_t i) const { return ids[i]; }
+    __device__ inline int64_t id_s(int64_t i) const { return sload(ids + i); }
+    __device__ inline int32_t raw_s(int64_t i) const { return sload(ids + i); }
+    __device__ inline int64_t at(int64_t i, uint32_t bit) const { return (indexed & bit) ? (int64_t)ids[i] : i; }
+    __device__ inline int64_t at_s(int64_t i, uint32_t bit) const { return (indexed & bit) ? (int64_t)sload(ids + i) : i; }
+};
+inline MapIds map_ids(const flc_row_map* map) { return MapIds{map->d_ids, map->indexed}; }
+inline bool map_has(const flc_row_map* map, uint32_t bit) { return map && (map->indexed & bit); }
+// device array tab[i] = base + at(i) * ld (the rows of an indexed operand as a RowSrc pointer table)
+int row_ptrs_launch(const float* base, int64_t ld, const flc_row_map* map, int64_t n, const float** tab, hipStream_t st);
+
 // Internal entry points of the codec families (reduce.hip, codecs.hip, the selection core:
 // select.hip with topk_filter.hip, topk_select.hip, lone_row.hip, randk.hip and chunk_accum.hip).
 int reduce_impl(RowSrc src, bool rows_vec_ok, int64_t n, int64_t d, const float* x, const float* w, float wt,
@@ -141,7 +171,7 @@ struct CodeArgs {
 int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool vec, int64_t n, int64_t d,
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt, void* ws,
            size_t ws_bytes, hipStream_t st, const ShiftArgs* sh = nullptr, const CodeArgs* ca = nullptr,
-           int norm_mode = FLC_NORMMODE_EXACT, const flc_shift_rows* sr = nullptr);
+           int norm_mode = FLC_NORMMODE_EXACT, const flc_shift_rows* sr = nullptr, const flc_row_map* map = nullptr);
 // the dithering codecs' parameter check (s, levels, p-norm), before any launch
 int check_dither(const flc_codec_params* prm);
 size_t ew_shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
@@ -150,7 +180,8 @@ size_t shift_workspace(const flc_codec_params* prm, int64_t d);
 // pass (codecs.hip k_ew_shift_accum), RandK / TopK / Rank-K row by row (shift.hip)
 size_t shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
-                     const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+                     const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st,
+                     const flc_row_map* map = nullptr);
 // FRECON's two-message round (flc_frecon_reduce, codecs.hip k_ew_frecon_accum): elementwise codecs
 // only; frecon_precheck is the codec's host-side parameter / pattern check, before any launch
 bool frecon_elementwise(int codec);
@@ -202,10 +233,14 @@ enum { SHAPE_D = 0, SHAPE_A = 1, SHAPE_C = 2, SHAPE_B = 3 };
 int shift_shape(const flc_shift_rows& sr, const char* me);
 // the in-place shapes (A, B) store into the b rows: they must not overlap
 int inplace_rows_check(const char* me, int shape, const flc_shift_rows& sr, int64_t n, int64_t d);
+// the sampled rounds' extra workspace (the pointer table of shape B's fold over the mapped rows)
+size_t sampled_tab_bytes(int64_t n);
 // a round over (index, value) lists: K in [1, D], D within 32-bit entry indices, then inplace_rows_check
 int sparse_round_precheck(const char* me, int shape, const flc_shift_rows& sr, int64_t n, int64_t d, int64_t K);
 // shape B's tail: the dense fold of the rows the round has just updated in place
-int fold_updated_rows(const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt, float* out, hipStream_t st);
+// (map with FLC_IDX_B: over the participants' rows, through the pointer table tab[n] built here)
+int fold_updated_rows(const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt, float* out, hipStream_t st,
+                      const flc_row_map* map = nullptr, const float** tab = nullptr);
 // the SPARSE payload of a dense row (wire.hip k_pack_count / scan / write): bc holds pack_blocks(d)
 // counters, the payload is zeroed by the caller
 int64_t pack_blocks(int64_t d);
@@ -254,7 +289,7 @@ int randk_device_counts(uint64_t seed, int64_t client0, int64_t n, int64_t d, in
 // chunk counts [C][n] (the pattern's d_randk_counts or computed) and client keys [n] of a device-draw
 // fold; wsp: randk_device_workspace(n, d) bytes
 int randk_device_prepare(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, void* wsp,
-                         const uint32_t** cnt, const uint64_t** ckey, hipStream_t st);
+                         const uint32_t** cnt, const uint64_t** ckey, hipStream_t st, const flc_row_map* map = nullptr);
 // The compat RandK lists by themselves: row r's entries of chunk c are idx / val[r * cap + tab[c * n + r].x + t],
 // t < tab[c * n + r].y (element index within the row; randk_scale * rows[r][idx]).  A caller may
 // rewrite val before randk_lists_fold (k_chunk_accum) folds the lists into out.
@@ -269,9 +304,10 @@ int randk_lists_build(const flc_codec_params* prm, const flc_pattern* pat, RowSr
                       RkLists* lists, hipStream_t st);
 int randk_lists_fold(int64_t n, int64_t d, int64_t K, void* wsp, const float* w, float wt, float* out, hipStream_t st);
 // the sparse in-place RandK shifted round (flc_randk_shift_reduce, randk_shift.hip)
-size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n, int64_t d);
+size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n, int64_t d, bool sampled = false);
 int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
-                    const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+                    const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st,
+                    const flc_row_map* map = nullptr);
 // shape C's fold of base + t over lists in the RkLists layout (k_randk_shift_lfold)
 int randk_shift_lfold_launch(const float* base, int64_t n, int64_t d, RkLists lists, const float* w, float wt, float* out,
                              hipStream_t st);
@@ -297,9 +333,9 @@ int topk_lists_build(const flc_codec_params* prm, RowSrc rows, bool vec, int64_t
 int topk_lists_fold(const flc_codec_params* prm, int64_t n, int64_t d, void* wsp, const float* w, float wt, float* out,
                     hipStream_t st);
 // the batched TopK shifted round (flc_topk_shift_reduce, topk_shift.hip)
-size_t topk_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
+size_t topk_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d, bool sampled = false);
 int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt,
-                   float* out, void* ws, size_t ws_bytes, hipStream_t st);
+                   float* out, void* ws, size_t ws_bytes, hipStream_t st, const flc_row_map* map = nullptr);
 // the one-read QSGD shifted round (flc_dither_shift_reduce): dither_shift.hip decides on the host,
 // before any launch, whether the call is taken (else the refusal with its reason) and runs it;
 // dither_sparse.hip's ds_shift_run is the sparse pipeline over a - b with the in-place epilogues

@@ -248,14 +248,16 @@ __global__ __launch_bounds__(256) void k_randk_ckeys(int64_t n, uint64_t seed, i
     if (row < n) ckey[row] = client_key(seed, client0 + row);
 }
 
+// M (the sampled sparse round): row `row` is the participant, its key the client's (client0 + ids[row])
+template <class M = MapNone>
 __global__ __launch_bounds__(RKC_NT) void k_randk_counts(int64_t n, int64_t d, int64_t K, uint64_t seed, int64_t client0,
-                                                         RkdWs ws) {
+                                                         RkdWs ws, M map) {
     __shared__ uint32_t bins[RKC_BINS / 2];
     const int64_t row = blockIdx.y;
     const int tid = threadIdx.x;
     const int64_t C = nchunks(d);
     const int64_t c0 = (int64_t)blockIdx.x * RKC_BINS, nc = min(C, c0 + RKC_BINS) - c0;
-    const uint64_t ck = client_key(seed, client0 + row);
+    const uint64_t ck = client_key(seed, client0 + (M::ON ? map.id_s(row) : row));
     for (int64_t i = tid; i < (nc + 1) / 2; i += RKC_NT) bins[i] = 0;
     __syncthreads();
     const rktree::RowPerm P(ck, (uint64_t)d);
@@ -526,11 +528,13 @@ size_t randk_device_workspace(int64_t n, int64_t d) {
 }
 
 static int randk_counts(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, RkdWs ws,
-                        hipStream_t st) {
+                        hipStream_t st, const flc_row_map* map = nullptr) {
     ProfScope _ps("k_randk_counts", st);
     const int64_t parts = (host_chunks(d) + RKC_BINS - 1) / RKC_BINS;
-    hipLaunchKernelGGL(k_randk_counts, dim3((unsigned)parts, (unsigned)n), dim3(RKC_NT), 0, st, n, d, prm->k, prm->seed,
-                       pat ? pat->client0 : (int64_t)0, ws);
+    if (map) hipLaunchKernelGGL(k_randk_counts<MapIds>, dim3((unsigned)parts, (unsigned)n), dim3(RKC_NT), 0, st, n, d, prm->k,
+                                prm->seed, pat ? pat->client0 : (int64_t)0, ws, map_ids(map));
+    else hipLaunchKernelGGL(k_randk_counts<MapNone>, dim3((unsigned)parts, (unsigned)n), dim3(RKC_NT), 0, st, n, d, prm->k, prm->seed,
+                       pat ? pat->client0 : (int64_t)0, ws, MapNone{});
     FLC_CHECK_LAUNCH("k_randk_counts");
     return FLC_OK;
 }
@@ -551,9 +555,10 @@ static int randk_counts_or_given(const flc_codec_params* prm, const flc_pattern*
 
 // the same for randk_shift.hip: wsp holds randk_device_workspace(n, d) bytes
 int randk_device_prepare(const flc_codec_params* prm, const flc_pattern* pat, int64_t n, int64_t d, void* wsp,
-                         const uint32_t** cnt, const uint64_t** ckey, hipStream_t st) {
+                         const uint32_t** cnt, const uint64_t** ckey, hipStream_t st, const flc_row_map* map) {
     RkdWs rw = carve_rkd(wsp, n, d, nullptr);
-    if (int rc = randk_counts_or_given(prm, pat, n, d, &rw, st)) return rc;
+    // a sampled round: counts and keys by client id, always computed (given counts are refused before)
+    if (int rc = map ? randk_counts(prm, pat, n, d, rw, st, map) : randk_counts_or_given(prm, pat, n, d, &rw, st)) return rc;
     *cnt = rw.cnt;
     *ckey = rw.ckey;
     return FLC_OK;

@@ -43,12 +43,15 @@ struct RksMeta {           // lane = row of a 64-row batch
     uint32_t m;            // members of this chunk
     uint32_t klo, khi;     // client key
     float w;
+    uint32_t brow;         // a sampled round: the participant's row of b (its client id where b is indexed)
 };
 
+template <class M>
 __device__ inline RksMeta rks_meta(const uint32_t* cnt, const uint64_t* ckey, const float* w, int64_t c, int64_t n,
-                                   int64_t r, uint32_t clen) {
-    RksMeta m{0u, 0u, 0u, 1.f};
+                                   int64_t r, uint32_t clen, const M& map) {
+    RksMeta m{0u, 0u, 0u, 1.f, 0u};
     if (r < n) {
+        if (M::ON) m.brow = (uint32_t)map.at(r, FLC_IDX_B);
         m.m = min(cnt[c * n + r], clen);                 // <= clen by construction; never index past it
         const uint64_t k = ckey[r];
         m.klo = (uint32_t)k;
@@ -66,10 +69,11 @@ __device__ inline void rks_tile_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_RE
 
 constexpr int RKS_AP = 8;                                 // rows in flight (their two gathers)
 
-template <int TS, int MODE>
+// M (flc_randk_shift_reduce_sampled): the b row of participant r travels with its key in RksMeta
+template <int TS, int MODE, class M = MapNone>
 __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64_t d, const uint32_t* __restrict__ cnt,
                                                      const uint64_t* __restrict__ ckey, const float* __restrict__ w,
-                                                     float wt, float* __restrict__ out) {
+                                                     float wt, float* __restrict__ out, M map) {
     constexpr int PARTS = CHUNK / TS;
     constexpr int AP = RKS_AP;
     constexpr int NR = MODE == SHAPE_C ? TS / 64 : 1;        // shape C: columns per lane, summed in registers
@@ -102,37 +106,39 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
         uint32_t ro[AP];                                      // ring: part-local column (>= TS: none)
         float ra[AP], rb[AP];                                 //       gathered a, b
         // row r's members of this part for this lane: two gathers in flight
-        auto fetch = [&](int slot, int64_t r, uint32_t m, uint64_t k) {
+        auto fetch = [&](int slot, int64_t r, uint32_t m, uint64_t k, int64_t br) {
             const int64_t rr = min(r, n - 1);                 // (rows past n have m == 0: nothing is loaded)
+            const int64_t rowb = M::ON ? br : rr;             // (M::ON: row 0 past n)
             const rktree::ChunkPerm P(k, c, clen);
             uint32_t col = (uint32_t)lane < m ? P((uint32_t)lane) : NOCOL;
             if (PARTS > 1 && col - pbase >= (uint32_t)TS) col = NOCOL;   // another wave's part: no gather
             const auto rsa = chunk_rsrc(g.a + rr * g.lda, cbase, d);
-            const auto rsb = chunk_rsrc(g.b + rr * g.ldb, cbase, d);
+            const auto rsb = chunk_rsrc(g.b + rowb * g.ldb, cbase, d);
             ro[slot] = col - pbase;
             ra[slot] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsa, (int)(col * 4u), 0, 0));
             rb[slot] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsb, (int)(col * 4u), 0, 0));
         };
         // one member (part-local column loc < TS) of row r: the epilogue, the in-place store, the fold
-        auto member = [&](uint32_t loc, float av, float bv, int64_t r, float wi) {
+        auto member = [&](uint32_t loc, float av, float bv, int64_t rowb, float wi) {
             const float v = av - bv;
             const float e = g.scale * v;
             const float tt = e * g.ms;
             if (MODE == SHAPE_A) {
-                const auto rsb = chunk_rsrc(g.b + r * g.ldb, cbase, d);
+                const auto rsb = chunk_rsrc(g.b + rowb * g.ldb, cbase, d);
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(bv + g.alpha * e), rsb, (int)((pbase + loc) * 4u), 0, 0);
             }
             if (MODE == SHAPE_C) tl[loc] = tt;
             else tl[loc] = tl[loc] + wi * tt;
         };
-        RksMeta cur = rks_meta(cnt, ckey, w, c, n, lane, clen), nxt;
+        RksMeta cur = rks_meta(cnt, ckey, w, c, n, lane, clen, map), nxt;
 #pragma unroll
         for (int q = 0; q < AP; ++q)
             fetch(q, q, (uint32_t)__builtin_amdgcn_readlane(cur.m, q),
-                  rks_join64((uint32_t)__builtin_amdgcn_readlane(cur.khi, q), (uint32_t)__builtin_amdgcn_readlane(cur.klo, q)));
+                  rks_join64((uint32_t)__builtin_amdgcn_readlane(cur.khi, q), (uint32_t)__builtin_amdgcn_readlane(cur.klo, q)),
+                  M::ON ? (int64_t)(uint32_t)__builtin_amdgcn_readlane(cur.brow, q) : (int64_t)q);
         for (int64_t b = 0; b < nb; ++b) {
             const int64_t i0 = b * 64;
-            nxt = rks_meta(cnt, ckey, w, c, n, i0 + 64 + lane, clen);
+            nxt = rks_meta(cnt, ckey, w, c, n, i0 + 64 + lane, clen, map);
 #pragma unroll 1
             for (int q0 = 0; q0 < 64; q0 += AP) {
                 const bool wrap = q0 + AP >= 64;              // the refills come from the next batch
@@ -143,16 +149,17 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
                     if (r < n) {
                         const float wi = __uint_as_float((uint32_t)__builtin_amdgcn_readlane(__float_as_uint(cur.w), q));
                         const uint32_t m = (uint32_t)__builtin_amdgcn_readlane(cur.m, q);
-                        if (ro[z] < (uint32_t)TS) member(ro[z], ra[z], rb[z], r, wi);
+                        const int64_t rowb = M::ON ? (int64_t)(uint32_t)__builtin_amdgcn_readlane(cur.brow, q) : r;
+                        if (ro[z] < (uint32_t)TS) member(ro[z], ra[z], rb[z], rowb, wi);
                         if (m > 64u) {                        // a row with more than 64 members here: its tail in place
                             const uint64_t k = rks_join64((uint32_t)__builtin_amdgcn_readlane(cur.khi, q),
                                                           (uint32_t)__builtin_amdgcn_readlane(cur.klo, q));
                             const rktree::ChunkPerm P(k, c, clen);
                             const float* ap = g.a + r * g.lda + cbase;
-                            const float* bp = g.b + r * g.ldb + cbase;
+                            const float* bp = g.b + rowb * g.ldb + cbase;
                             for (uint32_t e = 64u + lane; e < m; e += 64) {
                                 const uint32_t col = P(e), l2 = col - pbase;
-                                if (l2 < (uint32_t)TS) member(l2, ap[col], bp[col], r, wi);
+                                if (l2 < (uint32_t)TS) member(l2, ap[col], bp[col], rowb, wi);
                             }
                         }
                         if (MODE == SHAPE_C) {                  // every column: w * (base + t), t = +0 outside the set
@@ -168,7 +175,9 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
                     const uint32_t mn = (uint32_t)(wrap ? __builtin_amdgcn_readlane(nxt.m, qq) : __builtin_amdgcn_readlane(cur.m, qq));
                     const uint32_t kh = (uint32_t)(wrap ? __builtin_amdgcn_readlane(nxt.khi, qq) : __builtin_amdgcn_readlane(cur.khi, qq));
                     const uint32_t kl = (uint32_t)(wrap ? __builtin_amdgcn_readlane(nxt.klo, qq) : __builtin_amdgcn_readlane(cur.klo, qq));
-                    fetch(z, r + AP, mn, rks_join64(kh, kl));
+                    const int64_t bn = M::ON ? (int64_t)(uint32_t)(wrap ? __builtin_amdgcn_readlane(nxt.brow, qq) : __builtin_amdgcn_readlane(cur.brow, qq))
+                                             : r + AP;
+                    fetch(z, r + AP, mn, rks_join64(kh, kl), bn);
                 }
             }
             cur = nxt;
@@ -188,16 +197,17 @@ __global__ __launch_bounds__(256) void k_randk_shift(RksArgs g, int64_t n, int64
 
 // Shape B, device draws: no fold here (reduce_impl reads the updated rows afterwards), so the walk is
 // row-major like k_randk_gen — a wave stays inside one row, chunk after chunk.
+template <class M = MapNone>
 __global__ __launch_bounds__(256) void k_randk_shift_scatter(RksArgs g, int64_t n, int64_t d,
                                                              const uint32_t* __restrict__ cnt,
-                                                             const uint64_t* __restrict__ ckey) {
+                                                             const uint64_t* __restrict__ ckey, M map) {
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t C = nchunks(d);
     for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
         const uint64_t k = ckey[row];
         const float* ap = g.a + row * g.lda;
-        float* bp = g.b + row * g.ldb;
+        float* bp = g.b + map.at_s(row, FLC_IDX_B) * g.ldb;
         for (int64_t c = (int64_t)blockIdx.x * 4 + wv; c < C; c += (int64_t)gridDim.x * 4) {
             const int64_t cbase = c * CHUNK;
             const uint32_t clen = (uint32_t)min((int64_t)CHUNK, d - cbase);
@@ -215,11 +225,11 @@ __global__ __launch_bounds__(256) void k_randk_shift_scatter(RksArgs g, int64_t 
 
 // Compat, shapes A / C / D: entry (row, t) of the bucketed lists gets its value t = e * msg_scale and,
 // in shape A, the thread that gathered b[j] stores h'.  An index >= d stores nothing.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_randk_shift_lists(RksArgs g, int64_t n, int64_t d, int64_t K, RkLists L) {
+template <int MODE, class M = MapNone>
+__global__ __launch_bounds__(256) void k_randk_shift_lists(RksArgs g, int64_t n, int64_t d, int64_t K, RkLists L, M map) {
     for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
         const float* ap = g.a + row * g.lda;
-        float* bp = g.b + row * g.ldb;
+        float* bp = g.b + map.at_s(row, FLC_IDX_B) * g.ldb;
         for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < K; t += (int64_t)gridDim.x * 256) {
             const int64_t j = (int64_t)L.idx[row * L.cap + t];
             float tt = 0.f;
@@ -235,11 +245,12 @@ __global__ __launch_bounds__(256) void k_randk_shift_lists(RksArgs g, int64_t n,
 }
 
 // Compat, shape B: one thread per (row, t) straight from the caller's index rows
+template <class M = MapNone>
 __global__ __launch_bounds__(256) void k_randk_shift_idx(RksArgs g, int64_t n, int64_t d, int64_t K,
-                                                         const int64_t* __restrict__ idx, int64_t ldi) {
+                                                         const int64_t* __restrict__ idx, int64_t ldi, M map) {
     for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
         const float* ap = g.a + row * g.lda;
-        float* bp = g.b + row * g.ldb;
+        float* bp = g.b + map.at_s(row, FLC_IDX_B) * g.ldb;
         for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < K; t += (int64_t)gridDim.x * 256) {
             const int64_t j = idx[row * ldi + t];
             if ((uint64_t)j < (uint64_t)d) {
@@ -314,21 +325,26 @@ int randk_shift_lfold_launch(const float* base, int64_t n, int64_t d, RkLists L,
     return FLC_OK;
 }
 
-size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n, int64_t d) {
+size_t randk_shift_workspace(const flc_codec_params* prm, bool compat, int64_t n, int64_t d, bool sampled) {
     if (n <= 0 || d <= 0) return 0;
-    if (compat) return randk_lists_workspace(n, d, std::max<int64_t>(1, prm->k));
-    return randk_device_workspace(n, d);
+    const size_t b = compat ? randk_lists_workspace(n, d, std::max<int64_t>(1, prm->k)) : randk_device_workspace(n, d);
+    return sampled ? align_up(b, 256) + sampled_tab_bytes(n) : b;   // + shape B's pointer table of the mapped rows
 }
 
-int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
-                    const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
-    const char* me = "flc_randk_shift_reduce";
+// mk: MapNone{} (the contiguous round: its launches as they were) or the sampled round's MapIds
+template <class M>
+static int randk_shift_go(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
+                          const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st,
+                          const flc_row_map* map, M mk) {
+    const char* me = map ? "flc_randk_shift_reduce_sampled" : "flc_randk_shift_reduce";
     const int shape = shift_shape(sr, me);
     if (shape < 0) return FLC_ERR_UNSUPPORTED;
     const bool compat = pat && pat->d_randk_idx;
     const int64_t K = prm->k;
-    if (int rc = sparse_round_precheck(me, shape, sr, n, d, K)) return rc;
-    if (ws_bytes < randk_shift_workspace(prm, compat, n, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
+    if (int rc = sparse_round_precheck(me, shape, sr, map_has(map, FLC_IDX_B) ? map->n_total : n, d, K)) return rc;
+    const size_t base_ws = randk_shift_workspace(prm, compat, n, d);
+    if (ws_bytes < randk_shift_workspace(prm, compat, n, d, map != nullptr)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
+    const float** tab = map ? reinterpret_cast<const float**>(static_cast<char*>(ws) + align_up(base_ws, 256)) : nullptr;
     const int64_t C = rks_chunks(d);
     RksArgs g{sr.d_a, sr.lda, const_cast<float*>(sr.d_b), sr.ldb, sr.d_base, prm->randk_scale, sr.msg_scale, sr.shift_alpha};
     const unsigned gy = (unsigned)std::min<int64_t>(n, 65535);
@@ -337,11 +353,11 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
             {
                 ProfScope _ps("k_randk_shift_lists", st);
                 const int gx = rks_blocks((K + 255) / 256, 1024);
-                hipLaunchKernelGGL(k_randk_shift_idx, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, pat->d_randk_idx,
-                                   pat->idx_ld ? pat->idx_ld : K);
+                hipLaunchKernelGGL(k_randk_shift_idx<M>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, pat->d_randk_idx,
+                                   pat->idx_ld ? pat->idx_ld : K, mk);
                 FLC_CHECK_LAUNCH("k_randk_shift_idx");
             }
-            return fold_updated_rows(sr, n, d, w, wt, out, st);
+            return fold_updated_rows(sr, n, d, w, wt, out, st, map, tab);
         }
         RkLists L;
         RowSrc rows{sr.d_a, sr.lda, nullptr};
@@ -349,8 +365,8 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
         {
             ProfScope _ps("k_randk_shift_lists", st);
             const int gx = rks_blocks((K + 255) / 256, 1024);
-            if (shape == SHAPE_A) hipLaunchKernelGGL(k_randk_shift_lists<SHAPE_A>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L);
-            else hipLaunchKernelGGL(k_randk_shift_lists<SHAPE_D>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L);
+            if (shape == SHAPE_A) hipLaunchKernelGGL((k_randk_shift_lists<SHAPE_A, M>), dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L, mk);
+            else hipLaunchKernelGGL((k_randk_shift_lists<SHAPE_D, M>), dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, K, L, mk);
             FLC_CHECK_LAUNCH("k_randk_shift_lists");
         }
         if (shape != SHAPE_C) return randk_lists_fold(n, d, K, ws, w, wt, out, st);
@@ -358,23 +374,23 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
     }
     const uint32_t* cnt = nullptr;
     const uint64_t* ckey = nullptr;
-    if (int rc = randk_device_prepare(prm, pat, n, d, ws, &cnt, &ckey, st)) return rc;
+    if (int rc = randk_device_prepare(prm, pat, n, d, ws, &cnt, &ckey, st, map)) return rc;
     if (shape == SHAPE_B) {
         {
             ProfScope _ps("k_randk_shift", st);
             const int gx = rks_blocks((C + 3) / 4, 4096);
-            hipLaunchKernelGGL(k_randk_shift_scatter, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, cnt, ckey);
+            hipLaunchKernelGGL(k_randk_shift_scatter<M>, dim3((unsigned)gx, gy), dim3(256), 0, st, g, n, d, cnt, ckey, mk);
             FLC_CHECK_LAUNCH("k_randk_shift_scatter");
         }
-        return fold_updated_rows(sr, n, d, w, wt, out, st);
+        return fold_updated_rows(sr, n, d, w, wt, out, st, map, tab);
     }
     ProfScope _ps("k_randk_shift", st);
     // few chunks (short rows): split each chunk's columns over 2 or 4 waves, as k_chunk_accum does
     const int parts = shape == SHAPE_C ? CHUNK / RKS_CTS : (C >= 1024 ? 1 : (C >= 256 ? 2 : 4));
     const int ab = rks_blocks((C * parts + 3) / 4, 16384);
     auto go = [&](auto ts, auto mode) {
-        hipLaunchKernelGGL((k_randk_shift<decltype(ts)::value, decltype(mode)::value>), dim3(ab), dim3(256), 0, st, g, n, d,
-                           cnt, ckey, w, wt, out);
+        hipLaunchKernelGGL((k_randk_shift<decltype(ts)::value, decltype(mode)::value, M>), dim3(ab), dim3(256), 0, st, g, n, d,
+                           cnt, ckey, w, wt, out, mk);
     };
     auto by_parts = [&](auto mode) {
         if (parts == 1) go(std::integral_constant<int, CHUNK>{}, mode);
@@ -386,6 +402,12 @@ int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const f
     else by_parts(std::integral_constant<int, SHAPE_D>{});
     FLC_CHECK_LAUNCH("k_randk_shift");
     return FLC_OK;
+}
+
+int randk_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
+                    const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st, const flc_row_map* map) {
+    if (map) return randk_shift_go(prm, pat, sr, n, d, w, wt, out, ws, ws_bytes, st, map, map_ids(map));
+    return randk_shift_go(prm, pat, sr, n, d, w, wt, out, ws, ws_bytes, st, nullptr, MapNone{});
 }
 
 }  // namespace flc

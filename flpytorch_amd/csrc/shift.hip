@@ -152,15 +152,19 @@ size_t shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d)
     return c.bytes();
 }
 
+// map (flc_encode_shift_reduce_sampled): participant i is client map->h_ids[i]; the elementwise
+// kernels read the device ids, the row loop below takes its row pointers and keys from the host ids
 int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows& sr, int64_t n, int64_t d,
-                     const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+                     const float* w, float wt, float* pnorms_out, float* out, void* ws, size_t ws_bytes, hipStream_t st,
+                     const flc_row_map* map) {
     if (n == 0 || d == 0) return FLC_OK;
-    if (ws_bytes < shift_reduce_workspace(prm, n, d)) { set_error("flc_encode_shift_reduce: workspace too small"); return FLC_ERR_WORKSPACE; }
+    const char* me = map ? "flc_encode_shift_reduce_sampled" : "flc_encode_shift_reduce";
+    if (ws_bytes < shift_reduce_workspace(prm, n, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
     if (shift_elementwise(prm->codec)) {
         const bool vec = ((((uintptr_t)sr.d_a | (uintptr_t)sr.d_b) & 15u) == 0) && (((sr.lda | sr.ldb) & 3) == 0);
         RowSrc a{sr.d_a, sr.lda, nullptr};
         return ew_run(prm, pat, a, vec, n, d, nullptr, pnorms_out, /*dense=*/false, out, w, wt, ws, ws_bytes, st, nullptr,
-                      nullptr, FLC_NORMMODE_EXACT, &sr);
+                      nullptr, FLC_NORMMODE_EXACT, &sr, map);
     }
     if (prm->codec == FLC_RANDK && !(pat && pat->d_randk_idx) && prm->k > d) { set_error("randk: K > D"); return FLC_ERR_ARG; }
     Carver c(ws);
@@ -177,10 +181,13 @@ int shift_reduce_run(const flc_codec_params* prm, const flc_pattern* pat, const 
             if (pat->d_lazy_u) pi.d_lazy_u = pat->d_lazy_u + i;
             pi.d_randk_counts = nullptr;        // (laid out [chunk][n]: one row's are computed inside)
         }
-        pi.client0 = (pat ? pat->client0 : 0) + i;
-        float* m = sr.d_msg ? sr.d_msg + i * sr.ldmsg : mrow;
-        ShiftArgs sh{sr.d_b + i * sr.ldb, sr.msg_scale, sr.d_base ? sr.d_base + i * sr.ldbase : nullptr, m, sr.shift_alpha,
-                     sr.d_shift_out ? sr.d_shift_in + i * sr.ldin : nullptr, sr.d_shift_out ? sr.d_shift_out + i * sr.ldout : nullptr};
+        const int64_t ci = map ? (int64_t)map->h_ids[i] : i;
+        auto at = [&](uint32_t bit) { return map_has(map, bit) ? ci : i; };   // the operand's row of participant i
+        pi.client0 = (pat ? pat->client0 : 0) + ci;
+        float* m = sr.d_msg ? sr.d_msg + at(FLC_IDX_MSG) * sr.ldmsg : mrow;
+        ShiftArgs sh{sr.d_b + at(FLC_IDX_B) * sr.ldb, sr.msg_scale, sr.d_base ? sr.d_base + at(FLC_IDX_BASE) * sr.ldbase : nullptr, m,
+                     sr.shift_alpha, sr.d_shift_out ? sr.d_shift_in + at(FLC_IDX_SHIFT_IN) * sr.ldin : nullptr,
+                     sr.d_shift_out ? sr.d_shift_out + at(FLC_IDX_SHIFT_OUT) * sr.ldout : nullptr};
         if (int rc = shift_run(prm, &pi, sr.d_a + i * sr.lda, d, sh, nullptr, iws, inner, st)) return rc;
         if (int rc = shift_fold_launch(m, d, w, i, i == n - 1, wt, out, st)) return rc;
     }
@@ -224,6 +231,7 @@ int shift_shape(const flc_shift_rows& sr, const char* me) {
 }
 
 int inplace_rows_check(const char* me, int shape, const flc_shift_rows& sr, int64_t n, int64_t d) {
+    // (n: the rows of the in-place matrix; a sampled round over indexed rows passes n_total)
     if (n > 1 && (shape == SHAPE_A || shape == SHAPE_B) && (sr.ldb < 0 ? -sr.ldb : sr.ldb) < d) {
         set_error("%s: the in-place rows overlap (|ldb| < d)", me);
         return FLC_ERR_ARG;
@@ -237,8 +245,28 @@ int sparse_round_precheck(const char* me, int shape, const flc_shift_rows& sr, i
     return inplace_rows_check(me, shape, sr, n, d);
 }
 
-int fold_updated_rows(const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt, float* out, hipStream_t st) {
+// the rows of an indexed operand as a pointer table: tab[i] = base + ids[i] * ld
+__global__ __launch_bounds__(256) void k_row_ptrs(const float* base, int64_t ld, MapIds map, int64_t n, const float** tab) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) tab[i] = base + map.id(i) * ld;
+}
+
+int row_ptrs_launch(const float* base, int64_t ld, const flc_row_map* map, int64_t n, const float** tab, hipStream_t st) {
+    hipLaunchKernelGGL(k_row_ptrs, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 256)), dim3(256), 0, st, base, ld,
+                       map_ids(map), n, tab);
+    FLC_CHECK_LAUNCH("k_row_ptrs");
+    return FLC_OK;
+}
+
+size_t sampled_tab_bytes(int64_t n) { return align_up((size_t)std::max<int64_t>(n, 1) * sizeof(const float*), 256); }
+
+int fold_updated_rows(const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt, float* out, hipStream_t st,
+                      const flc_row_map* map, const float** tab) {
     const bool vec = (((uintptr_t)sr.d_b & 15u) == 0) && (sr.ldb % 4 == 0);
+    if (map_has(map, FLC_IDX_B)) {
+        if (int rc = row_ptrs_launch(sr.d_b, sr.ldb, map, n, tab, st)) return rc;
+        RowSrc rows{nullptr, 0, tab};
+        return reduce_impl(rows, vec, n, d, nullptr, w, wt, FLC_REDUCE_PLAIN, out, st);
+    }
     RowSrc rows{sr.d_b, sr.ldb, nullptr};
     return reduce_impl(rows, vec, n, d, nullptr, w, wt, FLC_REDUCE_PLAIN, out, st);
 }

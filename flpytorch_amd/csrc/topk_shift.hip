@@ -36,11 +36,12 @@ constexpr int TKS_U = 4;              // float4 load pairs a thread keeps in fli
 
 // diff[r][j] = a_r[j] - b_r[j], j < d (nothing at [d, ldd)).  VEC: every a and b row 16-B aligned; a and
 // b are read once (nontemporal), the difference is stored plainly: the filter reads it next.
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_shift_sub_rows(TksArgs g, int64_t n, int64_t d) {
+// M (flc_topk_shift_reduce_sampled): b_r is the participant's client row where b is indexed.
+template <bool VEC, class M = MapNone>
+__global__ __launch_bounds__(256) void k_shift_sub_rows(TksArgs g, int64_t n, int64_t d, M map) {
     for (int64_t row = blockIdx.y; row < n; row += gridDim.y) {
         const float* ap = g.a + row * g.lda;
-        const float* bp = g.b + row * g.ldb;
+        const float* bp = g.b + map.at_s(row, FLC_IDX_B) * g.ldb;
         float* dp = g.diff + row * g.ldd;
         int64_t done = 0;
         if (VEC) {
@@ -75,8 +76,8 @@ __global__ __launch_bounds__(256) void k_shift_sub_rows(TksArgs g, int64_t n, in
 // admitted entry's value is e = v: the in-place element is stored by the thread that gathered it
 // (a row's admitted indices are distinct) and, in A / C / D, the value becomes t = e * msg_scale.  A
 // rejected entry (or an index >= d) becomes 0xFFFFFFFF, "no column" to every list consumer.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_topk_shift_lists(TksArgs g, int64_t n, int64_t d, TkLists L) {
+template <int MODE, class M = MapNone>
+__global__ __launch_bounds__(256) void k_topk_shift_lists(TksArgs g, int64_t n, int64_t d, TkLists L, M map) {
     const int lane = threadIdx.x & 63;
     const int wv = threadIdx.x >> 6;
     const int64_t C = nchunks(d);
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(256) void k_topk_shift_lists(TksArgs g, int64_t n, 
         if (f & TK_F_EXACT) T = 0u;                            // exact list: every entry admitted
         else if (f & TK_F_TIES) cut = L.tiecut[row] ^ txm;
         const uint64_t bound = ((uint64_t)T << 32) | (uint64_t)cut;
-        float* bp = g.b + row * g.ldb;
+        float* bp = g.b + map.at_s(row, FLC_IDX_B) * g.ldb;
         for (int64_t c = (int64_t)blockIdx.x * 4 + wv; c < C; c += (int64_t)gridDim.x * 4) {
             const uint2 te = L.tab[c * n + row];
             for (uint32_t e = (uint32_t)lane; e < te.y; e += 64) {
@@ -130,38 +131,45 @@ __global__ __launch_bounds__(256) void k_topk_shift_admit(int64_t n, TkLists L) 
 static int64_t tks_ldd(int64_t d) { return (d + 3) & ~int64_t(3); }
 
 // the selection state first, exactly flc_encode_reduce's carve (flc_select_row_flags reads it at the
-// workspace base), then the difference matrix
-size_t topk_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d) {
+// workspace base), then the difference matrix; a sampled round: then shape B's pointer table
+size_t topk_shift_workspace(const flc_codec_params* prm, int64_t n, int64_t d, bool sampled) {
     if (n <= 0 || d <= 0) return 0;
     Carver c(nullptr);
     c.take<char>(sel_workspace(prm, n, d));
     c.take<float>((size_t)n * (size_t)tks_ldd(d));
+    if (sampled) c.take<char>(sampled_tab_bytes(n));
     return c.bytes();
 }
 
-int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt,
-                   float* out, void* ws, size_t ws_bytes, hipStream_t st) {
-    const char* me = "flc_topk_shift_reduce";
+// mk: MapNone{} (the contiguous round: its launches as they were) or the sampled round's MapIds
+template <class M>
+static int topk_shift_go(const flc_codec_params* prm, const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt,
+                         float* out, void* ws, size_t ws_bytes, hipStream_t st, const flc_row_map* map, M mk) {
+    const char* me = map ? "flc_topk_shift_reduce_sampled" : "flc_topk_shift_reduce";
     const int shape = shift_shape(sr, me);
     if (shape < 0) return FLC_ERR_UNSUPPORTED;
     const int64_t K = prm->k;
-    if (int rc = sparse_round_precheck(me, shape, sr, n, d, K)) return rc;
-    if (ws_bytes < topk_shift_workspace(prm, n, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
+    const bool b_mapped = map_has(map, FLC_IDX_B);
+    if (int rc = sparse_round_precheck(me, shape, sr, b_mapped ? map->n_total : n, d, K)) return rc;
+    if (ws_bytes < topk_shift_workspace(prm, n, d, map != nullptr)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
     const int64_t ldd = tks_ldd(d);
     Carver cv(ws);
     const size_t sel_bytes = sel_workspace(prm, n, d);
     void* sws = cv.take<char>(sel_bytes);
     float* diff = cv.take<float>((size_t)n * (size_t)ldd);
+    const float** tab = map ? reinterpret_cast<const float**>(cv.take<char>(sampled_tab_bytes(n))) : nullptr;
     TksArgs g{sr.d_a, sr.lda, const_cast<float*>(sr.d_b), sr.ldb, diff, ldd, sr.msg_scale, sr.shift_alpha};
     const unsigned gy = (unsigned)std::min<int64_t>(n, 65535);
     {
         ProfScope _ps("k_shift_sub_rows", st);
-        const bool vec = ((((uintptr_t)sr.d_a | (uintptr_t)sr.d_b) & 15u) == 0) && (n == 1 || ((sr.lda | sr.ldb) & 3) == 0);
+        // (b's leading dimension matters as soon as a second row of the matrix can be read)
+        const bool one_b = b_mapped ? map->n_total == 1 : n == 1;
+        const bool vec = ((((uintptr_t)sr.d_a | (uintptr_t)sr.d_b) & 15u) == 0) && ((n == 1 || (sr.lda & 3) == 0) && (one_b || (sr.ldb & 3) == 0));
         // capped and strided like the other streaming kernels: ~16 K workgroups over all rows
         const int64_t per_row = vec ? (d / 4 + 256 * TKS_U - 1) / (256 * TKS_U) : (d + 1023) / 1024;
         const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(per_row, std::max<int64_t>(1, 16384 / gy)));
-        if (vec) hipLaunchKernelGGL(k_shift_sub_rows<true>, dim3(gx, gy), dim3(256), 0, st, g, n, d);
-        else hipLaunchKernelGGL(k_shift_sub_rows<false>, dim3(gx, gy), dim3(256), 0, st, g, n, d);
+        if (vec) hipLaunchKernelGGL((k_shift_sub_rows<true, M>), dim3(gx, gy), dim3(256), 0, st, g, n, d, mk);
+        else hipLaunchKernelGGL((k_shift_sub_rows<false, M>), dim3(gx, gy), dim3(256), 0, st, g, n, d, mk);
         FLC_CHECK_LAUNCH("k_shift_sub_rows");
     }
     TkLists L;
@@ -172,19 +180,25 @@ int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_
         const int64_t C = nchunks(d);
         const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((C + 3) / 4, std::max<int64_t>(1, 32768 / gy)));
         const dim3 grid(gx, gy);
-        if (shape == SHAPE_A) hipLaunchKernelGGL(k_topk_shift_lists<SHAPE_A>, grid, dim3(256), 0, st, g, n, d, L);
-        else if (shape == SHAPE_B) hipLaunchKernelGGL(k_topk_shift_lists<SHAPE_B>, grid, dim3(256), 0, st, g, n, d, L);
-        else hipLaunchKernelGGL(k_topk_shift_lists<SHAPE_D>, grid, dim3(256), 0, st, g, n, d, L);
+        if (shape == SHAPE_A) hipLaunchKernelGGL((k_topk_shift_lists<SHAPE_A, M>), grid, dim3(256), 0, st, g, n, d, L, mk);
+        else if (shape == SHAPE_B) hipLaunchKernelGGL((k_topk_shift_lists<SHAPE_B, M>), grid, dim3(256), 0, st, g, n, d, L, mk);
+        else hipLaunchKernelGGL((k_topk_shift_lists<SHAPE_D, M>), grid, dim3(256), 0, st, g, n, d, L, mk);
         FLC_CHECK_LAUNCH("k_topk_shift_lists");
     }
     hipLaunchKernelGGL(k_topk_shift_admit, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 256)), dim3(256), 0, st, n, L);
     FLC_CHECK_LAUNCH("k_topk_shift_admit");
-    if (shape == SHAPE_B) return fold_updated_rows(sr, n, d, w, wt, out, st);
+    if (shape == SHAPE_B) return fold_updated_rows(sr, n, d, w, wt, out, st, map, tab);
     if (shape == SHAPE_C) {
         RkLists R{L.tab, L.ent_idx, L.ent_val, L.cap};
         return randk_shift_lfold_launch(sr.d_base, n, d, R, w, wt, out, st);
     }
     return topk_lists_fold(prm, n, d, sws, w, wt, out, st);
+}
+
+int topk_shift_run(const flc_codec_params* prm, const flc_shift_rows& sr, int64_t n, int64_t d, const float* w, float wt,
+                   float* out, void* ws, size_t ws_bytes, hipStream_t st, const flc_row_map* map) {
+    if (map) return topk_shift_go(prm, sr, n, d, w, wt, out, ws, ws_bytes, st, map, map_ids(map));
+    return topk_shift_go(prm, sr, n, d, w, wt, out, ws, ws_bytes, st, nullptr, MapNone{});
 }
 
 }  // namespace flc

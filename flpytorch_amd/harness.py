@@ -55,6 +55,13 @@ client step is the fused shift codec (``Compressor.compressShift``, one flc_enco
                                    x_prev = the round's starting iterate, g_server_prev = the result
 
 The others' serverGradient bodies are covered by ``aggregation.install``.
+
+``resident=True`` (DIANA, EF21, COFIG): the per-client state (h_i / g_i) lives in ONE
+[num_clients, D] device matrix instead of in the history records, and each local iteration of a
+round runs the sampled clients' steps as one call over the rows the sampling picked
+(``ShiftUplinkReducer(..., clients=ids)``, the ``_sampled`` entries), with the compat patterns in
+participant order.  Draw order, local steps, folds, history scalars and wire counts are those of the
+default mode, and so are the iterates, bit for bit.
 """
 import math
 import threading
@@ -241,13 +248,15 @@ class Simulation:
     ``cofig_step`` / ``frecon_step`` default to the product (flpytorch_amd.aggregation: HIP codecs,
     HIP fold, fused shift codec); tests may pass other implementations of the same protocol.
     ``algorithm_options``: the run's ``--algorithm-options`` string (or a dict); FRECON reads its
-    ``lambda_`` from it."""
+    ``lambda_`` from it.  ``resident=True`` (diana, ef21, cofig; no wire modes): the module docstring's
+    resident mode — same run, the clients' state rows in one device matrix, one sampled call per local
+    iteration."""
 
     def __init__(self, algorithm, client_compressor, model, x0, num_clients, clients_per_round, rounds,
                  local_lr, global_lr, local_iters=1, runtime_seed=0, device="cuda", sampling="uniform",
                  poisson_p=None, init_compressor=None, server_gradient=None, record_iterates=False, wire=False,
                  initialize_shifts_policy="zero", diana_step=None, ef21_step=None, marina_step=None, shift_wire=False,
-                 cofig_step=None, frecon_step=None, algorithm_options=None):
+                 cofig_step=None, frecon_step=None, algorithm_options=None, resident=False):
         algorithm = algorithm.lower()
         if algorithm not in ALGORITHMS:
             raise ValueError(f"harness drives {', '.join(ALGORITHMS)}, not {algorithm!r}")  # algorithms.py:1954 style
@@ -259,6 +268,8 @@ class Simulation:
             raise ValueError("shift_wire drives the shifted steps' messages (diana, ef21, marina) only")
         if wire and algorithm != "dcgd":
             raise ValueError("wire mode drives DCGD's compressVector messages only")
+        if resident and (algorithm not in ("diana", "ef21", "cofig") or wire or shift_wire):
+            raise ValueError("resident=True keeps the state rows of diana, ef21 or cofig on the device, without wire / shift_wire")
         if initialize_shifts_policy not in ("zero", "full_gradient_at_start"):
             raise ValueError(f"unknown initialize_shifts_policy {initialize_shifts_policy!r}")  # opts.py:437-441
         options = parse_algorithm_options(algorithm_options)
@@ -345,6 +356,16 @@ class Simulation:
             if algorithm == "frecon":
                 self.H.update({"g0": grad_start.clone(), "g_server_prev": grad_start.clone(),
                                "x_prev": self.x.clone()})
+        # resident=True: row c of `state` is client c's h_i (DIANA / COFIG: h0 until its first step) or
+        # g_i (EF21: no row until its first, uncompressed step: state_set[c])
+        self.resident = bool(resident)
+        if self.resident:
+            gpu = self.device if self.device.type == "cuda" else torch.device("cuda")
+            self.state = torch.zeros((self.num_clients, self.D), dtype=torch.float32, device=gpu)
+            self.state_set = [algorithm != "ef21"] * self.num_clients
+            if algorithm != "ef21":
+                self.state.copy_(self.H["h0"].to(gpu).unsqueeze(0).expand_as(self.state))
+            self.uplink = ag.ShiftUplinkReducer(ag.initCompressor(self.spec, self.D), device=gpu)
 
     # algorithms.clientState (2015-2069) with the class parts: DCGD 1729-1732, FedAvg 1793-1794,
     # DIANA 1360-1373, EF21 1471-1484, MARINA 495-509, COFIG 1236-1249, FRECON 1070-1089
@@ -358,11 +379,12 @@ class Simulation:
             p = 1.0 / (1.0 + comp.getW())
             cs.update({"p": p, "ck": 1 if self.H["test_ber_rv"] <= p else 0})
         if self.algorithm in ("diana", "cofig", "frecon"):
-            hi = find_recent_and_remove(self.H, client_id, "hi")
-            cs["hi"] = self.H["h0"].detach().clone() if hi is None else hi
+            if not self.resident:                                                # (resident: row client_id of self.state)
+                hi = find_recent_and_remove(self.H, client_id, "hi")
+                cs["hi"] = self.H["h0"].detach().clone() if hi is None else hi
             if self.algorithm != "diana":
                 cs["alpha"] = 1.0 / (1.0 + comp.getW())
-        elif self.algorithm == "ef21":
+        elif self.algorithm == "ef21" and not self.resident:
             cs["g_prev"] = find_recent_and_remove(self.H, client_id, "g_prev")
         cs.update({"algorithm": self.algorithm, "client_id": client_id, "weight": 1.0, "round": rnd,
                    "approximate_f_value": [], "seed": self.np_random.randint(2 ** 31),
@@ -500,6 +522,64 @@ class Simulation:
             xi.add_(c.to(xi.device), alpha=-self.local_lr)                      # SGD step, momentum 0
         return {"model": xi, "client_id": client_id, "client_state": cs}
 
+    # resident=True: the sampled clients of a round in lockstep.  clientState draws (pattern, seed)
+    # per client in the reference's order first: local training draws nothing from the stream
+    def resident_training(self, clients, rnd):
+        ids = [int(c) for c in clients]
+        states = [self.client_state(cid, rnd) for cid in ids]
+        xs = [self.x.clone() for _ in ids]
+        for _ in range(self.local_iters if ids else 0):
+            fg = [self.model.value_and_gradient(xi, cid) for xi, cid in zip(xs, ids)]
+            G = torch.stack([g.to(self.state.device) for _, g in fg])
+            C = self.resident_step(states, ids, G)
+            for xi, cs, (f, _), c in zip(xs, states, fg, C):
+                cs["approximate_f_value"].append(f)
+                xi.add_(c.to(xi.device), alpha=-self.local_lr)                  # SGD step, momentum 0
+        return [{"model": xi, "client_id": cid, "client_state": cs} for xi, cid, cs in zip(xs, ids, states)]
+
+    def resident_patterns(self, comps):
+        """The clients' compat patterns as the rows of one call, in participant order."""
+        t, dev = comps[0].compressorType, self.state.device
+        if t == ag.CompressorType.RANDK_COMPRESSOR:
+            return {"randk_idx": torch.stack([c.S.to(device=dev, dtype=torch.int64) for c in comps])}
+        if t in (ag.CompressorType.NATURAL_COMPRESSOR_FP32, ag.CompressorType.STANDARD_DITHERING_FP32,
+                 ag.CompressorType.NATURAL_DITHERING_FP32):
+            return {"uniforms": torch.stack([c.testp.to(device=dev) for c in comps])}
+        if t == ag.CompressorType.LAZY_COMPRESSOR:
+            return {"lazy_u": torch.tensor([c.testp for c in comps], dtype=torch.float64, device=dev)}
+        return {}
+
+    def resident_step(self, states, ids, G):
+        """client_step for every sampled client at once: G [n, D] the local gradients, the result
+        [n, D] the vectors their local steps apply; the state rows ids are updated in place."""
+        if self.algorithm == "ef21":                                             # algorithms.py:1494-1518
+            C = torch.empty_like(G)
+            have = [i for i, cid in enumerate(ids) if self.state_set[cid]]
+            for i, cid in enumerate(ids):
+                if not self.state_set[cid]:                                      # (first step: not counted)
+                    self.state[cid].copy_(G[i])
+                    self.state_set[cid] = True
+                    C[i].copy_(G[i])
+            if not have:
+                return C
+            comps = [states[i]["client_compressor"] for i in have]
+            sub = [ids[i] for i in have]
+            mult = 1.0 if comps[0].isContractionCompressor() else 1.0 / (1.0 + comps[0].getW())
+            self.uplink(G if len(have) == len(ids) else G[have], self.state, scale=mult, base=self.state,
+                        msg_out=self.state, clients=sub, **self.resident_patterns(comps))
+            C[have] = self.state[sub]
+        else:                                                                    # algorithms.py:1383-1392, 1265-1270
+            have = list(range(len(ids)))
+            comps = [cs["client_compressor"] for cs in states]
+            alpha = self.H["alpha"] if self.algorithm == "diana" else states[0]["alpha"]
+            C = torch.empty_like(G)
+            self.uplink(G, self.state, alpha=alpha, shift=self.state, shift_out=self.state, msg_out=C, clients=ids,
+                        indexed=("b", "shift", "shift_out"), **self.resident_patterns(comps))
+        for i, comp in zip(have, comps):                                         # each client's own wire count
+            comp._account(self.D)
+            states[i]["stats"]["send_scalars_to_master"] += comp.last_need_to_send_advance
+        return C
+
     # run_one_communication_round (model_funcs.py:459-614)
     def run_round(self, rnd):
         if self.H.get("request_use_full_list_of_clients"):                       # model_funcs.py:470-475
@@ -507,9 +587,13 @@ class Simulation:
         else:
             clients = self.sampled[rnd]
         buf = _Buffer()
-        for cid in clients:
-            cs = self.client_state(int(cid), rnd)
-            buf.pushBack(self.local_training(cs, int(cid)))
+        if self.resident:
+            for item in self.resident_training(clients, rnd):
+                buf.pushBack(item)
+        else:
+            for cid in clients:
+                cs = self.client_state(int(cid), rnd)
+                buf.pushBack(self.local_training(cs, int(cid)))
         n = len(clients)
         x_prev = self.x.clone()
         if n == 0:

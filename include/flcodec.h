@@ -380,6 +380,72 @@ int flc_topk_shift_reduce(const flc_codec_params* prm, const flc_shift_rows* row
                           void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Partial participation: the three shifted rounds above over SAMPLED client rows (additive:
+ * flc_version() stays 104, detect the entries by their symbols).  Of n_total resident clients n take
+ * part in a round (the reference's --num-clients-per-round; EF21-PP, PP-MARINA): participant
+ * i = 0..n-1, in this order, is client ids[i].  Each _sampled entry is its contiguous sibling with a
+ * row map after `rows`; apart from addresses and keys nothing changes:
+ *   - a_i is always at d_a + i * lda (this round's gradients);
+ *   - an operand whose FLC_IDX_ bit is set in `indexed` is a state matrix of n_total rows addressed
+ *     by id: its row for participant i is at ptr + ids[i] * ld.  An operand whose bit is clear is at
+ *     ptr + i * ld as in the sibling (MARINA's previous-gradient rows are fresh per round and stay
+ *     unindexed).  A shared base (ldbase == 0) is never indexed.  Bits of absent operands are ignored;
+ *   - draws and row keys are those of client pat->client0 + ids[i], so a client's device draws do not
+ *     depend on the company it keeps in a round;
+ *   - compat pattern rows (d_uniforms, d_randk_idx, d_lazy_u), d_w and d_pnorms_out stay in
+ *     participant order i;
+ *   - the fold runs in participant order, the first term assigned, one division at the end.
+ * Row ids[i] of an indexed output and d_out carry exactly the bits flc_encode_shift gives for
+ * (a_i, b_{ids[i]}, ...) under client client0 + ids[i], followed by the sequential fold.  Rows of an
+ * indexed operand that are not named in ids are neither read nor written.  The sparse and the batched
+ * entry keep the shape table (A - D) and THE CONTRACT on untouched elements of
+ * flc_randk_shift_reduce word for word.  "In place" now means same pointer, same leading dimension
+ * and the same `indexed` bit.
+ *
+ * Elementwise codecs run the sibling's kernels in their row-mapped instantiations (the id is
+ * wave-uniform and read through the scalar cache): an in-place DIANA round moves 12 n d bytes (20 n d
+ * with dithering's norm pass) where gathering the state rows, running the contiguous round and
+ * scattering them back moves 16 n d more.  RandK / TopK / Rank-K of the general entry run row by row
+ * from h_ids (correct, not a fast path).
+ *
+ * Checked before any launch, a refused call writes nothing — FLC_ERR_ARG: a null map, h_ids or d_ids
+ * with n * d > 0; n_total < 1 or above 2^31 - 1; an unknown bit in `indexed`; an id outside
+ * [0, n_total); duplicate ids when an output operand is indexed; an indexed output whose rows overlap
+ * (|ld| < d, n_total > 1); an output with the pointer and leading dimension of an operand whose
+ * `indexed` bit differs from its own; FLC_IDX_BASE with a shared base (ldbase == 0); d_randk_counts
+ * given to flc_randk_shift_reduce_sampled (there is no id-keyed form of flc_device_randk_counts; the
+ * entry computes its counts itself).  Every check of the contiguous sibling applies unchanged
+ * (FLC_ERR_UNSUPPORTED and FLC_ERR_WORKSPACE included, the latter against the _sampled size query).
+ * n == 0 or d == 0: FLC_OK, the device is not touched.  h_ids is read only during the call; d_ids by
+ * the kernels, on `stream`.
+ * -------------------------------------------------------------------------------------- */
+#define FLC_IDX_B 1
+#define FLC_IDX_BASE 2
+#define FLC_IDX_MSG 4
+#define FLC_IDX_SHIFT_IN 8
+#define FLC_IDX_SHIFT_OUT 16
+typedef struct {
+    const int32_t* h_ids;  /* host [n]: checked before any launch; drives the row-at-a-time paths */
+    const int32_t* d_ids;  /* device [n]: the same values, read by the kernels */
+    int64_t n_total;       /* rows of every indexed operand; every id in [0, n_total) */
+    uint32_t indexed;      /* which per-row operands are state matrices addressed by id */
+} flc_row_map;
+
+size_t flc_encode_shift_reduce_sampled_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_encode_shift_reduce_sampled(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
+                                    const flc_row_map* map, int64_t n, int64_t d, const float* d_w, float w_total,
+                                    float* d_pnorms_out, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+size_t flc_randk_shift_reduce_sampled_workspace_size(const flc_codec_params* prm, const flc_pattern* pat, int64_t n,
+                                                     int64_t d);
+int flc_randk_shift_reduce_sampled(const flc_codec_params* prm, const flc_pattern* pat, const flc_shift_rows* rows,
+                                   const flc_row_map* map, int64_t n, int64_t d, const float* d_w, float w_total,
+                                   float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+size_t flc_topk_shift_reduce_sampled_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_topk_shift_reduce_sampled(const flc_codec_params* prm, const flc_shift_rows* rows, const flc_row_map* map,
+                                  int64_t n, int64_t d, const float* d_w, float w_total, float* d_out,
+                                  void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * One-read QSGD shifted round (additive: flc_version() stays 104, detect the entry by its symbol).
  * flc_encode_shift_reduce runs FLC_STD_DITHERING in two full reads: the norms of the n differences
  * (8 n d bytes), then the encode, which also stores every element of an in-place operand (12 n d

@@ -70,6 +70,21 @@ each on its own copy of H and of h_prev, interleaved in one process on one alloc
 the results, the H matrices and the two h_prev vectors are compared as int32.  Byte models (N D terms):
 QSGD 28 N D against 36 N D, natural 16 N D against 20 N D.  Writes <out-dir>/<spec>.jsonl (default
 profiles/r14/frecon).  --fused-libs adds "one_call@<tag>" legs as above (timing only, the bit check off).
+
+--sampled (partial participation; default specs qsgd:127,natural,randk:1%,topk:1%; device draws): n = --n
+participants of --n-total resident clients (default 512), their ids a seeded draw without replacement, the
+state an [n_total, d] matrix.  The in-place DIANA round (qsgd, natural: the general entry; randk: sparse=True)
+or the in-place EF21 round (topk: batched=True) three ways,
+  sampled    ShiftUplinkReducer(G, S, ..., clients=ids)                     the _sampled entry
+  gathered   S.index_select(0, ids), the contiguous entry on the copy, S.index_copy_(0, ids, copy): what a
+             caller had to do before (16 n d more bytes)
+  pregather  the contiguous entry on rows gathered once, outside the clock: what the indirection itself costs
+each on its own state, interleaved in one process on one allocation.  After every repeat the participants'
+rows and the outputs of gathered and pregather are compared as int32, and so are sampled's wherever the codec
+draws nothing (TopK): with device draws the sampled call keys client ids[i] where the contiguous entry keys
+position i, so their bits differ by design (tests/test_gpu_sampled_round.py pins the sampled bits).  Byte
+models (n d terms): qsgd 20 against 36, natural 12 against 28.  Writes <out-dir>/<spec>.jsonl (default
+profiles/r15/sampled).
 """
 import argparse
 import json
@@ -660,6 +675,129 @@ def main_frecon(a):
         print("wrote", path, flush=True)
 
 
+def main_sampled(a):
+    import numpy as np
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d, nt = a.n, a.d, a.n_total
+    if n > nt:
+        raise SystemExit("--sampled: --n participants of --n-total clients")
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev)
+
+    def fill(t, seed):
+        gen.manual_seed(seed)
+        for i in range(0, t.shape[0], 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    ids = [int(c) for c in np.random.RandomState(SEED % (1 << 31)).choice(nt, n, replace=False)]
+    ids_t = torch.tensor(ids, dtype=torch.int64, device=dev)
+    G = fill(torch.empty((n, d), dtype=torch.float32, device=dev), 1000)
+    Sa, Sb = (torch.empty((nt, d), dtype=torch.float32, device=dev) for _ in range(2))   # (no third copy: refilled per spec)
+    T, Hc = torch.empty_like(G), torch.empty_like(G)
+    outs = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in ("sampled", "gathered", "pregather")}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for spec in a.specs.split(","):
+        comps = [ag.initCompressor(spec, d) for _ in range(3)]
+        reds = [ag.ShiftUplinkReducer(c, device=dev, seed=SEED) for c in comps]
+        fast = {"sparse": True} if spec.startswith("randk") else {"batched": True} if spec.startswith("topk") else {}
+        ef21 = spec.startswith("topk")
+        alpha = None if ef21 else 1.0 / (1.0 + comps[0].getW())
+
+        def round_on(red, H, out, **kw):
+            if ef21:
+                red(G, H, base=H, msg_out=H, out=out, **fast, **kw)
+            else:
+                red(G, H, alpha=alpha, shift=H, shift_out=H, out=out, **fast, **kw)
+        Sb.copy_(fill(Sa, 1001))
+        torch.index_select(Sa, 0, ids_t, out=Hc)
+
+        def run_sampled():
+            round_on(reds[0], Sa, outs["sampled"], clients=ids)
+
+        def run_gathered():
+            torch.index_select(Sb, 0, ids_t, out=T)
+            round_on(reds[1], T, outs["gathered"])
+            Sb.index_copy_(0, ids_t, T)
+
+        def run_pregather():
+            round_on(reds[2], Hc, outs["pregather"])
+        runs = {"sampled": run_sampled, "gathered": run_gathered, "pregather": run_pregather}
+        dither = not (spec.startswith("natural") or fast)
+        model = None
+        if not fast:
+            per = 20 if dither else 12
+            model = {"sampled": per * n * d + 4 * d, "gathered": (per + 16) * n * d + 4 * d, "pregather": per * n * d + 4 * d}
+        for f in runs.values():                        # warm: code objects, workspaces
+            f()
+        torch.cuda.synchronize()
+
+        def same_rows(X, Y_rows):
+            return all(torch.equal(X[c].view(torch.int32), Y_rows[i].view(torch.int32)) for i, c in enumerate(ids))
+
+        def agree():
+            ok = torch.equal(outs["gathered"].view(torch.int32), outs["pregather"].view(torch.int32)) and same_rows(Sb, Hc)
+            if ok and ef21:                            # no draws: the sampled call's bits are the contiguous entry's
+                ok = torch.equal(outs["sampled"].view(torch.int32), outs["pregather"].view(torch.int32)) and same_rows(Sa, Hc)
+            return ok
+        if not agree():
+            raise SystemExit(f"{spec}: the legs differ after the warm-up round")
+        ms = {v: [] for v in runs}
+        path = os.path.join(a.out_dir, spec.replace(":", "_").replace(".", "_").replace("%", "pct") + ".jsonl")
+        with open(path, "w") as fh:
+            def emit(rec):
+                line = json.dumps(rec)
+                fh.write(line + "\n")
+                fh.flush()
+                print(line, flush=True)
+            for r in range(a.repeats):
+                for v, f in runs.items():
+                    e0.record()
+                    for _ in range(a.steps):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    t = e0.elapsed_time(e1) / a.steps
+                    ms[v].append(t)
+                    emit({"spec": spec, "n": n, "n_total": nt, "d": d, "repeat": r, "variant": v, "ms_per_call": round(t, 4)})
+                if not agree():
+                    raise SystemExit(f"{spec}: the legs differ after repeat {r}")
+            kernels = ("k_ew_shift_accum", "k_norm_partials", "k_randk_shift", "k_randk_counts", "k_shift_sub_rows",
+                       "k_topk_shift_lists", "k_topk_filter", "k_chunk_accum", "k_reduce_vec")
+            kms = {}
+            for v in ("sampled", "pregather"):
+                _lib.profile_enable(True)
+                for kn in kernels:
+                    _lib.profile_collect(kn)
+                runs[v]()
+                torch.cuda.synchronize()
+                _lib.profile_enable(False)
+                kms[v] = {kn: round(t, 4) for kn in kernels for t, c in [_lib.profile_collect(kn)] if c}
+            med = {v: statistics.median(ms[v]) for v in runs}
+            rec = {"spec": spec, "n": n, "n_total": nt, "d": d, "summary": True, "repeats": a.repeats, "steps": a.steps,
+                   "round": ("ef21 in place" if ef21 else "diana in place") + (", " + next(iter(fast)) if fast else ""),
+                   "median_ms": {v: round(med[v], 4) for v in runs},
+                   "min_ms": {v: round(min(ms[v]), 4) for v in runs},
+                   "max_ms": {v: round(max(ms[v]), 4) for v in runs},
+                   "gathered_over_sampled": round(med["gathered"] / med["sampled"], 3),
+                   "sampled_over_pregather": round(med["sampled"] / med["pregather"], 3),
+                   "sampled_faster_than_gathered_beyond_spread": max(ms["sampled"]) < min(ms["gathered"]),
+                   "sampled_slower_than_pregather_beyond_spread": min(ms["sampled"]) > max(ms["pregather"]),
+                   "bits_compared": "gathered = pregather" + (" = sampled" if ef21 else " (sampled draws by client id)"),
+                   "kernel_ms_one_call": kms}
+            if model:
+                rec["algorithmic_bytes"] = model
+                rec["GBps_at_median"] = {v: round(model[v] / med[v] / 1e6, 1) for v in runs}
+                rec["byte_model_gathered_over_sampled"] = round(model["gathered"] / model["sampled"], 3)
+            emit(rec)
+        print("wrote", path, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--specs", default="natural,qsgd:127")
@@ -675,7 +813,13 @@ def main():
     ap.add_argument("--wire", action="store_true", help="flc_pack_shift / flc_unpack_shift_reduce against their compositions")
     ap.add_argument("--frecon", action="store_true", help="flc_frecon_reduce against two fused rounds plus the tail in torch")
     ap.add_argument("--shapes", default="diana,ef21", help="--topk / --one-read: the in-place rounds to time")
+    ap.add_argument("--sampled", action="store_true", help="the _sampled entries against gather + contiguous entry + scatter")
+    ap.add_argument("--n-total", type=int, default=512, help="--sampled: resident clients (rows of the state matrix)")
     a = ap.parse_args()
+    if a.sampled and a.out_dir == ap.get_default("out_dir"):
+        a.out_dir = os.path.join(ROOT, "profiles", "r15", "sampled")
+    if a.sampled and a.specs == ap.get_default("specs"):
+        a.specs = "qsgd:127,natural,randk:1%,topk:1%"
     if a.topk and a.out_dir == ap.get_default("out_dir"):
         a.out_dir = os.path.join(ROOT, "profiles", "r11", "topk_shift")
     if a.one_read and a.out_dir == ap.get_default("out_dir"):
@@ -692,6 +836,8 @@ def main():
         a.specs = "qsgd:127,natural"
     if a.repeats < 1 or a.steps < 1 or a.n < 1 or a.d < 1:
         ap.error("--repeats, --steps, --n and --d are positive")
+    if a.sampled:
+        return main_sampled(a)
     if a.sparse:
         return main_sparse(a)
     if a.topk:
