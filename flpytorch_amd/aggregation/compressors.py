@@ -115,6 +115,15 @@ def nat_levels(levels):
     return torch.flip(v, dims=[0])
 
 
+# the byte-format wire entries and their bit-packed counterparts (Compressor._wire_entry)
+_BITS_ENTRY = {
+    "flc_payload_bytes": "flc_payload_bits_bytes", "flc_payload_validate": "flc_payload_validate_bits",
+    "flc_pack_workspace_size": "flc_pack_bits_workspace_size", "flc_pack": "flc_pack_bits",
+    "flc_unpack": "flc_unpack_bits", "flc_unpack_reduce_workspace_size": "flc_unpack_reduce_bits_workspace_size",
+    "flc_unpack_reduce": "flc_unpack_reduce_bits",
+}
+
+
 def _gpu_device(x):
     _lib.require_gpu()
     if x.is_cuda:
@@ -436,23 +445,41 @@ class Compressor:
             return prm
         return self.codec_params(torch.device("cpu"))[0]
 
-    def payloadBytes(self, d=None):
-        """Bytes of one row's payload (flc_payload_bytes: 16-B header + body, 16-B padded)."""
-        return int(_lib.load().flc_payload_bytes(ctypes.byref(self._host_params()), self._dim(d)))
+    def _wire_entry(self, name, bits, prm=None):
+        """The C entry ``name`` of the byte formats or, with ``bits``, its bit-packed counterpart
+        (FMT_LBITS / FMT_NAT9, include/flcodec.h "Bit-packed messages").  A codec without a bit-packed
+        form is refused here, before any size is computed or anything is launched."""
+        lib = _lib.load()
+        if not bits:
+            return getattr(lib, name)
+        if not hasattr(lib, "flc_pack_bits"):
+            raise NotImplementedError("this library build has no flc_pack_bits")
+        prm = prm if prm is not None else self._host_params()
+        if lib.flc_payload_bits_format(ctypes.byref(prm)) == 0:
+            raise NotImplementedError(f"{name}: this codec has no bit-packed wire form "
+                                      "(natural, or standard dithering / qsgd / terngrad with s <= 63)")
+        return getattr(lib, _BITS_ENTRY[name])
 
-    def validatePayload(self, payload, d=None):
+    def payloadBytes(self, d=None, bits=False):
+        """Bytes of one row's payload (flc_payload_bytes: 16-B header + body, 16-B padded; ``bits``:
+        flc_payload_bits_bytes, 16 + 256 b ceil(d / 2048))."""
+        prm = self._host_params()
+        return int(self._wire_entry("flc_payload_bytes", bits, prm)(ctypes.byref(prm), self._dim(d)))
+
+    def validatePayload(self, payload, d=None, bits=False):
         """Check a message received from a peer before it is decoded (flc_payload_validate, host
         only): its size, header and codes fit this codec and d.  ``payload``: bytes-like, a uint8
-        numpy array or a host uint8 tensor.  Raises ValueError with the reason."""
+        numpy array or a host uint8 tensor.  ``bits``: the bit-packed message
+        (flc_payload_validate_bits).  Raises ValueError with the reason."""
         if torch.is_tensor(payload):
             if payload.dtype != torch.uint8 or payload.is_cuda:
                 raise TypeError("validatePayload: a host uint8 tensor (or bytes) is expected")
             arr = payload.contiguous().numpy()
         else:
             arr = np.frombuffer(payload, dtype=np.uint8)
-        lib = _lib.load()
-        rc = lib.flc_payload_validate(ctypes.byref(self._host_params()), ctypes.c_void_p(arr.ctypes.data),
-                                      int(arr.nbytes), self._dim(d))
+        prm = self._host_params()
+        rc = self._wire_entry("flc_payload_validate", bits, prm)(ctypes.byref(prm), ctypes.c_void_p(arr.ctypes.data),
+                                                               int(arr.nbytes), self._dim(d))
         _lib.check(rc, "validatePayload")
 
     def _dim(self, d):
@@ -462,10 +489,11 @@ class Compressor:
             raise ValueError("this compressor has no D (identity): pass d")
         return int(d)
 
-    def compressPayload(self, x, out=None):
+    def compressPayload(self, x, out=None, bits=False):
         """The message this client would send: flc_pack of compressVector(x) (same pattern, same
-        draws), as a uint8 device tensor of payloadBytes() bytes.  Statistics advance like
-        compressVector."""
+        draws), as a uint8 device tensor of payloadBytes() bytes.  ``bits``: the bit-packed message
+        (flc_pack_bits, payloadBytes(bits=True) bytes), the same codes at sub-byte width.  Statistics
+        advance like compressVector."""
         if x.dtype != torch.float32:
             raise TypeError(f"flcodec encodes fp32 only (got {x.dtype})")
         dev = _gpu_device(x)
@@ -473,31 +501,34 @@ class Compressor:
         d = xd.numel()
         lib = _lib.load()
         prm, keep = self.codec_params(dev)
+        pack = self._wire_entry("flc_pack", bits, prm)
         pat = self._pattern(dev, keep)
-        nbytes = int(lib.flc_payload_bytes(ctypes.byref(prm), d))
+        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm)(ctypes.byref(prm), d))
         if out is None:
             out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         elif out.numel() < nbytes or out.dtype != torch.uint8 or out.data_ptr() % 16:
             raise ValueError("compressPayload: out must be a 16-byte aligned uint8 tensor of payloadBytes()")
-        ws_bytes = lib.flc_pack_workspace_size(ctypes.byref(prm), d)
+        ws_bytes = self._wire_entry("flc_pack_workspace_size", bits, prm)(ctypes.byref(prm), d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):
-            rc = lib.flc_pack(ctypes.byref(prm), ctypes.byref(pat), ctypes.c_void_p(xd.data_ptr()), d,
-                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                              _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_pack")
+            rc = pack(ctypes.byref(prm), ctypes.byref(pat), ctypes.c_void_p(xd.data_ptr()), d,
+                      ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                      _lib.stream_ptr(dev))
+        _lib.check(rc, "flc_pack_bits" if bits else "flc_pack")
         self._account(d)
         return out
 
-    def decompressPayload(self, payload, d=None):
-        """Dense fp32 row of a payload (flc_unpack): compressVector's output, bit for bit."""
+    def decompressPayload(self, payload, d=None, bits=False):
+        """Dense fp32 row of a payload (flc_unpack; ``bits``: flc_unpack_bits of a bit-packed one):
+        compressVector's output, bit for bit."""
         dev = _gpu_device(payload)
         d = self._dim(d)
         lib = _lib.load()
         prm, keep = self.codec_params(dev)
         if payload.dtype != torch.uint8:
             raise TypeError(f"decompressPayload: payload must be uint8 (got {payload.dtype})")
-        nbytes = int(lib.flc_payload_bytes(ctypes.byref(prm), d))
+        unpack = self._wire_entry("flc_unpack", bits, prm)
+        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm)(ctypes.byref(prm), d))
         if payload.numel() < nbytes:
             raise ValueError(f"decompressPayload: {payload.numel()} bytes, the payload of d={d} is {nbytes}")
         # a host message (off the network) crosses to the device first; the kernel reads HBM only
@@ -506,9 +537,9 @@ class Compressor:
             payload = payload.clone()
         out = torch.empty(d, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = lib.flc_unpack(ctypes.byref(prm), ctypes.c_void_p(payload.data_ptr()), d,
-                                ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_unpack")
+            rc = unpack(ctypes.byref(prm), ctypes.c_void_p(payload.data_ptr()), d,
+                        ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(dev))
+        _lib.check(rc, "flc_unpack_bits" if bits else "flc_unpack")
         return out
 
     # -- shift codecs ----------------------------------------------------

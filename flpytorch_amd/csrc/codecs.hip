@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "codec_ops.hpp"
+#include "wire_bits.hpp"
 #include "wire_codes.hpp"
 
 namespace flc {
@@ -1374,6 +1375,10 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
         if (sr) return launch_shift_accum(*sr, n, d, op, levels, s, w, wt, out, st, map);
         if (sh && ca) return launch_shift_code(src.base, d, op, levels, s, *sh, *ca, st);
         if (sh) return launch_shift(src.base, d, op, levels, s, *sh, st);
+        if (ca && ca->bits) {                        // flc_pack_bits: the bit-packed form (wire_bits.hip)
+            if constexpr (BitsOp<decltype(op)>::value) return launch_code_bits(src.base, d, op, levels, s, *ca, st);
+            else { set_error("ew_run: codec %d has no bit-packed form", codec); return FLC_ERR_UNSUPPORTED; }
+        }
         if (ca) return launch_code(src.base, d, op, levels, s, *ca, st);
         if (dense) return launch_dense(src.base, d, op, levels, s, out, st);
         return launch_accum(src, vec, n, d, op, levels, s, w, wt, out, st);

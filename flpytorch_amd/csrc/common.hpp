@@ -167,6 +167,7 @@ struct CodeArgs {
     const float* lv;     // the level table (dithering)
     int s;
     const float* pn;     // device norm the codes are relative to (dithering)
+    int bits = 0;        // > 0: the bit-packed form of that many bits per code (wire_bits.hip); fmt unused
 };
 int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool vec, int64_t n, int64_t d,
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt, void* ws,
@@ -252,6 +253,18 @@ int pack_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const fl
 size_t unpack_shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 int unpack_shift_reduce_run(const flc_codec_params* prm, const flc_payload_rows& pr, int64_t n, int64_t d,
                             const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+// the bit-packed forms of the dense level / natural messages (wire_bits.hip): flc_pack_bits & co.
+// bits_width: bits per code of the codec's bit-packed form, 0 when it has none
+int bits_width(const flc_codec_params* prm);
+int bits_format(const flc_codec_params* prm);
+int64_t bits_payload_bytes(const flc_codec_params* prm, int64_t d);
+int bits_payload_validate(const flc_codec_params* prm, const uint8_t* p, int64_t nbytes, int64_t d);
+size_t bits_pack_workspace(const flc_codec_params* prm, int64_t d);
+int bits_pack_run(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, char* payload, void* ws,
+                  size_t ws_bytes, hipStream_t st);
+int bits_unpack_run(const flc_codec_params* prm, const char* payload, int64_t d, float* out, hipStream_t st);
+int bits_unpack_reduce_run(const flc_codec_params* prm, const char* base, int64_t ld, const char* const* ptrs, int64_t n,
+                           int64_t d, const float* w, float wt, float* out, hipStream_t st);
 // Row g's boundary of G row groups whose last group is `lastpct` % of the others' size (the last
 // group's tail is the exposed one): rows [group_row(n, G, g), group_row(n, G, g + 1)).
 // lastpct is clamped to [1, 100]: 0 or less would leave the last group (the one whose fold writes

@@ -1,11 +1,15 @@
 // Wire-format constants and the per-element codes (wire.hip's layout; include/flcodec.h), shared by
 // the pack / decode kernels of wire.hip and the fused encode -> code kernel of codecs.hip.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "common.hpp"
 
 namespace flc {
 
-enum { FMT_F32 = 1, FMT_Q8 = 2, FMT_Q16 = 3, FMT_NAT16 = 4, FMT_SPARSE = 5, FMT_RANKK = 6 };
+enum { FMT_F32 = 1, FMT_Q8 = 2, FMT_Q16 = 3, FMT_NAT16 = 4, FMT_SPARSE = 5, FMT_RANKK = 6,
+       FMT_LBITS = 7, FMT_NAT9 = 8 };      // the bit-packed forms (wire_bits.hip)
 struct PayloadHeader {
     uint32_t fmt, count;
     float norm;
@@ -97,6 +101,56 @@ __device__ inline void dec16(uint4 v, const float* lv, int s, float norm, float*
         else c = (w[q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
         e[q] = dec1<FMT>(c, lv, s, norm);
     }
+}
+
+// ---- bit-packed tiles (wire_bits.hip; FMT_LBITS / FMT_NAT9) ------------------------------------
+// A tile is 2048 consecutive elements; lane l of the owning wave holds the 32 codes of elements
+// 256 t + 4 l + q (code number i = 4 t + q), concatenated LSB-first into B words: code i at bits
+// [i B, (i + 1) B).  Word k of lane l is the tile's word k * 64 + l.  Every index below is a
+// constant after instantiation, so the words stay in registers.
+constexpr int BT_TILE = 2048;
+
+// codes 4 T .. 4 T + 3 of a lane (grp: 4 B bits, code q at bit q B) into its words
+template <int B, int T>
+__device__ inline void bt_put(uint32_t (&w)[B], uint64_t grp) {
+    constexpr int P = 4 * B * T, k = P >> 5, sh = P & 31;
+    static_assert(sh + 4 * B <= 64, "a group spans at most two words");
+    w[k] |= (uint32_t)(grp << sh);
+    if constexpr (sh + 4 * B > 32) w[k + 1] |= (uint32_t)(grp >> (32 - sh));
+}
+
+template <int B, int I>
+__device__ inline uint32_t bt_get(const uint32_t (&w)[B]) {
+    constexpr int P = B * I, k = P >> 5, sh = P & 31;
+    uint32_t c = w[k] >> sh;
+    if constexpr (sh + B > 32) c |= w[k + 1] << (32 - sh);
+    return c & ((1u << B) - 1u);
+}
+
+template <class F, int... I>
+__device__ inline void bt_each(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+
+// A lane's 32 values from its B words.  NAT9: the code is the value's top nine bits.  Level codes:
+// `lv` is |levels[min(lane, s)]|, so an element's magnitude is lane idx's register (one cross-lane
+// read, no LDS table, no barrier) and an index past s reads the top level; then the sign and the
+// norm exactly as lev_decode: (levels[idx] * sign) * norm, code 0 the exact +0.  Every lane of the
+// wave must be active.
+template <int B>
+__device__ inline void bt_decode(const uint32_t (&w)[B], float lv, float norm, float* e) {
+    bt_each([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        const uint32_t c = bt_get<B, I>(w);
+        if constexpr (B == 9) {
+            e[I] = __uint_as_float(c << 23);
+        } else {
+            const uint32_t idx = c & ((1u << (B - 1)) - 1u);
+            const uint32_t mag = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << 2), (int)__float_as_uint(lv));
+            const float v = __uint_as_float(mag | ((c >> (B - 1)) << 31)) * norm;
+            e[I] = c == 0u ? 0.f : v;
+        }
+    }, std::make_integer_sequence<int, 32>{});
 }
 
 }  // namespace flc

@@ -256,7 +256,7 @@ class Simulation:
                  local_lr, global_lr, local_iters=1, runtime_seed=0, device="cuda", sampling="uniform",
                  poisson_p=None, init_compressor=None, server_gradient=None, record_iterates=False, wire=False,
                  initialize_shifts_policy="zero", diana_step=None, ef21_step=None, marina_step=None, shift_wire=False,
-                 cofig_step=None, frecon_step=None, algorithm_options=None, resident=False):
+                 cofig_step=None, frecon_step=None, algorithm_options=None, resident=False, wire_bits=False):
         algorithm = algorithm.lower()
         if algorithm not in ALGORITHMS:
             raise ValueError(f"harness drives {', '.join(ALGORITHMS)}, not {algorithm!r}")  # algorithms.py:1954 style
@@ -295,6 +295,17 @@ class Simulation:
         if wire not in (False, True, "socket"):
             raise ValueError(f"wire must be False, True or 'socket' (got {wire!r})")
         self.wire = wire
+        # wire_bits=True (with wire): the messages go in the bit-packed form (compressPayload(bits=True):
+        # natural at 9 bits, qsgd / terngrad with s <= 63 at 1 + bit_length(s)), validated with the
+        # bit-packed check on receipt; same iterates and history, fewer payload_bytes
+        if wire_bits and not wire:
+            raise ValueError("wire_bits goes with wire=True or wire='socket'")
+        self.wire_bits = bool(wire_bits)
+        if self.wire_bits:
+            try:
+                ag.initCompressor(self.spec, self.D).payloadBytes(self.D, bits=True)
+            except NotImplementedError as e:
+                raise ValueError(f"wire_bits: {self.spec!r} has no bit-packed wire form") from e
         # shift_wire=True (DIANA / EF21 / MARINA): every compressed client step ships its message
         # C(a - b) as the wire payload, written by the pass that updates the client's state
         # (Compressor.compressShiftPayload, flc_pack_shift), and the server side rebuilds the vector
@@ -400,11 +411,11 @@ class Simulation:
             return g
         if self.algorithm == "dcgd":                                             # algorithms.py:1741-1745
             if self.wire:
-                msg = comp.compressPayload(g)
+                msg = comp.compressPayload(g, bits=self.wire_bits)
                 cs["stats"]["payload_bytes"] = cs["stats"].get("payload_bytes", 0) + msg.numel()
                 if self.link is not None:
                     msg = self.transfer(comp, msg, g.numel())
-                c = comp.decompressPayload(msg, g.numel())
+                c = comp.decompressPayload(msg, g.numel(), bits=self.wire_bits)
             else:
                 c = comp.compressVector(g)
             cs["stats"]["send_scalars_to_master"] += comp.last_need_to_send_advance
@@ -499,7 +510,7 @@ class Simulation:
         t = threading.Thread(target=send, daemon=True)
         t.start()
         try:
-            got = server.recvPayload(comp, d)
+            got = server.recvPayload(comp, d, bits=self.wire_bits)
         except BaseException:
             # a refused or broken message: unblock the sender (it may sit in sendall on a full
             # socket buffer) before waiting for it

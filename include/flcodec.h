@@ -602,6 +602,54 @@ int flc_unpack_reduce(const flc_codec_params* prm, const void* d_payloads, int64
                       float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Bit-packed messages (additive to ABI 1.04: detect by symbol): the dense level and natural
+ * messages at sub-byte width, beside the byte formats above (which keep every byte).
+ *   7 LBITS  std dithering / qsgd / terngrad, s <= 63      b = 1 + bit_length(s) bits per code (2..7):
+ *                                                          sign << (b - 1) | level index, i.e. Q8's
+ *                                                          code with the sign bit moved; the header's
+ *                                                          format word is 7 | (b << 8)
+ *   8 NAT9   natural                                       9 bits: the top nine bits of the fp32 value
+ *                                                          +-2^k (decode: code << 23) — exact for +-0,
+ *                                                          +-inf and every normal power of two
+ * b is the reference's count 1 + ceil(log2 s) (compressors.py:367-368) except when s is a power of
+ * two, where it is one bit more: s + 1 levels cannot be addressed in ceil(log2 s) bits.  NAT9 is the
+ * reference's 9 bits (compressors.py:268).
+ * Header: the 16 bytes above {format word, count = d, norm, bad}.  Body: tiles of 2048 consecutive
+ * elements, the last one padded with code 0; flc_payload_bits_bytes = 16 + 256 b ceil(d / 2048)
+ * (d == 0: the header alone).  Inside a tile, element e = 256 t + 4 l + q (t < 8, l < 64, q < 4) is
+ * lane l's code number i = 4 t + q; a lane's 32 codes are concatenated LSB-first into b 32-bit words
+ * (code i at bits [i b, (i + 1) b)), and word k of lane l is at body offset
+ * tile * 256 b + (k * 64 + l) * 4.
+ * Level codes keep the byte formats' value rule: code 0 is +0, sign with index 0 is -0 * norm, an
+ * index above s (a malformed message) decodes to the top level.  NAT9 cannot carry a subnormal
+ * power of two or a NaN: flc_pack_bits writes the value's top nine bits, counts the element in the
+ * header's bad field, and flc_payload_validate_bits refuses the message (bad != 0).
+ *
+ * flc_pack_bits writes, byte for byte, this layout of the codes flc_pack gives for the same x, prm
+ * and pat (one pass after the norm pass; no byte-format message is formed on the way);
+ * flc_unpack_bits(flc_pack_bits(x)) == flc_unpack(flc_pack(x)) and flc_unpack_reduce_bits(payloads)
+ * == flc_unpack_reduce(the byte payloads of the same rows), bit for bit.  Arguments as the byte
+ * entries': 16-byte aligned payloads, strided rows (ld_bytes >= flc_payload_bits_bytes, a multiple
+ * of 16) or a device pointer array, n == 0 zero-fills d_out, a refused call writes nothing.
+ * Every other codec (s > 63, randk / topk, rank_k, ident, lazy, natural dithering) has no
+ * bit-packed form: flc_payload_bits_format / _bytes and the workspace query return 0 and the other
+ * entries FLC_ERR_UNSUPPORTED before any launch.  flc_payload_validate_bits is host only: size,
+ * header format and b, count, bad == 0, every level index <= s.
+ * -------------------------------------------------------------------------------------- */
+int flc_payload_bits_format(const flc_codec_params* prm);
+int64_t flc_payload_bits_bytes(const flc_codec_params* prm, int64_t d);
+int flc_payload_validate_bits(const flc_codec_params* prm, const void* h_payload, int64_t nbytes, int64_t d);
+size_t flc_pack_bits_workspace_size(const flc_codec_params* prm, int64_t d);
+int flc_pack_bits(const flc_codec_params* prm, const flc_pattern* pat, const float* d_x, int64_t d,
+                  void* d_payload, void* d_ws, size_t ws_bytes, void* stream);
+int flc_unpack_bits(const flc_codec_params* prm, const void* d_payload, int64_t d, float* d_out,
+                    void* stream);
+size_t flc_unpack_reduce_bits_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_unpack_reduce_bits(const flc_codec_params* prm, const void* d_payloads, int64_t ld_bytes,
+                           const void* const* d_payload_ptrs, int64_t n, int64_t d, const float* d_w,
+                           float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * Shifted steps on the wire (additive to ABI 1.04: detect by symbol): the shift codecs' client
  * step e = C(a - b) that EMITS its message, and the server fold of n such messages with the
  * shifted round's semantics.
