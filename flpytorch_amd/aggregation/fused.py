@@ -796,22 +796,39 @@ class ShiftPayloadReducer:
     ``Compressor.compressShiftPayload`` it leaves the ``out`` and the ``msg_out`` rows of
     ``ShiftUplinkReducer`` (flc_encode_shift_reduce) over the rows they were packed from, bit for
     bit.  Dense formats run one tile-owner pass (k_unpack_shift_accum); RandK / TopK payloads go row
-    by row through a dense workspace row (the dense round's bits, not a fast path).  Rank-K raises
-    ``NotImplementedError``."""
+    by row through a dense workspace row (the dense round's bits).  Rank-K raises
+    ``NotImplementedError``.
+
+    ``sparse=True`` (RandK / TopK payloads): the one-pass fold flc_unpack_shift_reduce_sparse — a tile
+    table of the payloads' index lists (k_sparse_tile_tab), then one tile-owner pass over all N
+    messages (k_sparse_shift_accum), for the EF21 mirror in place (``msg_out is base``: only the
+    listed elements of a mirror row are written, an unlisted one keeps its stored bits — a stored -0
+    stays -0, where the general entry stores +0), MARINA's shared [D] base and the plain fold.  The
+    mirror rows and ``out`` are those of ``ShiftUplinkReducer(..., sparse=True / batched=True)`` over
+    the rows the payloads were packed from, bit for bit.  ``clients=ids`` (with ``sparse=True``): the
+    mirror is an [N_total, D] state matrix and payload i updates row ``ids[i]``; rows not named are
+    neither read nor written.  Any other codec, operand shape or a scale that is not finite and > 0
+    raises ``NotImplementedError`` with the library's reason: there is no silent fallback."""
 
     def __init__(self, compressor: Compressor, device=None):
         _lib.require_gpu()
         self.comp = compressor
         self.device = _device(device)
 
-    def __call__(self, payloads, d=None, *, scale=1.0, base=None, msg_out=None, out=None, weights=None, divisor=None):
+    def __call__(self, payloads, d=None, *, scale=1.0, base=None, msg_out=None, out=None, weights=None, divisor=None,
+                 sparse=False, clients=None):
         """payloads: [N, ld] uint8 device tensor (rows 16-byte aligned, ld % 16 == 0) or a list of N
         16-byte aligned uint8 device tensors.  ``base``: None, [N, D], or ONE [D] vector for every row
         (MARINA's g_prev).  ``msg_out``: None or [N, D]; it may be ``base`` (EF21's server mirror in
-        place).  ``weights`` / ``divisor`` as in ``PayloadReducer``.  Returns ``out``."""
+        place).  ``weights`` / ``divisor`` as in ``PayloadReducer``.  ``sparse`` / ``clients``: the
+        one-pass fold of RandK / TopK payloads (the class docstring); with ``clients`` a per-row
+        ``base`` / ``msg_out`` is [N_total, D].  Returns ``out``."""
         lib = _lib.load()
-        if not hasattr(lib, "flc_unpack_shift_reduce"):
-            raise NotImplementedError("this library build has no flc_unpack_shift_reduce")
+        entry = "flc_unpack_shift_reduce_sparse" if sparse else "flc_unpack_shift_reduce"
+        if not hasattr(lib, entry):
+            raise NotImplementedError(f"this library build has no {entry}")
+        if clients is not None and not sparse:
+            raise ValueError("ShiftPayloadReducer: clients=... is taken by the sparse fold only (sparse=True)")
         dev = self.device
         d = self.comp._dim(d)
         prm, keep = self.comp.codec_params(dev)
@@ -835,11 +852,18 @@ class ShiftPayloadReducer:
             if n:
                 pr.d_payload_ptrs = _pointer_table(payloads, dev, keep)
         who = "ShiftPayloadReducer"
+        ids, n_rows = None, n
+        if clients is not None:
+            ids = _client_ids(who, clients, n)
+            state = [v for v in (base, msg_out) if v is not None and v.dim() == 2]
+            n_rows = int(state[0].shape[0]) if state else (max(ids) + 1 if ids else 1)
+            if ids and max(ids) >= n_rows:
+                raise ValueError(f"{who}: client id {max(ids)} outside the [{n_rows}, {d}] state matrix")
 
         def rows(name, v):
             if not _is_fp32_device(v):
                 raise TypeError(f"{who}: {name} must be an fp32 device tensor")
-            return _row_matrix(who, name, v, n, d)
+            return _row_matrix(who, name, v, n_rows, d)
         if base is not None:
             if base.dim() == 1 and not _is_fp32_device(base):
                 raise TypeError(f"{who}: base must be an fp32 device tensor")
@@ -852,11 +876,24 @@ class ShiftPayloadReducer:
         elif out.dtype != torch.float32 or not out.is_cuda or out.numel() != d or not out.is_contiguous():
             raise ValueError(f"ShiftPayloadReducer: out must be a contiguous fp32 device [{d}] vector")
         w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
-        ws_bytes = lib.flc_unpack_shift_reduce_workspace_size(ctypes.byref(prm), n, d)
+        ws_bytes = getattr(lib, entry + "_workspace_size")(ctypes.byref(prm), n, d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
+        args = [ctypes.byref(prm), ctypes.byref(pr)]
+        if sparse:
+            rmap = None
+            if ids is not None:
+                h_ids = np.asarray(ids, dtype=np.int32)
+                d_ids = torch.from_numpy(h_ids).to(dev)
+                keep += [h_ids, d_ids]
+                rmap = _lib.FlcRowMap()
+                rmap.h_ids, rmap.d_ids, rmap.n_total = h_ids.ctypes.data, d_ids.data_ptr(), n_rows
+                rmap.indexed = _lib.FLC_IDX_BASE | _lib.FLC_IDX_MSG       # (a shared [D] base is never indexed)
+                if base is not None and base.dim() == 1:
+                    rmap.indexed = _lib.FLC_IDX_MSG
+            args.append(ctypes.byref(rmap) if rmap is not None else None)
         with torch.cuda.device(dev):
-            rc = lib.flc_unpack_shift_reduce(ctypes.byref(prm), ctypes.byref(pr), n, d, ctypes.c_void_p(w_ptr),
-                                             ctypes.c_float(total), ctypes.c_void_p(out.data_ptr()),
-                                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_unpack_shift_reduce")
+            rc = getattr(lib, entry)(*args, n, d, ctypes.c_void_p(w_ptr), ctypes.c_float(total),
+                                     ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                     _lib.stream_ptr(dev))
+        _lib.check(rc, entry)                                   # (a refusal: NotImplementedError with the reason)
         return out

@@ -786,6 +786,61 @@ extern "C" int flc_unpack_shift_reduce(const flc_codec_params* prm, const flc_pa
     return unpack_shift_reduce_run(prm, pr, n, d, d_w, w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- the sparse shifted-wire fold (wire_shift_sparse.hip) ------------------------------------------
+extern "C" size_t flc_unpack_shift_reduce_sparse_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (!prm || !is_sel(prm->codec) || n < 0 || d < 0) return 0;
+    return unpack_shift_sparse_workspace(n, d);
+}
+
+extern "C" int flc_unpack_shift_reduce_sparse(const flc_codec_params* prm, const flc_payload_rows* rows, const flc_row_map* map,
+                                              int64_t n, int64_t d, const float* d_w, float w_total, float* d_out, void* d_ws,
+                                              size_t ws_bytes, void* stream) {
+    const char* me = "flc_unpack_shift_reduce_sparse";
+    if (!prm || !is_sel(prm->codec)) {
+        set_error("%s: only RandK / TopK payloads (the SPARSE format) have a one-pass fold (use flc_unpack_shift_reduce)", me);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) return too_many(me, n, "payloads", FLC_ERR_ARG);
+    if (d == 0) return FLC_OK;
+    if (d >= (int64_t)0xFFFFFFFF) { set_error("%s: D too large for 32-bit entry indices", me); return FLC_ERR_ARG; }
+    if (!d_out) { set_error("%s: need out", me); return FLC_ERR_ARG; }
+    flc_payload_rows pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.msg_scale = 1.f;
+    flc_row_map m;
+    int shape = SHAPE_D;
+    if (n > 0) {
+        if (!rows || (!rows->d_payloads && !rows->d_payload_ptrs)) { set_error("%s: no payloads", me); return FLC_ERR_ARG; }
+        pr = *rows;
+        if (pr.d_payloads) {
+            pr.d_payload_ptrs = nullptr;
+            if ((uintptr_t)pr.d_payloads & 15u) { set_error("%s: payload rows must be 16-byte aligned", me); return FLC_ERR_ARG; }
+            if (pr.ld_bytes < payload_bytes(prm, d) || (pr.ld_bytes & 15)) {
+                set_error("%s: ld_bytes=%lld, at least the payload's %lld bytes and a multiple of 16", me,
+                          (long long)pr.ld_bytes, (long long)payload_bytes(prm, d));
+                return FLC_ERR_ARG;
+            }
+        }
+        if (!pr.d_base) pr.ldbase = 0;
+        if (!pr.d_msg) pr.ldmsg = 0;
+        shape = unpack_shift_sparse_shape(pr, me);
+        if (shape < 0) return FLC_ERR_UNSUPPORTED;
+        flc_shift_rows sr;                              // the operands a row map can address
+        memset(&sr, 0, sizeof(sr));
+        sr.d_base = pr.d_base; sr.ldbase = pr.ldbase;
+        sr.d_msg = pr.d_msg; sr.ldmsg = pr.ldmsg;
+        if (map) {
+            if (int rc = row_map_check(me, map, sr, n, d, &m)) return rc;
+            if (int rc = sampled_outputs_overlap(me, sr, m, n, d)) return rc;
+        } else if (int rc = outputs_overlap(me, {{"d_msg", "ldmsg", pr.d_msg, pr.ldmsg}}, pr.d_base, pr.ldbase, n, d)) {
+            return rc;
+        }
+    }
+    return unpack_shift_sparse_run(prm, pr, shape, (map && n > 0) ? &m : nullptr, n, d, d_w, w_total, d_out, d_ws, ws_bytes,
+                                   (hipStream_t)stream);
+}
+
 namespace flc {
 // the torch-order mode restates p = 2 of the dithering codecs; p = inf: a maximum, exact in any order
 static bool dithering(int codec) { return codec == FLC_STD_DITHERING || codec == FLC_NAT_DITHERING; }

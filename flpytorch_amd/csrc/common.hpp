@@ -253,6 +253,14 @@ int pack_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const fl
 size_t unpack_shift_reduce_workspace(const flc_codec_params* prm, int64_t n, int64_t d);
 int unpack_shift_reduce_run(const flc_codec_params* prm, const flc_payload_rows& pr, int64_t n, int64_t d,
                             const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+// the sparse shifted-wire fold (wire_shift_sparse.hip, flc_unpack_shift_reduce_sparse): n SPARSE
+// payloads in one tile-owner pass; shape: SHAPE_B / C / D from unpack_shift_sparse_shape (-1: refused,
+// the reason set under `me`), map: the checked row map of shape B's mirror rows or null
+size_t unpack_shift_sparse_workspace(int64_t n, int64_t d);
+int unpack_shift_sparse_shape(const flc_payload_rows& pr, const char* me);
+int unpack_shift_sparse_run(const flc_codec_params* prm, const flc_payload_rows& pr, int shape, const flc_row_map* map,
+                            int64_t n, int64_t d, const float* w, float wt, float* out, void* ws, size_t ws_bytes,
+                            hipStream_t st);
 // the bit-packed forms of the dense level / natural messages (wire_bits.hip): flc_pack_bits & co.
 // bits_width: bits per code of the codec's bit-packed form, 0 when it has none
 int bits_width(const flc_codec_params* prm);

@@ -12,7 +12,8 @@
 // (wire.hip k_pack_*), then the epilogue over the stored e — a constant number of launches.
 // Server, dense formats: one tile-owner pass (k_unpack_shift_accum below).  Server, SPARSE: row by
 // row through a dense workspace row (k_unpack_sparse_row, k_shift_epi, k_shift_fold), so the bits are
-// the dense shifted round's.
+// the dense shifted round's.  The one-pass fold of SPARSE messages in the in-place, shared-base and
+// plain shapes is an entry of its own: flc_unpack_shift_reduce_sparse (wire_shift_sparse.hip).
 #include "wire_codes.hpp"
 
 namespace flc {

@@ -675,7 +675,8 @@ int flc_unpack_reduce_bits(const flc_codec_params* prm, const void* d_payloads, 
  * place); ldbase == 0 is ONE shared [d] base (MARINA's g_prev).  Without base and d_msg and with
  * msg_scale == 1 it is flc_unpack_reduce's fold.  Dense formats: one tile-owner pass
  * (k_unpack_shift_accum; an in-place EF21 mirror with Q8 moves (1 + 4 + 4) n d + 4 d bytes); SPARSE:
- * row by row through a dense workspace row, so the bits are the dense shifted round's.
+ * row by row through a dense workspace row, so the bits are the dense shifted round's (the one-pass
+ * fold of SPARSE messages is flc_unpack_shift_reduce_sparse, below).
  *
  * The identity: for any flc_shift_rows round in which nothing is written through a shift operand,
  * flc_pack_shift of each row into payload i followed by flc_unpack_shift_reduce over the n payloads
@@ -709,6 +710,62 @@ size_t flc_unpack_shift_reduce_workspace_size(const flc_codec_params* prm, int64
 int flc_unpack_shift_reduce(const flc_codec_params* prm, const flc_payload_rows* rows,
                             int64_t n, int64_t d, const float* d_w, float w_total,
                             float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * Sparse shifted-wire fold (additive: flc_version() stays 104, detect the entry by its symbol):
+ * flc_unpack_shift_reduce's server step for n SPARSE messages (RandK / TopK payloads) in one pass.
+ * The general entry takes such payloads row by row through a dense [d] workspace row: four launches
+ * and about 28 d bytes of traffic per client for a message of 8 K bytes.  This entry cuts every
+ * payload's index list at the boundaries of 4096-element tiles (k_sparse_tile_tab) and folds each
+ * tile for all n rows in one workgroup (k_sparse_shift_accum): a mirror row is read once and
+ * written at the listed elements only, 4 n d + 12 n K + 4 d bytes for the EF21 mirror in place.
+ *
+ * Payload i is a SPARSE message as flc_pack / flc_pack_shift write it: header, u32 idx[cap],
+ * f32 val[cap], cap = max(1, min(K, d)), ascending indices, `count` entries used.  The count is cut
+ * at cap and an index >= d is never stored to, as in flc_unpack.  For an entry (j, v) of payload i,
+ * each operation rounded separately:
+ *     t = v * msg_scale;  m = base ? base_i[j] + t : t
+ * d_out is folded in row order, the first term assigned, d_w == NULL meaning no multiply, one
+ * division by w_total at the end.
+ *
+ * Accepted shapes: B, C and D of flc_randk_shift_reduce's shape table, with "row i's index set" read
+ * as "the indices listed in payload i", recognised by pointer and leading dimension:
+ *   B  EF21's server mirror in place: d_base == d_msg with equal leading dimensions.  Only the listed
+ *      elements of mirror row i are written; an unlisted element is not written and contributes its
+ *      stored bits to the fold, as the dense fold of the updated rows does in the sibling's shape B.
+ *   C  MARINA: ONE shared [d] base (ldbase == 0), no d_msg.  A row that does not list column j
+ *      contributes exactly w_i * (base[j] + 0.0f * msg_scale) (evaluated, not skipped).
+ *   D  the plain fold: no base, no d_msg.  An unlisted element contributes 0.0f * msg_scale.
+ * Under THE CONTRACT stated at flc_randk_shift_reduce:
+ *   - shapes C and D are bit-identical to flc_unpack_shift_reduce without condition;
+ *   - shape B is bit-identical to it whenever the mirror holds no -0 at an unlisted place; otherwise
+ *     the two differ only in that zero's sign;
+ *   - shape B is bit-identical to flc_topk_shift_reduce / flc_randk_shift_reduce in shape B over the
+ *     rows the payloads were packed from, the mirror rows and d_out, with no condition on the
+ *     unselected places: neither writes them.  (A message
+ *     does not list an element whose difference is +0 even where the round selected it; the round
+ *     stores base + 0 there, which changes a bit only if the mirror holds -0 at that place.)
+ *
+ * map (NULL: contiguous rows): mirror row i is row ids[i] of an [n_total, d] matrix.  Only
+ * FLC_IDX_BASE | FLC_IDX_MSG are meaningful, in shape B both set or both clear; the id is wave-uniform
+ * and read through the scalar cache; rows not named in ids are neither read nor written; payloads and
+ * d_w stay in participant order.  Checked as in the _sampled entries: null h_ids / d_ids, the id
+ * range, duplicate ids with an indexed output, FLC_IDX_BASE with a shared base.
+ *
+ * Everything is checked before any launch; a refused call writes nothing.  FLC_ERR_UNSUPPORTED (the
+ * caller then uses flc_unpack_shift_reduce): a codec whose payload format is not SPARSE (the size
+ * query then returns 0); any other operand shape (a separate dense d_msg matrix, a per-row base
+ * without d_msg == d_base); msg_scale not finite and > 0.  FLC_ERR_ARG: null payloads or out with
+ * work to do, misaligned payloads, ld_bytes < flc_payload_bytes or ld_bytes % 16 != 0,
+ * n > FLC_MAX_ROWS, negative n or d, d >= 0xFFFFFFFF, mirror rows that overlap.  FLC_ERR_WORKSPACE:
+ * ws_bytes below the size query.  d == 0: FLC_OK, the device is not touched; n == 0 with d > 0
+ * zero-fills d_out.  Workspace: the tile table, 8 n ceil(d / 4096) bytes; no [d]-sized row.
+ * -------------------------------------------------------------------------------------- */
+size_t flc_unpack_shift_reduce_sparse_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_unpack_shift_reduce_sparse(const flc_codec_params* prm, const flc_payload_rows* rows,
+                                   const flc_row_map* map /* NULL: contiguous rows */,
+                                   int64_t n, int64_t d, const float* d_w, float w_total,
+                                   float* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
  * Multi-GPU combine on a caller-owned RCCL communicator (rccl_comm: an ncclComm_t, passed as

@@ -62,6 +62,15 @@ and the folds are compared (bytes / int32).  Byte models: client 21 d (QSGD; nat
 2-byte codes) against 41 d (30 d); server (c + 8) N d + 4 d against (c + 28) N d with c code bytes per
 element.  Writes <out-dir>/<spec>_client.jsonl and <spec>_server.jsonl (default profiles/r13/shift_wire).
 
+--wire --sparse (RandK / TopK specs, default topk:1%,randk:1%; device draws): the server fold of N SPARSE
+payloads, packed once outside the clock, in the EF21 mirror in place and with MARINA's one shared base,
+  sparse   ShiftPayloadReducer(P, ..., sparse=True)                          flc_unpack_shift_reduce_sparse
+  general  ShiftPayloadReducer(P, ...) on its own copy of the mirror         flc_unpack_shift_reduce
+interleaved in one process on one allocation; after every repeat the two outputs and the two mirrors are
+compared as int32.  Byte models: sparse 4 N D + 12 N K + 4 D (mirror in place; 8 N K + 8 D with a shared
+base) against about 28 N D; the summary carries the two kernels' own times.  Writes
+<out-dir>/<spec>_<shape>.jsonl (default profiles/r17/sparse_wire).
+
 --frecon (elementwise specs, default qsgd:127,natural; device draws): the FRECON round with its server tail,
   one_call     FreconUplinkReducer(G, H, P, alpha, server=...)                flc_frecon_reduce
   composition  ShiftUplinkReducer twice (in-place DIANA over (G, H), the plain fold over (G, P)) and the
@@ -554,6 +563,103 @@ def main_wire(a):
         del P
 
 
+def main_wire_sparse(a):
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d = a.n, a.d
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev).manual_seed(1000)
+
+    def filled(rows):
+        t = torch.empty((rows, d), dtype=torch.float32, device=dev)
+        for i in range(0, rows, 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    G, M0, gprev = filled(n), filled(n), filled(1)[0]
+    Ms, Mg = torch.empty_like(M0), torch.empty_like(M0)
+    outs = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in ("sparse", "general")}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    kernels = ("k_sparse_tile_tab", "k_sparse_shift_accum")
+    for spec in a.specs.split(","):
+        if not spec.startswith(("topk", "randk")):
+            raise SystemExit("--wire --sparse times RandK / TopK specs only")
+        comp = ag.initCompressor(spec, d)
+        k, pb = comp.K, comp.payloadBytes(d)
+        mult = 1.0 if comp.isContractionCompressor() else 1.0 / (1.0 + comp.getW())
+        P = torch.empty((n, pb), dtype=torch.uint8, device=dev)    # packed once, outside the clock
+        for i in range(n):
+            comp.device_rng = (SEED, i)
+            comp.compressShiftPayload(G[i], M0[i], payload_out=P[i])
+        red = ag.ShiftPayloadReducer(comp, device=dev)
+        for shape in ("ef21", "marina"):
+            Ms.copy_(M0)
+            Mg.copy_(M0)
+            if shape == "ef21":                        # the server mirror in place, each leg on its own copy
+                runs = {"sparse": lambda: red(P, d, scale=mult, base=Ms, msg_out=Ms, out=outs["sparse"], sparse=True),
+                        "general": lambda: red(P, d, scale=mult, base=Mg, msg_out=Mg, out=outs["general"])}
+                model = {"sparse": 4 * n * d + 12 * n * k + 4 * d, "general": 28 * n * d}
+            else:                                      # MARINA: one shared base, nothing stored
+                runs = {"sparse": lambda: red(P, d, base=gprev, out=outs["sparse"], sparse=True),
+                        "general": lambda: red(P, d, base=gprev, out=outs["general"])}
+                model = {"sparse": 8 * n * k + 8 * d, "general": 28 * n * d}
+
+            def agree():
+                return (torch.equal(outs["sparse"].view(torch.int32), outs["general"].view(torch.int32))
+                        and torch.equal(Ms.view(torch.int32), Mg.view(torch.int32)))
+            for f in runs.values():                    # warm: code objects, workspaces
+                f()
+            torch.cuda.synchronize()
+            if not agree():
+                raise SystemExit(f"{spec} {shape}: the sparse and the general fold differ after the warm-up call")
+            ms = {v: [] for v in runs}
+            path = os.path.join(a.out_dir, spec.replace(":", "_").replace("%", "pct") + f"_{shape}.jsonl")
+            with open(path, "w") as fh:
+                def emit(rec):
+                    line = json.dumps(rec)
+                    fh.write(line + "\n")
+                    fh.flush()
+                    print(line, flush=True)
+                extra = {"spec": spec, "shape": shape, "n": n, "d": d, "k": k}
+                for r in range(a.repeats):
+                    for v, f in runs.items():
+                        e0.record()
+                        for _ in range(a.steps):
+                            f()
+                        e1.record()
+                        e1.synchronize()
+                        t = e0.elapsed_time(e1) / a.steps
+                        ms[v].append(t)
+                        emit(dict(extra, repeat=r, variant=v, ms_per_call=round(t, 4)))
+                    if not agree():
+                        raise SystemExit(f"{spec} {shape}: the sparse and the general fold differ after repeat {r}")
+                _lib.profile_enable(True)              # the two kernels' own times, one call
+                for kn in kernels:
+                    _lib.profile_collect(kn)
+                runs["sparse"]()
+                runs["general"]()                      # (keeps the two mirrors in step; its kernels carry no timers)
+                torch.cuda.synchronize()
+                _lib.profile_enable(False)
+                kms = {kn: round(t, 4) for kn in kernels for t, c in [_lib.profile_collect(kn)] if c}
+                if not agree():
+                    raise SystemExit(f"{spec} {shape}: the sparse and the general fold differ after the timer pass")
+                med = {v: statistics.median(ms[v]) for v in runs}
+                emit(dict(extra, summary=True, repeats=a.repeats, steps=a.steps,
+                          median_ms={v: round(med[v], 4) for v in runs}, min_ms={v: round(min(ms[v]), 4) for v in runs},
+                          max_ms={v: round(max(ms[v]), 4) for v in runs}, model_bytes=model,
+                          TBps_of_model_at_median={v: round(model[v] / med[v] / 1e9, 3) for v in runs},
+                          general_over_sparse=round(med["general"] / med["sparse"], 3),
+                          byte_model_general_over_sparse=round(model["general"] / model["sparse"], 3),
+                          sparse_faster_beyond_spread=max(ms["sparse"]) < min(ms["general"]),
+                          bits_equal_every_repeat=True, kernel_ms_one_call=kms))
+            print("wrote", path, flush=True)
+        del P
+
+
 def main_frecon(a):
     import torch
 
@@ -826,6 +932,11 @@ def main():
         a.out_dir = os.path.join(ROOT, "profiles", "r12", "dither_shift")
     if a.one_read and a.specs == ap.get_default("specs"):
         a.specs = "qsgd:127"
+    if a.wire and a.sparse:
+        if a.out_dir == ap.get_default("out_dir"):
+            a.out_dir = os.path.join(ROOT, "profiles", "r17", "sparse_wire")
+        if a.specs == ap.get_default("specs"):
+            a.specs = "topk:1%,randk:1%"
     if a.wire and a.out_dir == ap.get_default("out_dir"):
         a.out_dir = os.path.join(ROOT, "profiles", "r13", "shift_wire")
     if a.wire and a.specs == ap.get_default("specs"):
@@ -838,6 +949,8 @@ def main():
         ap.error("--repeats, --steps, --n and --d are positive")
     if a.sampled:
         return main_sampled(a)
+    if a.wire and a.sparse:
+        return main_wire_sparse(a)
     if a.sparse:
         return main_sparse(a)
     if a.topk:
