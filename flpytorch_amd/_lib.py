@@ -54,6 +54,9 @@ EXPORTS = [
     "flc_payload_bits_format", "flc_payload_bits_bytes", "flc_payload_validate_bits",
     "flc_pack_bits_workspace_size", "flc_pack_bits", "flc_unpack_bits",
     "flc_unpack_reduce_bits_workspace_size", "flc_unpack_reduce_bits",
+    "flc_payload_seeded_format", "flc_payload_seeded_bytes", "flc_payload_validate_seeded",
+    "flc_pack_seeded_workspace_size", "flc_pack_seeded", "flc_unpack_seeded_workspace_size", "flc_unpack_seeded",
+    "flc_unpack_reduce_seeded_workspace_size", "flc_unpack_reduce_seeded",
     "flc_pack_shift_workspace_size", "flc_pack_shift",
     "flc_unpack_shift_reduce_workspace_size", "flc_unpack_shift_reduce",
     "flc_unpack_shift_reduce_sparse_workspace_size", "flc_unpack_shift_reduce_sparse",
@@ -303,6 +306,19 @@ def _bind(lib):
         lib.flc_unpack_reduce_bits_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
         lib.flc_unpack_reduce_bits_workspace_size.restype = sz
         lib.flc_unpack_reduce_bits.argtypes = [P(FlcCodecParams), vp, i64, vp, i64, i64, vp, f32, vp, vp, sz, vp]
+    if hasattr(lib, "flc_pack_seeded"):             # (absent from A/B builds of older revisions)
+        lib.flc_payload_seeded_format.argtypes = [P(FlcCodecParams)]
+        lib.flc_payload_seeded_bytes.argtypes = [P(FlcCodecParams), i64]
+        lib.flc_payload_seeded_bytes.restype = i64
+        lib.flc_payload_validate_seeded.argtypes = [P(FlcCodecParams), vp, i64, i64, i64]
+        for q in ("flc_pack_seeded", "flc_unpack_seeded"):
+            getattr(lib, q + "_workspace_size").argtypes = [P(FlcCodecParams), i64]
+            getattr(lib, q + "_workspace_size").restype = sz
+        lib.flc_pack_seeded.argtypes = [P(FlcCodecParams), P(FlcPattern), vp, i64, vp, vp, sz, vp]
+        lib.flc_unpack_seeded.argtypes = [P(FlcCodecParams), vp, i64, vp, vp, sz, vp]
+        lib.flc_unpack_reduce_seeded_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_unpack_reduce_seeded_workspace_size.restype = sz
+        lib.flc_unpack_reduce_seeded.argtypes = [P(FlcCodecParams), vp, i64, vp, i64, i64, vp, f32, vp, vp, sz, vp]
     lib.flc_combine_workspace_size.argtypes = [vp, i64, i32]
     lib.flc_combine_workspace_size.restype = sz
     lib.flc_combine_partials.argtypes = [vp, vp, i64, f32, i32, vp, sz, vp]
@@ -350,6 +366,8 @@ def _bind(lib):
                         "flc_unpack_reduce_workspace_size", "flc_combine_workspace_size",
                         "flc_payload_bits_bytes", "flc_pack_bits_workspace_size",
                         "flc_unpack_reduce_bits_workspace_size",
+                        "flc_payload_seeded_bytes", "flc_pack_seeded_workspace_size", "flc_unpack_seeded_workspace_size",
+                        "flc_unpack_reduce_seeded_workspace_size",
                         "flc_combine_blocks_workspace_size", "flc_device_randk_counts_workspace_size",
                         "flc_norm2_torch_cpu_workspace_size"):
             getattr(lib, name).restype = i32

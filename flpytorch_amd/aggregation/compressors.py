@@ -122,6 +122,8 @@ _BITS_ENTRY = {
     "flc_unpack": "flc_unpack_bits", "flc_unpack_reduce_workspace_size": "flc_unpack_reduce_bits_workspace_size",
     "flc_unpack_reduce": "flc_unpack_reduce_bits",
 }
+# ... and their seeded counterparts (RandK with device draws: values only, FMT_SEEDED)
+_SEEDED_ENTRY = {name: b.replace("_bits", "_seeded") for name, b in _BITS_ENTRY.items()}
 
 
 def _gpu_device(x):
@@ -445,11 +447,21 @@ class Compressor:
             return prm
         return self.codec_params(torch.device("cpu"))[0]
 
-    def _wire_entry(self, name, bits, prm=None):
+    def _wire_entry(self, name, bits, prm=None, seeded=False):
         """The C entry ``name`` of the byte formats or, with ``bits``, its bit-packed counterpart
         (FMT_LBITS / FMT_NAT9, include/flcodec.h "Bit-packed messages").  A codec without a bit-packed
-        form is refused here, before any size is computed or anything is launched."""
+        form is refused here, before any size is computed or anything is launched.  ``seeded``: the
+        seeded counterpart (FMT_SEEDED, "Seeded RandK messages"), under the same contract: only RandK
+        with ``device_rng`` set has it (the server redraws the index set from the client's key)."""
         lib = _lib.load()
+        if seeded:
+            if bits:
+                raise ValueError(f"{name}: seeded=True with bits=True (a message has one form)")
+            if not hasattr(lib, "flc_pack_seeded"):
+                raise NotImplementedError("this library build has no flc_pack_seeded")
+            if self.compressorType != CompressorType.RANDK_COMPRESSOR or self.device_rng is None:
+                raise NotImplementedError(f"{name}: only RandK with device draws (device_rng) has a seeded wire form")
+            return getattr(lib, _SEEDED_ENTRY[name])
         if not bits:
             return getattr(lib, name)
         if not hasattr(lib, "flc_pack_bits"):
@@ -460,17 +472,20 @@ class Compressor:
                                       "(natural, or standard dithering / qsgd / terngrad with s <= 63)")
         return getattr(lib, _BITS_ENTRY[name])
 
-    def payloadBytes(self, d=None, bits=False):
+    def payloadBytes(self, d=None, bits=False, seeded=False):
         """Bytes of one row's payload (flc_payload_bytes: 16-B header + body, 16-B padded; ``bits``:
-        flc_payload_bits_bytes, 16 + 256 b ceil(d / 2048))."""
+        flc_payload_bits_bytes, 16 + 256 b ceil(d / 2048); ``seeded``: flc_payload_seeded_bytes,
+        32 + 4 K padded to 16)."""
         prm = self._host_params()
-        return int(self._wire_entry("flc_payload_bytes", bits, prm)(ctypes.byref(prm), self._dim(d)))
+        return int(self._wire_entry("flc_payload_bytes", bits, prm, seeded)(ctypes.byref(prm), self._dim(d)))
 
-    def validatePayload(self, payload, d=None, bits=False):
+    def validatePayload(self, payload, d=None, bits=False, seeded=False, client=None):
         """Check a message received from a peer before it is decoded (flc_payload_validate, host
         only): its size, header and codes fit this codec and d.  ``payload``: bytes-like, a uint8
         numpy array or a host uint8 tensor.  ``bits``: the bit-packed message
-        (flc_payload_validate_bits).  Raises ValueError with the reason."""
+        (flc_payload_validate_bits).  ``seeded``: the seeded RandK message
+        (flc_payload_validate_seeded); with ``client`` its key must be that client's under this
+        compressor's seed.  Raises ValueError with the reason."""
         if torch.is_tensor(payload):
             if payload.dtype != torch.uint8 or payload.is_cuda:
                 raise TypeError("validatePayload: a host uint8 tensor (or bytes) is expected")
@@ -478,8 +493,9 @@ class Compressor:
         else:
             arr = np.frombuffer(payload, dtype=np.uint8)
         prm = self._host_params()
-        rc = self._wire_entry("flc_payload_validate", bits, prm)(ctypes.byref(prm), ctypes.c_void_p(arr.ctypes.data),
-                                                               int(arr.nbytes), self._dim(d))
+        more = (-1 if client is None else int(client),) if seeded else ()
+        rc = self._wire_entry("flc_payload_validate", bits, prm, seeded)(ctypes.byref(prm), ctypes.c_void_p(arr.ctypes.data),
+                                                                       int(arr.nbytes), self._dim(d), *more)
         _lib.check(rc, "validatePayload")
 
     def _dim(self, d):
@@ -489,11 +505,12 @@ class Compressor:
             raise ValueError("this compressor has no D (identity): pass d")
         return int(d)
 
-    def compressPayload(self, x, out=None, bits=False):
+    def compressPayload(self, x, out=None, bits=False, seeded=False):
         """The message this client would send: flc_pack of compressVector(x) (same pattern, same
         draws), as a uint8 device tensor of payloadBytes() bytes.  ``bits``: the bit-packed message
-        (flc_pack_bits, payloadBytes(bits=True) bytes), the same codes at sub-byte width.  Statistics
-        advance like compressVector."""
+        (flc_pack_bits, payloadBytes(bits=True) bytes), the same codes at sub-byte width.  ``seeded``:
+        RandK's values alone (flc_pack_seeded, payloadBytes(seeded=True) bytes), gathered in O(K).
+        Statistics advance like compressVector."""
         if x.dtype != torch.float32:
             raise TypeError(f"flcodec encodes fp32 only (got {x.dtype})")
         dev = _gpu_device(x)
@@ -501,34 +518,34 @@ class Compressor:
         d = xd.numel()
         lib = _lib.load()
         prm, keep = self.codec_params(dev)
-        pack = self._wire_entry("flc_pack", bits, prm)
+        pack = self._wire_entry("flc_pack", bits, prm, seeded)
         pat = self._pattern(dev, keep)
-        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm)(ctypes.byref(prm), d))
+        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm, seeded)(ctypes.byref(prm), d))
         if out is None:
             out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         elif out.numel() < nbytes or out.dtype != torch.uint8 or out.data_ptr() % 16:
             raise ValueError("compressPayload: out must be a 16-byte aligned uint8 tensor of payloadBytes()")
-        ws_bytes = self._wire_entry("flc_pack_workspace_size", bits, prm)(ctypes.byref(prm), d)
+        ws_bytes = self._wire_entry("flc_pack_workspace_size", bits, prm, seeded)(ctypes.byref(prm), d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):
             rc = pack(ctypes.byref(prm), ctypes.byref(pat), ctypes.c_void_p(xd.data_ptr()), d,
                       ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
                       _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_pack_bits" if bits else "flc_pack")
+        _lib.check(rc, "flc_pack_seeded" if seeded else ("flc_pack_bits" if bits else "flc_pack"))
         self._account(d)
         return out
 
-    def decompressPayload(self, payload, d=None, bits=False):
-        """Dense fp32 row of a payload (flc_unpack; ``bits``: flc_unpack_bits of a bit-packed one):
-        compressVector's output, bit for bit."""
+    def decompressPayload(self, payload, d=None, bits=False, seeded=False):
+        """Dense fp32 row of a payload (flc_unpack; ``bits``: flc_unpack_bits of a bit-packed one;
+        ``seeded``: flc_unpack_seeded of a seeded one): compressVector's output, bit for bit."""
         dev = _gpu_device(payload)
         d = self._dim(d)
         lib = _lib.load()
         prm, keep = self.codec_params(dev)
         if payload.dtype != torch.uint8:
             raise TypeError(f"decompressPayload: payload must be uint8 (got {payload.dtype})")
-        unpack = self._wire_entry("flc_unpack", bits, prm)
-        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm)(ctypes.byref(prm), d))
+        unpack = self._wire_entry("flc_unpack", bits, prm, seeded)
+        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm, seeded)(ctypes.byref(prm), d))
         if payload.numel() < nbytes:
             raise ValueError(f"decompressPayload: {payload.numel()} bytes, the payload of d={d} is {nbytes}")
         # a host message (off the network) crosses to the device first; the kernel reads HBM only
@@ -536,10 +553,14 @@ class Compressor:
         if not payload.is_contiguous() or payload.data_ptr() % 16:
             payload = payload.clone()
         out = torch.empty(d, dtype=torch.float32, device=dev)
+        more = ()
+        if seeded:                                    # the redrawn counts and offsets live in a workspace
+            ws = _lib.WORKSPACE.get(dev, lib.flc_unpack_seeded_workspace_size(ctypes.byref(prm), d))
+            more = (ctypes.c_void_p(ws.data_ptr()), ws.numel())
         with torch.cuda.device(dev):
             rc = unpack(ctypes.byref(prm), ctypes.c_void_p(payload.data_ptr()), d,
-                        ctypes.c_void_p(out.data_ptr()), _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_unpack_bits" if bits else "flc_unpack")
+                        ctypes.c_void_p(out.data_ptr()), *more, _lib.stream_ptr(dev))
+        _lib.check(rc, "flc_unpack_seeded" if seeded else ("flc_unpack_bits" if bits else "flc_unpack"))
         return out
 
     # -- shift codecs ----------------------------------------------------

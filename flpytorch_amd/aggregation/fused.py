@@ -747,13 +747,17 @@ class PayloadReducer:
     client order straight from the messages (flc_unpack_reduce) — the same bits as
     flc_encode_reduce of the rows the payloads were packed from.  ``bits=True``: the payloads are
     the bit-packed messages (compressPayload(bits=True)), folded by flc_unpack_reduce_bits to the
-    same bits; a codec without a bit-packed form is refused with NotImplementedError."""
+    same bits; a codec without a bit-packed form is refused with NotImplementedError.
+    ``seeded=True``: the payloads are seeded RandK messages (compressPayload(seeded=True)), folded by
+    flc_unpack_reduce_seeded — each row's index set redrawn from the key its message carries — to the
+    same bits; anything but RandK with device draws is refused with NotImplementedError."""
 
-    def __init__(self, compressor: Compressor, device=None, bits=False):
+    def __init__(self, compressor: Compressor, device=None, bits=False, seeded=False):
         _lib.require_gpu()
         self.comp = compressor
         self.device = _device(device)
         self.bits = bool(bits)
+        self.seeded = bool(seeded)
 
     def __call__(self, payloads, d=None, out=None, weights=None, divisor=None):
         """payloads: [N, ld] uint8 device tensor (rows 16-byte aligned, ld % 16 == 0) or a list of
@@ -762,7 +766,7 @@ class PayloadReducer:
         dev = self.device
         d = self.comp._dim(d)
         prm, keep = self.comp.codec_params(dev)
-        fold = self.comp._wire_entry("flc_unpack_reduce", self.bits, prm)
+        fold = self.comp._wire_entry("flc_unpack_reduce", self.bits, prm, self.seeded)
         if torch.is_tensor(payloads) and payloads.dim() == 2:
             n, ld = payloads.shape
             if payloads.stride(1) != 1 or payloads.stride(0) % 16 or payloads.data_ptr() % 16:
@@ -777,13 +781,14 @@ class PayloadReducer:
         if out is None:
             out = torch.empty(d, dtype=torch.float32, device=dev)
         w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
-        ws_bytes = self.comp._wire_entry("flc_unpack_reduce_workspace_size", self.bits, prm)(ctypes.byref(prm), n, d)
+        ws_bytes = self.comp._wire_entry("flc_unpack_reduce_workspace_size", self.bits, prm, self.seeded)(ctypes.byref(prm), n, d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):
             rc = fold(ctypes.byref(prm), ctypes.c_void_p(base), ldb, ctypes.c_void_p(ptrs), n, d,
                       ctypes.c_void_p(w_ptr), ctypes.c_float(total), ctypes.c_void_p(out.data_ptr()),
                       ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_unpack_reduce_bits" if self.bits else "flc_unpack_reduce")
+        _lib.check(rc, "flc_unpack_reduce_seeded" if self.seeded else
+                   ("flc_unpack_reduce_bits" if self.bits else "flc_unpack_reduce"))
         return out
 
 

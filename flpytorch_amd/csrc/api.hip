@@ -727,6 +727,79 @@ extern "C" int flc_unpack_reduce_bits(const flc_codec_params* prm, const void* d
                                   w_total, d_out, (hipStream_t)stream);
 }
 
+// ---- seeded RandK messages (wire_seeded.hip) --------------------------------------------------------
+// only RandK has a seeded form: FLC_ERR_UNSUPPORTED before anything else is looked at (given indices,
+// which the entry that takes a pattern sees, are refused by flc_pack_seeded itself)
+static int seeded_codec(const flc_codec_params* prm, const char* me) {
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (prm->codec != FLC_RANDK) {
+        set_error("%s: codec %d has no seeded form (RandK with device draws only)", me, prm->codec);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    return FLC_OK;
+}
+
+extern "C" int flc_payload_seeded_format(const flc_codec_params* prm) {
+    return prm && prm->codec == FLC_RANDK ? 9 : 0;
+}
+
+extern "C" int64_t flc_payload_seeded_bytes(const flc_codec_params* prm, int64_t d) {
+    if (!prm || prm->codec != FLC_RANDK || d < 0) return 0;
+    return seeded_payload_bytes(prm, d);
+}
+
+extern "C" int flc_payload_validate_seeded(const flc_codec_params* prm, const void* h_payload, int64_t nbytes, int64_t d,
+                                           int64_t client) {
+    const char* me = "flc_payload_validate_seeded";
+    if (int rc = seeded_codec(prm, me)) return rc;
+    if (d < 0 || nbytes < 0 || (nbytes > 0 && !h_payload)) { set_error("%s: bad payload/nbytes/d", me); return FLC_ERR_ARG; }
+    return seeded_payload_validate(prm, (const uint8_t*)h_payload, nbytes, d, client);
+}
+
+extern "C" size_t flc_pack_seeded_workspace_size(const flc_codec_params* prm, int64_t d) {
+    if (!prm || prm->codec != FLC_RANDK || d < 0) return 0;
+    return seeded_workspace(1, d);
+}
+
+extern "C" int flc_pack_seeded(const flc_codec_params* prm, const flc_pattern* pat, const float* d_x, int64_t d,
+                               void* d_payload, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_pack_seeded";
+    if (int rc = seeded_codec(prm, me)) return rc;
+    if (d < 0 || !d_payload || (d > 0 && !d_x)) { set_error("%s: bad x/payload/d", me); return FLC_ERR_ARG; }
+    return seeded_pack_run(prm, pat, d_x, d, (char*)d_payload, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t flc_unpack_seeded_workspace_size(const flc_codec_params* prm, int64_t d) {
+    if (!prm || prm->codec != FLC_RANDK || d < 0) return 0;
+    return seeded_workspace(1, d);
+}
+
+extern "C" int flc_unpack_seeded(const flc_codec_params* prm, const void* d_payload, int64_t d, float* d_out, void* d_ws,
+                                 size_t ws_bytes, void* stream) {
+    const char* me = "flc_unpack_seeded";
+    if (int rc = seeded_codec(prm, me)) return rc;
+    if (d < 0 || (d > 0 && (!d_payload || !d_out))) { set_error("%s: bad payload/out/d", me); return FLC_ERR_ARG; }
+    return seeded_unpack_run(prm, (const char*)d_payload, d, d_out, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t flc_unpack_reduce_seeded_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    if (!prm || prm->codec != FLC_RANDK || n < 0 || d < 0) return 0;
+    return seeded_workspace(n, d);
+}
+
+extern "C" int flc_unpack_reduce_seeded(const flc_codec_params* prm, const void* d_payloads, int64_t ld_bytes,
+                                        const void* const* d_payload_ptrs, int64_t n, int64_t d, const float* d_w,
+                                        float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_unpack_reduce_seeded";
+    if (int rc = seeded_codec(prm, me)) return rc;
+    if (n < 0 || d < 0 || (d > 0 && !d_out)) { set_error("%s: bad n/d/out", me); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) return too_many(me, n, "payloads", FLC_ERR_UNSUPPORTED);
+    if (n > 0 && d > 0 && !d_payloads && !d_payload_ptrs) { set_error("%s: no payloads", me); return FLC_ERR_ARG; }
+    if (d_payloads && ld_bytes < seeded_payload_bytes(prm, d)) { set_error("%s: ld_bytes < payload size", me); return FLC_ERR_ARG; }
+    return seeded_unpack_reduce_run(prm, (const char*)d_payloads, ld_bytes, (const char* const*)d_payload_ptrs, n, d, d_w,
+                                    w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
 // ---- shifted steps on the wire (wire_shift.hip) ----------------------------------------------------
 extern "C" size_t flc_pack_shift_workspace_size(const flc_codec_params* prm, int64_t d) {
     if (!prm || !known(prm->codec) || prm->codec == FLC_RANK_K || d < 0) return 0;

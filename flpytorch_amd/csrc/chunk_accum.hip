@@ -68,6 +68,7 @@ __device__ void resolve_neg_zero(float* tl, uint32_t* rm, const SelWs& ws, int64
         any |= b != 0ull;
     }
     if (!any) return;
+    wave_lds_fence();                                  // lane 0's mask words, read by every lane
     uint32_t z0[WL], zc[WL];
 #pragma unroll
     for (int j = 0; j < WL; ++j) {
@@ -79,6 +80,7 @@ __device__ void resolve_neg_zero(float* tl, uint32_t* rm, const SelWs& ws, int64
         if (w && (__float_as_uint(w[r]) >> 31)) continue;      // its skipped term is -0: no constraint
 #pragma unroll
         for (int j = 0; j < WL; ++j) if (lane + 64 * j < NW) rm[lane + 64 * j] = 0u;
+        wave_lds_fence();
         const RowMeta m = load_meta(ws, c, n, r, w);
         const uint32_t mode = m.mode, T = m.thr, cut = m.cut;
         for (uint32_t e = (uint32_t)lane; e < m.te.y; e += 64) {
@@ -88,6 +90,8 @@ __device__ void resolve_neg_zero(float* tl, uint32_t* rm, const SelWs& ws, int64
             if (loc < (uint32_t)TS && (mode == 2u || key > T || (key == T && tie_pref(ix, ws.tie_hi) >= cut)))
                 atomicOr(&rm[loc >> 5], 1u << (loc & 31));
         }
+        // a lane that listed no entry still reads the words other lanes have set: not its own zeros
+        wave_lds_fence();
         bool left = false;
 #pragma unroll
         for (int j = 0; j < WL; ++j) {
@@ -96,6 +100,7 @@ __device__ void resolve_neg_zero(float* tl, uint32_t* rm, const SelWs& ws, int64
         }
         if (__ballot(left) == 0ull) break;
     }
+    wave_lds_fence();
 #pragma unroll
     for (int j = 0; j < WL; ++j) {
         uint32_t dead = z0[j] & ~zc[j];
@@ -105,6 +110,7 @@ __device__ void resolve_neg_zero(float* tl, uint32_t* rm, const SelWs& ws, int64
             tl[(lane + 64 * j) * 32 + b] = 0.f;
         }
     }
+    wave_lds_fence();                                  // the caller's lanes read columns other lanes cleared
 }
 
 // resolve_neg_zero for one-wave workgroups whose LDS holds only the tile: the -0 column masks

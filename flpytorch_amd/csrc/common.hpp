@@ -273,6 +273,21 @@ int bits_pack_run(const flc_codec_params* prm, const flc_pattern* pat, const flo
 int bits_unpack_run(const flc_codec_params* prm, const char* payload, int64_t d, float* out, hipStream_t st);
 int bits_unpack_reduce_run(const flc_codec_params* prm, const char* base, int64_t ld, const char* const* ptrs, int64_t n,
                            int64_t d, const float* w, float wt, float* out, hipStream_t st);
+// the seeded RandK message (wire_seeded.hip, FMT_SEEDED): flc_pack_seeded & co.; randk.hip's count
+// pass with the keys given by (seed, client0 + row) or read from the n messages' draw blocks
+int randk_counts_keyed(uint64_t seed, int64_t client0, int64_t n, int64_t d, int64_t K, uint32_t* cnt, uint64_t* ckey,
+                       hipStream_t st);
+int randk_counts_from_messages(const char* base, int64_t ld, const char* const* ptrs, int64_t n, int64_t d, int64_t K,
+                               uint32_t* cnt, uint64_t* ckey, hipStream_t st);
+int64_t seeded_payload_bytes(const flc_codec_params* prm, int64_t d);
+int seeded_payload_validate(const flc_codec_params* prm, const uint8_t* p, int64_t nbytes, int64_t d, int64_t client);
+size_t seeded_workspace(int64_t n, int64_t d);
+int seeded_pack_run(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, char* payload, void* ws,
+                    size_t ws_bytes, hipStream_t st);
+int seeded_unpack_run(const flc_codec_params* prm, const char* payload, int64_t d, float* out, void* ws, size_t ws_bytes,
+                      hipStream_t st);
+int seeded_unpack_reduce_run(const flc_codec_params* prm, const char* base, int64_t ld, const char* const* ptrs, int64_t n,
+                             int64_t d, const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
 // Row g's boundary of G row groups whose last group is `lastpct` % of the others' size (the last
 // group's tail is the exposed one): rows [group_row(n, G, g), group_row(n, G, g + 1)).
 // lastpct is clamped to [1, 100]: 0 or less would leave the last group (the one whose fold writes
@@ -472,6 +487,12 @@ __host__ __device__ inline bool below32(uint32_t h, float p) { return h < thr32(
 // Wave helpers
 // ------------------------------------------------------------------------------------------
 __device__ inline int lane_id() { return __lane_id(); }
+
+// The lanes of a wave exchange values through LDS.  To the compiler every lane is a thread of its
+// own: without a fence it forwards a lane's own earlier store to its later load on the paths where
+// that lane stored nothing in between, although another lane did.  Wavefront scope: no instruction
+// is emitted (a wave's LDS operations execute in order).
+__device__ inline void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
 template <class T>
 __device__ inline T wave_sum(T v) {

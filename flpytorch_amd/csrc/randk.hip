@@ -2,6 +2,7 @@
 // (counts, list-free fold, short-row lists), the lists on their own for the shifted round, and the
 // dense single-vector encode.  Data flow, workspace and switches: select_impl.hpp.
 #include "select_impl.hpp"
+#include "wire_codes.hpp"
 
 namespace flc {
 
@@ -248,6 +249,27 @@ __global__ __launch_bounds__(256) void k_randk_ckeys(int64_t n, uint64_t seed, i
     if (row < n) ckey[row] = client_key(seed, client0 + row);
 }
 
+// A row's key.  MapNone / MapIds: the client's, client_key(seed, client0 + row or ids[row]).  MsgKeys
+// (the seeded wire format, wire_seeded.hip): the key in the draw block of the row's message; a
+// message that is not a seeded one of this K and d draws nothing (K = 0: every count 0), so
+// nothing downstream reads a value of it.
+struct MsgKeys {
+    const char* base;
+    int64_t ld;
+    const char* const* ptrs;
+};
+template <class M>
+__device__ inline uint64_t rk_row_key(const M& map, uint64_t seed, int64_t client0, int64_t row, int64_t, int64_t&) {
+    return client_key(seed, client0 + (M::ON ? map.id_s(row) : row));
+}
+__device__ inline uint64_t rk_row_key(const MsgKeys& mk, uint64_t, int64_t, int64_t row, int64_t d, int64_t& K) {
+    // {fmt, count, norm, bad} {key_lo, key_hi, d_lo, d_hi}
+    const uint32_t* h = reinterpret_cast<const uint32_t*>(mk.base ? mk.base + row * mk.ld : mk.ptrs[row]);
+    const uint64_t md = ((uint64_t)h[7] << 32) | (uint64_t)h[6];
+    if (h[0] != (uint32_t)FMT_SEEDED || h[1] != (uint32_t)K || md != (uint64_t)d) K = 0;
+    return ((uint64_t)h[5] << 32) | (uint64_t)h[4];
+}
+
 // M (the sampled sparse round): row `row` is the participant, its key the client's (client0 + ids[row])
 template <class M = MapNone>
 __global__ __launch_bounds__(RKC_NT) void k_randk_counts(int64_t n, int64_t d, int64_t K, uint64_t seed, int64_t client0,
@@ -257,7 +279,7 @@ __global__ __launch_bounds__(RKC_NT) void k_randk_counts(int64_t n, int64_t d, i
     const int tid = threadIdx.x;
     const int64_t C = nchunks(d);
     const int64_t c0 = (int64_t)blockIdx.x * RKC_BINS, nc = min(C, c0 + RKC_BINS) - c0;
-    const uint64_t ck = client_key(seed, client0 + (M::ON ? map.id_s(row) : row));
+    const uint64_t ck = rk_row_key(map, seed, client0, row, d, K);
     for (int64_t i = tid; i < (nc + 1) / 2; i += RKC_NT) bins[i] = 0;
     __syncthreads();
     const rktree::RowPerm P(ck, (uint64_t)d);
@@ -535,6 +557,28 @@ static int randk_counts(const flc_codec_params* prm, const flc_pattern* pat, int
                                 prm->seed, pat ? pat->client0 : (int64_t)0, ws, map_ids(map));
     else hipLaunchKernelGGL(k_randk_counts<MapNone>, dim3((unsigned)parts, (unsigned)n), dim3(RKC_NT), 0, st, n, d, prm->k, prm->seed,
                        pat ? pat->client0 : (int64_t)0, ws, MapNone{});
+    FLC_CHECK_LAUNCH("k_randk_counts");
+    return FLC_OK;
+}
+
+// counts [C][n] and keys [n] into the caller's arrays (wire_seeded.hip): the keys of clients
+// client0 .. client0 + n - 1, or the keys the n seeded messages carry
+int randk_counts_keyed(uint64_t seed, int64_t client0, int64_t n, int64_t d, int64_t K, uint32_t* cnt, uint64_t* ckey,
+                       hipStream_t st) {
+    ProfScope _ps("k_randk_counts", st);
+    const int64_t parts = (host_chunks(d) + RKC_BINS - 1) / RKC_BINS;
+    hipLaunchKernelGGL(k_randk_counts<MapNone>, dim3((unsigned)parts, (unsigned)n), dim3(RKC_NT), 0, st, n, d, K, seed, client0,
+                       RkdWs{cnt, ckey}, MapNone{});
+    FLC_CHECK_LAUNCH("k_randk_counts");
+    return FLC_OK;
+}
+
+int randk_counts_from_messages(const char* base, int64_t ld, const char* const* ptrs, int64_t n, int64_t d, int64_t K,
+                               uint32_t* cnt, uint64_t* ckey, hipStream_t st) {
+    ProfScope _ps("k_randk_counts", st);
+    const int64_t parts = (host_chunks(d) + RKC_BINS - 1) / RKC_BINS;
+    hipLaunchKernelGGL(k_randk_counts<MsgKeys>, dim3((unsigned)parts, (unsigned)n), dim3(RKC_NT), 0, st, n, d, K, (uint64_t)0,
+                       (int64_t)0, RkdWs{cnt, ckey}, MsgKeys{base, ld, ptrs});
     FLC_CHECK_LAUNCH("k_randk_counts");
     return FLC_OK;
 }

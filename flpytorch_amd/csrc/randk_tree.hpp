@@ -106,6 +106,7 @@ __device__ void rk_resolve_neg_zero(float* tl, uint32_t* rm, const uint32_t* cnt
         any |= b != 0ull;
     }
     if (!any) return;
+    wave_lds_fence();                                  // lane 0's mask words, read by every lane
     uint32_t z0[WL], zc[WL];
 #pragma unroll
     for (int j = 0; j < WL; ++j) {
@@ -117,12 +118,15 @@ __device__ void rk_resolve_neg_zero(float* tl, uint32_t* rm, const uint32_t* cnt
         if (w && (__float_as_uint(w[r]) >> 31)) continue;
 #pragma unroll
         for (int j = 0; j < WL; ++j) if (lane + 64 * j < NW) rm[lane + 64 * j] = 0u;
+        wave_lds_fence();
         const uint32_t m = min(cnt[c * n + r], clen);
         const rktree::ChunkPerm P(ckey[r], c, clen);
         for (uint32_t t = (uint32_t)lane; t < m; t += 64) {
             const uint32_t loc = P(t) - pbase;
             if (loc < (uint32_t)TS) atomicOr(&rm[loc >> 5], 1u << (loc & 31));
         }
+        // a lane that listed no member still reads the words other lanes have set: not its own zeros
+        wave_lds_fence();
         bool left = false;
 #pragma unroll
         for (int j = 0; j < WL; ++j) {
@@ -140,6 +144,7 @@ __device__ void rk_resolve_neg_zero(float* tl, uint32_t* rm, const uint32_t* cnt
             tl[(lane + 64 * j) * 32 + b] = 0.f;
         }
     }
+    wave_lds_fence();                                  // the caller's lanes read columns other lanes cleared
 }
 #endif
 

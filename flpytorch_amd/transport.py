@@ -92,13 +92,15 @@ class PayloadSocket:
             payload = payload.detach().reshape(-1).cpu().numpy()
         self.rawSend(payload)
 
-    def recvPayload(self, compressor, d=None, device=None, bits=False):
+    def recvPayload(self, compressor, d=None, device=None, bits=False, seeded=False, client=None):
         """Receive one wire message for ``compressor`` (rows of ``d`` elements), check it
         (``validatePayload``: nothing malformed reaches the decode) and return it as a uint8
         tensor on ``device`` (host when None), ready for ``decompressPayload`` /
         ``PayloadReducer``.  The expected size is known up front: any other length is refused
         before the body is read."""
-        want = compressor.payloadBytes(d, bits=bits)     # bits: the bit-packed message and its check
+        # bits: the bit-packed message and its check; seeded: RandK's seeded one (client: whose key it must carry)
+        kw = {"seeded": True, "client": client} if seeded else {}
+        want = compressor.payloadBytes(d, bits=bits, seeded=seeded)
         n = self._recv_prefix()
         if n != want:
             # the body is never read, so the stream is out of step: end the connection (the peer's
@@ -106,7 +108,7 @@ class PayloadSocket:
             self.abort()
             raise ValueError(f"recvPayload: message of {n} bytes, the codec's payload is {want}")
         buf = self._recv_exact(n)
-        compressor.validatePayload(buf, d, bits=bits)
+        compressor.validatePayload(buf, d, bits=bits, **kw)
         t = torch.from_numpy(np.frombuffer(buf, dtype=np.uint8))
         return t if device is None else t.to(device)
 

@@ -592,7 +592,9 @@ int flc_unpack(const flc_codec_params* prm, const void* d_payload, int64_t d, fl
  * flc_payload_bytes, header format = the codec's, bad = 0, count = d (dense formats) / <= K with
  * strictly ascending indices < d (SPARSE) / the codec's rank (RANKK), level codes <= s (Q8 / Q16).
  * FLC_OK or FLC_ERR_ARG with the reason in flc_last_error_string.  Host memory only; no device work.
- * (The decode kernels also never index outside the row or the level table, whatever the bytes.)
+ * (The decode kernels also never index outside the row or the level table, whatever the bytes.
+ * A seeded message, below, whose draw block names another d than the call's, or whose count is not
+ * the call's K', contributes nothing: it decodes as the +0 row.)
  * Replaces the trust the reference's transport places in pickle.loads of the peer's reply
  * (model_funcs.py:445-452, comm_socket.py:59-82). */
 int flc_payload_validate(const flc_codec_params* prm, const void* h_payload, int64_t nbytes, int64_t d);
@@ -648,6 +650,54 @@ size_t flc_unpack_reduce_bits_workspace_size(const flc_codec_params* prm, int64_
 int flc_unpack_reduce_bits(const flc_codec_params* prm, const void* d_payloads, int64_t ld_bytes,
                            const void* const* d_payload_ptrs, int64_t n, int64_t d, const float* d_w,
                            float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
+ * Seeded RandK messages (additive to ABI 1.04: detect by symbol): RandK's K' values alone.  With
+ * device draws the index set is a pure function of the client's 64-bit key (flc_device_randk_indices),
+ * so the server redraws it and the message carries no index: the reference's own count of K
+ * components (compressors.py:240-245).
+ *   9 SEEDED  randk, device draws      header {9, count = K', norm = 0, bad = 0}, K' = max(1, min(k, d));
+ *                                      draw block {u32 key_lo, key_hi, d_lo, d_hi}: key =
+ *                                      client_key(seed, client), d the row length the set was drawn
+ *                                      for; then f32 val[K'], 16-B padded with zero bytes
+ * The values are in the sampler's own order: chunk by chunk (4096 elements, ascending), inside chunk
+ * c in draw order t = 0 .. m_c - 1, i.e. the order of flc_device_randk_indices; each is
+ * randk_scale * x[j], flc_encode's bits at j.  All K' are sent: a +-0 value keeps its place and its
+ * sign (SPARSE drops the +0 entries), NaN and inf travel as their bits.
+ * flc_payload_seeded_bytes = 32 + a16(4 K') against SPARSE's 16 + 2 a16(4 K'); d == 0: the two
+ * 16-byte blocks alone.
+ *
+ * flc_pack_seeded is O(K): chunk counts, their scan, one gather (no dense row, no index list);
+ * the client is pat->client0.  flc_unpack_seeded(flc_pack_seeded(x)) == flc_encode(x) and
+ * flc_unpack_reduce_seeded(payloads) == flc_unpack_reduce(the SPARSE payloads of the same rows) ==
+ * flc_encode_reduce(rows), bit for bit.  Arguments as the byte entries': 16-byte aligned payloads,
+ * strided rows (ld_bytes >= flc_payload_seeded_bytes, a multiple of 16) or a device pointer array,
+ * n == 0 zero-fills d_out, d == 0 touches nothing, a refused call writes nothing.
+ * The device entries take the key from the message and compare the message's d and count with the
+ * call's; every count, offset and column is recomputed from the key, so nothing outside the row or
+ * the value list is indexed whatever the bytes are (the rule for a mismatch: above, at
+ * flc_payload_validate).
+ * Every codec but RandK: flc_payload_seeded_format / _bytes and the workspace queries return 0 and
+ * the other entries FLC_ERR_UNSUPPORTED before any launch.  flc_codec_params does not say where the
+ * draws come from: flc_pack_seeded refuses a pattern with given indices (d_randk_idx) the same way,
+ * and a caller in compat mode must not ask for the format.
+ * flc_payload_validate_seeded is host only: size, format, count == K', norm bits == 0, bad == 0,
+ * the draw block's d == d and, with client >= 0, key == client_key(prm->seed, client).
+ * -------------------------------------------------------------------------------------- */
+int flc_payload_seeded_format(const flc_codec_params* prm);
+int64_t flc_payload_seeded_bytes(const flc_codec_params* prm, int64_t d);
+int flc_payload_validate_seeded(const flc_codec_params* prm, const void* h_payload, int64_t nbytes, int64_t d,
+                                int64_t client);
+size_t flc_pack_seeded_workspace_size(const flc_codec_params* prm, int64_t d);
+int flc_pack_seeded(const flc_codec_params* prm, const flc_pattern* pat, const float* d_x, int64_t d,
+                    void* d_payload, void* d_ws, size_t ws_bytes, void* stream);
+size_t flc_unpack_seeded_workspace_size(const flc_codec_params* prm, int64_t d);
+int flc_unpack_seeded(const flc_codec_params* prm, const void* d_payload, int64_t d, float* d_out,
+                      void* d_ws, size_t ws_bytes, void* stream);
+size_t flc_unpack_reduce_seeded_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_unpack_reduce_seeded(const flc_codec_params* prm, const void* d_payloads, int64_t ld_bytes,
+                             const void* const* d_payload_ptrs, int64_t n, int64_t d, const float* d_w,
+                             float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
  * Shifted steps on the wire (additive to ABI 1.04: detect by symbol): the shift codecs' client
