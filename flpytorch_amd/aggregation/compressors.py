@@ -124,6 +124,8 @@ _BITS_ENTRY = {
 }
 # ... and their seeded counterparts (RandK with device draws: values only, FMT_SEEDED)
 _SEEDED_ENTRY = {name: b.replace("_bits", "_seeded") for name, b in _BITS_ENTRY.items()}
+# ... and their sparse level counterparts (the nonzero Q8 codes as per-chunk lists, FMT_SLEV)
+_SLEV_ENTRY = {name: b.replace("_bits", "_slev") for name, b in _BITS_ENTRY.items()}
 
 
 def _gpu_device(x):
@@ -447,13 +449,26 @@ class Compressor:
             return prm
         return self.codec_params(torch.device("cpu"))[0]
 
-    def _wire_entry(self, name, bits, prm=None, seeded=False):
+    def _wire_entry(self, name, bits, prm=None, seeded=False, sparse_levels=False):
         """The C entry ``name`` of the byte formats or, with ``bits``, its bit-packed counterpart
         (FMT_LBITS / FMT_NAT9, include/flcodec.h "Bit-packed messages").  A codec without a bit-packed
         form is refused here, before any size is computed or anything is launched.  ``seeded``: the
         seeded counterpart (FMT_SEEDED, "Seeded RandK messages"), under the same contract: only RandK
-        with ``device_rng`` set has it (the server redraws the index set from the client's key)."""
+        with ``device_rng`` set has it (the server redraws the index set from the client's key).
+        ``sparse_levels``: the sparse level counterpart (FMT_SLEV, "Sparse level messages"), same
+        contract: standard dithering / qsgd / terngrad with s <= 127 only."""
         lib = _lib.load()
+        if sparse_levels:
+            if bits or seeded:
+                raise ValueError(f"{name}: sparse_levels=True with {'bits' if bits else 'seeded'}=True "
+                                 "(a message has one form)")
+            if not hasattr(lib, "flc_pack_slev"):
+                raise NotImplementedError("this library build has no flc_pack_slev")
+            prm = prm if prm is not None else self._host_params()
+            if lib.flc_payload_slev_format(ctypes.byref(prm)) == 0:
+                raise NotImplementedError(f"{name}: this codec has no sparse level wire form "
+                                          "(standard dithering / qsgd / terngrad with s <= 127)")
+            return getattr(lib, _SLEV_ENTRY[name])
         if seeded:
             if bits:
                 raise ValueError(f"{name}: seeded=True with bits=True (a message has one form)")
@@ -472,20 +487,22 @@ class Compressor:
                                       "(natural, or standard dithering / qsgd / terngrad with s <= 63)")
         return getattr(lib, _BITS_ENTRY[name])
 
-    def payloadBytes(self, d=None, bits=False, seeded=False):
+    def payloadBytes(self, d=None, bits=False, seeded=False, sparse_levels=False):
         """Bytes of one row's payload (flc_payload_bytes: 16-B header + body, 16-B padded; ``bits``:
         flc_payload_bits_bytes, 16 + 256 b ceil(d / 2048); ``seeded``: flc_payload_seeded_bytes,
-        32 + 4 K padded to 16)."""
+        32 + 4 K padded to 16; ``sparse_levels``: flc_payload_slev_bytes, the CAPACITY of a sparse level
+        message — its used size depends on the row)."""
         prm = self._host_params()
-        return int(self._wire_entry("flc_payload_bytes", bits, prm, seeded)(ctypes.byref(prm), self._dim(d)))
+        return int(self._wire_entry("flc_payload_bytes", bits, prm, seeded, sparse_levels)(ctypes.byref(prm), self._dim(d)))
 
-    def validatePayload(self, payload, d=None, bits=False, seeded=False, client=None):
+    def validatePayload(self, payload, d=None, bits=False, seeded=False, client=None, sparse_levels=False):
         """Check a message received from a peer before it is decoded (flc_payload_validate, host
         only): its size, header and codes fit this codec and d.  ``payload``: bytes-like, a uint8
         numpy array or a host uint8 tensor.  ``bits``: the bit-packed message
         (flc_payload_validate_bits).  ``seeded``: the seeded RandK message
         (flc_payload_validate_seeded); with ``client`` its key must be that client's under this
-        compressor's seed.  Raises ValueError with the reason."""
+        compressor's seed.  ``sparse_levels``: the sparse level message (flc_payload_validate_slev).
+        Raises ValueError with the reason."""
         if torch.is_tensor(payload):
             if payload.dtype != torch.uint8 or payload.is_cuda:
                 raise TypeError("validatePayload: a host uint8 tensor (or bytes) is expected")
@@ -494,8 +511,8 @@ class Compressor:
             arr = np.frombuffer(payload, dtype=np.uint8)
         prm = self._host_params()
         more = (-1 if client is None else int(client),) if seeded else ()
-        rc = self._wire_entry("flc_payload_validate", bits, prm, seeded)(ctypes.byref(prm), ctypes.c_void_p(arr.ctypes.data),
-                                                                       int(arr.nbytes), self._dim(d), *more)
+        rc = self._wire_entry("flc_payload_validate", bits, prm, seeded, sparse_levels)(
+            ctypes.byref(prm), ctypes.c_void_p(arr.ctypes.data), int(arr.nbytes), self._dim(d), *more)
         _lib.check(rc, "validatePayload")
 
     def _dim(self, d):
@@ -505,11 +522,25 @@ class Compressor:
             raise ValueError("this compressor has no D (identity): pass d")
         return int(d)
 
-    def compressPayload(self, x, out=None, bits=False, seeded=False):
+    def _slev_used(self, payload, d):
+        """Used bytes of a sparse level message on the device: tab[C] read back (one 4-byte copy)."""
+        off = 16 + 4 * ((d + 4095) // 4096)
+        if payload.numel() < off + 4:
+            raise ValueError(f"sparse level payload: {payload.numel()} bytes do not hold the chunk table of d={d}")
+        nnz = int(payload[off:off + 4].cpu().numpy().view(np.uint32)[0])
+        if nnz > d:
+            raise ValueError(f"sparse level payload: {nnz} entries, d={d}")
+        a16 = lambda b: (b + 15) & ~15
+        return 16 + a16(off - 12) + a16(2 * nnz) + a16(nnz)
+
+    def compressPayload(self, x, out=None, bits=False, seeded=False, sparse_levels=False):
         """The message this client would send: flc_pack of compressVector(x) (same pattern, same
         draws), as a uint8 device tensor of payloadBytes() bytes.  ``bits``: the bit-packed message
         (flc_pack_bits, payloadBytes(bits=True) bytes), the same codes at sub-byte width.  ``seeded``:
         RandK's values alone (flc_pack_seeded, payloadBytes(seeded=True) bytes), gathered in O(K).
+        ``sparse_levels``: the nonzero Q8 codes as per-chunk lists (flc_pack_slev), packed into a buffer
+        of payloadBytes(sparse_levels=True) bytes (``out`` when given) and returned as the view of the
+        used length, which tab[C] settles (one 4-byte copy to the host).
         Statistics advance like compressVector."""
         if x.dtype != torch.float32:
             raise TypeError(f"flcodec encodes fp32 only (got {x.dtype})")
@@ -518,34 +549,42 @@ class Compressor:
         d = xd.numel()
         lib = _lib.load()
         prm, keep = self.codec_params(dev)
-        pack = self._wire_entry("flc_pack", bits, prm, seeded)
+        pack = self._wire_entry("flc_pack", bits, prm, seeded, sparse_levels)
         pat = self._pattern(dev, keep)
-        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm, seeded)(ctypes.byref(prm), d))
+        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm, seeded, sparse_levels)(ctypes.byref(prm), d))
         if out is None:
             out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         elif out.numel() < nbytes or out.dtype != torch.uint8 or out.data_ptr() % 16:
             raise ValueError("compressPayload: out must be a 16-byte aligned uint8 tensor of payloadBytes()")
-        ws_bytes = self._wire_entry("flc_pack_workspace_size", bits, prm, seeded)(ctypes.byref(prm), d)
+        ws_bytes = self._wire_entry("flc_pack_workspace_size", bits, prm, seeded, sparse_levels)(ctypes.byref(prm), d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):
             rc = pack(ctypes.byref(prm), ctypes.byref(pat), ctypes.c_void_p(xd.data_ptr()), d,
                       ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
                       _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_pack_seeded" if seeded else ("flc_pack_bits" if bits else "flc_pack"))
+        _lib.check(rc, "flc_pack_slev" if sparse_levels else
+                   ("flc_pack_seeded" if seeded else ("flc_pack_bits" if bits else "flc_pack")))
         self._account(d)
+        if sparse_levels:
+            return out.reshape(-1)[:self._slev_used(out.reshape(-1), d)]
         return out
 
-    def decompressPayload(self, payload, d=None, bits=False, seeded=False):
+    def decompressPayload(self, payload, d=None, bits=False, seeded=False, sparse_levels=False):
         """Dense fp32 row of a payload (flc_unpack; ``bits``: flc_unpack_bits of a bit-packed one;
-        ``seeded``: flc_unpack_seeded of a seeded one): compressVector's output, bit for bit."""
+        ``seeded``: flc_unpack_seeded of a seeded one): compressVector's output, bit for bit.
+        ``sparse_levels``: flc_unpack_slev of a sparse level message — compressVector's output with
+        every zero +0 (the sign of zero does not travel in that form)."""
         dev = _gpu_device(payload)
         d = self._dim(d)
         lib = _lib.load()
         prm, keep = self.codec_params(dev)
         if payload.dtype != torch.uint8:
             raise TypeError(f"decompressPayload: payload must be uint8 (got {payload.dtype})")
-        unpack = self._wire_entry("flc_unpack", bits, prm, seeded)
-        nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm, seeded)(ctypes.byref(prm), d))
+        unpack = self._wire_entry("flc_unpack", bits, prm, seeded, sparse_levels)
+        if sparse_levels:                             # the message's own length, from its tab[C]
+            nbytes = self._slev_used(payload.reshape(-1), d)
+        else:
+            nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm, seeded)(ctypes.byref(prm), d))
         if payload.numel() < nbytes:
             raise ValueError(f"decompressPayload: {payload.numel()} bytes, the payload of d={d} is {nbytes}")
         # a host message (off the network) crosses to the device first; the kernel reads HBM only
@@ -560,7 +599,8 @@ class Compressor:
         with torch.cuda.device(dev):
             rc = unpack(ctypes.byref(prm), ctypes.c_void_p(payload.data_ptr()), d,
                         ctypes.c_void_p(out.data_ptr()), *more, _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_unpack_seeded" if seeded else ("flc_unpack_bits" if bits else "flc_unpack"))
+        _lib.check(rc, "flc_unpack_slev" if sparse_levels else
+                   ("flc_unpack_seeded" if seeded else ("flc_unpack_bits" if bits else "flc_unpack")))
         return out
 
     # -- shift codecs ----------------------------------------------------

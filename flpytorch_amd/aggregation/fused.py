@@ -15,6 +15,7 @@ Pattern sources
               kernels: no host work, no uniform bytes (the benchmark mode).
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -750,14 +751,20 @@ class PayloadReducer:
     same bits; a codec without a bit-packed form is refused with NotImplementedError.
     ``seeded=True``: the payloads are seeded RandK messages (compressPayload(seeded=True)), folded by
     flc_unpack_reduce_seeded — each row's index set redrawn from the key its message carries — to the
-    same bits; anything but RandK with device draws is refused with NotImplementedError."""
+    same bits; anything but RandK with device draws is refused with NotImplementedError.
+    ``sparse_levels=True``: the payloads are sparse level messages (compressPayload(sparse_levels=True)),
+    a list of tensors of unequal used lengths or a strided matrix of capacity rows, folded by
+    flc_unpack_reduce_slev in work proportional to their nonzeros.  The result agrees with the Q8
+    fold up to the sign of zero (every nonzero sum has its bits; a zero sum is +0).  The weights
+    must be finite (ValueError): the dense fold turns 0 * inf into NaN, this one never sees the zero."""
 
-    def __init__(self, compressor: Compressor, device=None, bits=False, seeded=False):
+    def __init__(self, compressor: Compressor, device=None, bits=False, seeded=False, sparse_levels=False):
         _lib.require_gpu()
         self.comp = compressor
         self.device = _device(device)
         self.bits = bool(bits)
         self.seeded = bool(seeded)
+        self.sparse_levels = bool(sparse_levels)
 
     def __call__(self, payloads, d=None, out=None, weights=None, divisor=None):
         """payloads: [N, ld] uint8 device tensor (rows 16-byte aligned, ld % 16 == 0) or a list of
@@ -766,7 +773,11 @@ class PayloadReducer:
         dev = self.device
         d = self.comp._dim(d)
         prm, keep = self.comp.codec_params(dev)
-        fold = self.comp._wire_entry("flc_unpack_reduce", self.bits, prm, self.seeded)
+        fold = self.comp._wire_entry("flc_unpack_reduce", self.bits, prm, self.seeded, self.sparse_levels)
+        if self.sparse_levels and weights is not None:
+            weights = [float(w) for w in weights]
+            if not all(math.isfinite(w) for w in weights):
+                raise ValueError("PayloadReducer(sparse_levels=True): the weights must be finite")
         if torch.is_tensor(payloads) and payloads.dim() == 2:
             n, ld = payloads.shape
             if payloads.stride(1) != 1 or payloads.stride(0) % 16 or payloads.data_ptr() % 16:
@@ -777,18 +788,23 @@ class PayloadReducer:
             for p in payloads:
                 if p.data_ptr() % 16:
                     raise ValueError("payloads must be 16-byte aligned")
+                # (a message's own length is its tab[C]'s: validatePayload checks it on the host)
+                if self.sparse_levels and p.numel() < 16 + ((4 * ((d + 4095) // 4096 + 1) + 15) & ~15):
+                    raise ValueError(f"sparse level payload: {p.numel()} bytes do not hold the chunk table of d={d}")
             base, ldb, ptrs = None, 0, _pointer_table(payloads, dev, keep)
         if out is None:
             out = torch.empty(d, dtype=torch.float32, device=dev)
         w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
-        ws_bytes = self.comp._wire_entry("flc_unpack_reduce_workspace_size", self.bits, prm, self.seeded)(ctypes.byref(prm), n, d)
+        ws_bytes = self.comp._wire_entry("flc_unpack_reduce_workspace_size", self.bits, prm, self.seeded,
+                                         self.sparse_levels)(ctypes.byref(prm), n, d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):
             rc = fold(ctypes.byref(prm), ctypes.c_void_p(base), ldb, ctypes.c_void_p(ptrs), n, d,
                       ctypes.c_void_p(w_ptr), ctypes.c_float(total), ctypes.c_void_p(out.data_ptr()),
                       ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_unpack_reduce_seeded" if self.seeded else
-                   ("flc_unpack_reduce_bits" if self.bits else "flc_unpack_reduce"))
+        _lib.check(rc, "flc_unpack_reduce_slev" if self.sparse_levels else
+                   ("flc_unpack_reduce_seeded" if self.seeded else
+                    ("flc_unpack_reduce_bits" if self.bits else "flc_unpack_reduce")))
         return out
 
 

@@ -800,6 +800,78 @@ extern "C" int flc_unpack_reduce_seeded(const flc_codec_params* prm, const void*
                                     w_total, d_out, d_ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- sparse level messages (wire_slev.hip) ----------------------------------------------------------
+// a codec without the sparse level form: FLC_ERR_UNSUPPORTED before anything else is looked at
+static int slev_codec(const flc_codec_params* prm, const char* me) {
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (!slev_ok(prm)) {
+        set_error("%s: codec %d has no sparse level form (standard dithering / qsgd / terngrad with s <= 127)", me, prm->codec);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    return FLC_OK;
+}
+
+extern "C" int flc_payload_slev_format(const flc_codec_params* prm) {
+    return prm && known(prm->codec) && slev_ok(prm) ? 10 : 0;
+}
+
+extern "C" int64_t flc_payload_slev_bytes(const flc_codec_params* prm, int64_t d) {
+    if (!prm || !known(prm->codec) || !slev_ok(prm) || d < 0) return 0;
+    return slev_used_bytes(d, d);
+}
+
+extern "C" int64_t flc_payload_slev_used(const void* h_payload, int64_t nbytes, int64_t d) {
+    if (d < 0 || nbytes < 0) return 0;
+    return slev_payload_used((const uint8_t*)h_payload, nbytes, d);
+}
+
+extern "C" int flc_payload_validate_slev(const flc_codec_params* prm, const void* h_payload, int64_t nbytes, int64_t d) {
+    const char* me = "flc_payload_validate_slev";
+    if (int rc = slev_codec(prm, me)) return rc;
+    if (d < 0 || nbytes < 0 || (nbytes > 0 && !h_payload)) { set_error("%s: bad payload/nbytes/d", me); return FLC_ERR_ARG; }
+    return slev_payload_validate(prm, (const uint8_t*)h_payload, nbytes, d);
+}
+
+extern "C" size_t flc_pack_slev_workspace_size(const flc_codec_params* prm, int64_t d) {
+    if (!prm || !known(prm->codec) || d < 0) return 0;
+    return slev_pack_workspace(prm, d);
+}
+
+extern "C" int flc_pack_slev(const flc_codec_params* prm, const flc_pattern* pat, const float* d_x, int64_t d,
+                             void* d_payload, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_pack_slev";
+    if (int rc = slev_codec(prm, me)) return rc;
+    if (int rc = bad_params(prm, me)) return rc;
+    if (d < 0 || !d_payload || (d > 0 && !d_x)) { set_error("%s: bad x/payload/d", me); return FLC_ERR_ARG; }
+    return slev_pack_run(prm, pat, d_x, d, (char*)d_payload, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int flc_unpack_slev(const flc_codec_params* prm, const void* d_payload, int64_t d, float* d_out, void* stream) {
+    const char* me = "flc_unpack_slev";
+    if (int rc = slev_codec(prm, me)) return rc;
+    if (d < 0 || (d > 0 && (!d_payload || !d_out))) { set_error("%s: bad payload/out/d", me); return FLC_ERR_ARG; }
+    return slev_unpack_run(prm, (const char*)d_payload, d, d_out, (hipStream_t)stream);
+}
+
+extern "C" size_t flc_unpack_reduce_slev_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    (void)prm; (void)n; (void)d;
+    return 0;                                       // the fold keeps its tiles in LDS
+}
+
+extern "C" int flc_unpack_reduce_slev(const flc_codec_params* prm, const void* d_payloads, int64_t ld_bytes,
+                                      const void* const* d_payload_ptrs, int64_t n, int64_t d, const float* d_w,
+                                      float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_unpack_reduce_slev";
+    (void)d_ws; (void)ws_bytes;
+    if (int rc = slev_codec(prm, me)) return rc;
+    if (n < 0 || d < 0 || (d > 0 && !d_out)) { set_error("%s: bad n/d/out", me); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) return too_many(me, n, "payloads", FLC_ERR_UNSUPPORTED);
+    if (n > 0 && d > 0 && !d_payloads && !d_payload_ptrs) { set_error("%s: no payloads", me); return FLC_ERR_ARG; }
+    if (d_payloads && ld_bytes < slev_used_bytes(d, d)) { set_error("%s: ld_bytes < the capacity flc_payload_slev_bytes", me); return FLC_ERR_ARG; }
+    return slev_unpack_reduce_run(prm, (const char*)d_payloads, ld_bytes, (const char* const*)d_payload_ptrs, n, d, d_w,
+                                  w_total, d_out, (hipStream_t)stream);
+}
+
 // ---- shifted steps on the wire (wire_shift.hip) ----------------------------------------------------
 extern "C" size_t flc_pack_shift_workspace_size(const flc_codec_params* prm, int64_t d) {
     if (!prm || !known(prm->codec) || prm->codec == FLC_RANK_K || d < 0) return 0;

@@ -22,6 +22,7 @@
 #include "codec_ops.hpp"
 #include "wire_bits.hpp"
 #include "wire_codes.hpp"
+#include "wire_slev.hpp"
 
 namespace flc {
 
@@ -1378,6 +1379,10 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
         if (ca && ca->bits) {                        // flc_pack_bits: the bit-packed form (wire_bits.hip)
             if constexpr (BitsOp<decltype(op)>::value) return launch_code_bits(src.base, d, op, levels, s, *ca, st);
             else { set_error("ew_run: codec %d has no bit-packed form", codec); return FLC_ERR_UNSUPPORTED; }
+        }
+        if (ca && ca->sl_cnt) {                      // flc_pack_slev: the sparse level form (wire_slev.hip)
+            if constexpr (SlevOp<decltype(op)>::value) return launch_code_slev(src.base, d, op, levels, s, *ca, st);
+            else { set_error("ew_run: codec %d has no sparse level form", codec); return FLC_ERR_UNSUPPORTED; }
         }
         if (ca) return launch_code(src.base, d, op, levels, s, *ca, st);
         if (dense) return launch_dense(src.base, d, op, levels, s, out, st);

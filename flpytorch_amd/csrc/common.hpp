@@ -168,6 +168,11 @@ struct CodeArgs {
     int s;
     const float* pn;     // device norm the codes are relative to (dithering)
     int bits = 0;        // > 0: the bit-packed form of that many bits per code (wire_bits.hip); fmt unused
+    // non-null: the sparse level form (wire_slev.hip), staged per 4096-element chunk c: its count and
+    // its (chunk-local index, Q8 code) runs at sl_idx / sl_code + c * 4096; fmt unused
+    uint32_t* sl_cnt = nullptr;
+    uint16_t* sl_idx = nullptr;
+    uint8_t* sl_code = nullptr;
 };
 int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool vec, int64_t n, int64_t d,
            const float* pnorm_in, float* pnorm_out, bool dense, float* out, const float* w, float wt, void* ws,
@@ -288,6 +293,18 @@ int seeded_unpack_run(const flc_codec_params* prm, const char* payload, int64_t 
                       hipStream_t st);
 int seeded_unpack_reduce_run(const flc_codec_params* prm, const char* base, int64_t ld, const char* const* ptrs, int64_t n,
                              int64_t d, const float* w, float wt, float* out, void* ws, size_t ws_bytes, hipStream_t st);
+// the sparse level message (wire_slev.hip, FMT_SLEV): flc_pack_slev & co.  slev_ok: the codec has the
+// form (standard dithering / QSGD / TernGrad with s <= 127, the specs whose byte format is Q8)
+bool slev_ok(const flc_codec_params* prm);
+int64_t slev_used_bytes(int64_t d, int64_t nnz);
+int64_t slev_payload_used(const uint8_t* p, int64_t nbytes, int64_t d);
+int slev_payload_validate(const flc_codec_params* prm, const uint8_t* p, int64_t nbytes, int64_t d);
+size_t slev_pack_workspace(const flc_codec_params* prm, int64_t d);
+int slev_pack_run(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, char* payload, void* ws,
+                  size_t ws_bytes, hipStream_t st);
+int slev_unpack_run(const flc_codec_params* prm, const char* payload, int64_t d, float* out, hipStream_t st);
+int slev_unpack_reduce_run(const flc_codec_params* prm, const char* base, int64_t ld, const char* const* ptrs, int64_t n,
+                           int64_t d, const float* w, float wt, float* out, hipStream_t st);
 // Row g's boundary of G row groups whose last group is `lastpct` % of the others' size (the last
 // group's tail is the exposed one): rows [group_row(n, G, g), group_row(n, G, g + 1)).
 // lastpct is clamped to [1, 100]: 0 or less would leave the last group (the one whose fold writes

@@ -10,7 +10,8 @@ namespace flc {
 
 enum { FMT_F32 = 1, FMT_Q8 = 2, FMT_Q16 = 3, FMT_NAT16 = 4, FMT_SPARSE = 5, FMT_RANKK = 6,
        FMT_LBITS = 7, FMT_NAT9 = 8,        // the bit-packed forms (wire_bits.hip)
-       FMT_SEEDED = 9 };                   // RandK values only, the set redrawn from the key (wire_seeded.hip)
+       FMT_SEEDED = 9,                     // RandK values only, the set redrawn from the key (wire_seeded.hip)
+       FMT_SLEV = 10 };                    // the nonzero Q8 codes as per-chunk lists (wire_slev.hip)
 struct PayloadHeader {
     uint32_t fmt, count;
     float norm;

@@ -700,6 +700,65 @@ int flc_unpack_reduce_seeded(const flc_codec_params* prm, const void* d_payloads
                              float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Sparse level messages (additive to ABI 1.04: detect by symbol): the Q8 message as lists of its
+ * nonzero codes.  A standard dithering / QSGD / TernGrad element is nonzero only when it reaches
+ * level 1 or its draw goes up, so E[nonzeros] <= s sqrt(d).
+ *   10 SLEV  std dithering / qsgd / terngrad, s <= 127 (the specs whose byte format is Q8)
+ *     header  16 B               {10, count = d, norm, bad}                 C = ceil(d / 4096)
+ *     tab     a16(4 (C + 1)) B   u32 exclusive offsets of the chunks' entries; tab[C] = nnz
+ *     idx     a16(2 nnz) B       u16 chunk-local index (0..4095), ascending inside a chunk
+ *     code    a16(nnz) B         u8, Q8's code of that element (sign << 7 | level index)
+ * a16 rounds up to 16; padding bytes are zero.  The used size 16 + a16(4 (C + 1)) + a16(2 nnz) +
+ * a16(nnz) is data-dependent and computable from tab[C] alone (flc_payload_slev_used, host; 0 when
+ * nbytes does not reach tab[C] or tab[C] > d); the capacity a caller provides is the size at
+ * nnz = d (flc_payload_slev_bytes).
+ * Element j is listed iff its encoded value v_j (flc_encode's) is neither +0 nor -0,
+ * (bits(v_j) << 1) != 0, with the code flc_pack gives it.  NaN outputs are kept: under a non-finite
+ * norm the code is sign | 0, which decodes to NaN, and only there is level index 0 legal.
+ *
+ * THE SIGN OF ZERO DOES NOT TRAVEL.  About half of a dense QSGD output is -0 (negative elements at
+ * level 0); carrying it would cost a bit per element, more than the rest of the message.  The
+ * contract is on values:
+ *     canon(a) = the fp32 array a + 0.0f viewed as uint32 (-0 becomes +0, every other value keeps
+ *     its bits, NaN compared by position); two results agree when their canon are equal.
+ * flc_unpack_slev(flc_pack_slev(x)) agrees with flc_unpack(flc_pack(x)), and flc_unpack_reduce_slev
+ * agrees with flc_unpack_reduce of the Q8 payloads of the same rows: the fold adds a row's entries
+ * in row order, so every nonzero sum carries the dense fold's bits.
+ * The fold's weights must be finite: the dense fold turns 0 * inf into NaN where this one never
+ * sees the zero.  d_w is device memory and is not inspected; a caller with host weights checks them.
+ *
+ * flc_pack_slev: the norm pass, one pass over x that stages each chunk's listed (index, code) runs
+ * (no dense message row), the scan of the chunk counts into tab and one gather: 8 d bytes of row
+ * reads plus about 6 nnz of list traffic; d_payload holds flc_payload_slev_bytes, bytes past the
+ * used size are not written.  flc_unpack_reduce_slev takes strided rows at capacity
+ * (ld_bytes >= flc_payload_slev_bytes, a multiple of 16) or a device pointer array of messages of
+ * unequal used lengths; n == 0 zero-fills d_out; a refused call writes nothing.
+ * Whatever the bytes, the device entries index nothing outside the row, the level table or a
+ * capacity-sized message: idx & 4095, a level index past s reads the top level, entry ranges are
+ * clamped to [0, min(tab[C], d)].  A message in a buffer shorter than its tab[C] claims is caught
+ * by flc_payload_validate_slev (host only): format, count == d, nbytes >= used(tab[C]), tab[C] <= d,
+ * tab[0] == 0, tab non-decreasing with each chunk's count at most its length, indices strictly
+ * ascending and below the chunk's length, level index in 1..s (0 only under a non-finite norm),
+ * zero padding, bad == 0.
+ * Every other codec (s > 127, natural, natural dithering, randk / topk, rank_k, ident, lazy):
+ * flc_payload_slev_format / _bytes and the workspace queries return 0 and the other entries
+ * FLC_ERR_UNSUPPORTED before any launch.
+ * -------------------------------------------------------------------------------------- */
+int flc_payload_slev_format(const flc_codec_params* prm);
+int64_t flc_payload_slev_bytes(const flc_codec_params* prm, int64_t d);
+int64_t flc_payload_slev_used(const void* h_payload, int64_t nbytes, int64_t d);
+int flc_payload_validate_slev(const flc_codec_params* prm, const void* h_payload, int64_t nbytes, int64_t d);
+size_t flc_pack_slev_workspace_size(const flc_codec_params* prm, int64_t d);
+int flc_pack_slev(const flc_codec_params* prm, const flc_pattern* pat, const float* d_x, int64_t d,
+                  void* d_payload, void* d_ws, size_t ws_bytes, void* stream);
+int flc_unpack_slev(const flc_codec_params* prm, const void* d_payload, int64_t d, float* d_out,
+                    void* stream);
+size_t flc_unpack_reduce_slev_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_unpack_reduce_slev(const flc_codec_params* prm, const void* d_payloads, int64_t ld_bytes,
+                           const void* const* d_payload_ptrs, int64_t n, int64_t d, const float* d_w,
+                           float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * Shifted steps on the wire (additive to ABI 1.04: detect by symbol): the shift codecs' client
  * step e = C(a - b) that EMITS its message, and the server fold of n such messages with the
  * shifted round's semantics.
