@@ -60,6 +60,7 @@ EXPORTS = [
     "flc_payload_slev_format", "flc_payload_slev_bytes", "flc_payload_slev_used", "flc_payload_validate_slev",
     "flc_pack_slev_workspace_size", "flc_pack_slev", "flc_unpack_slev",
     "flc_unpack_reduce_slev_workspace_size", "flc_unpack_reduce_slev",
+    "flc_unpack_reduce_factored_workspace_size", "flc_unpack_reduce_factored",
     "flc_pack_shift_workspace_size", "flc_pack_shift",
     "flc_unpack_shift_reduce_workspace_size", "flc_unpack_shift_reduce",
     "flc_unpack_shift_reduce_sparse_workspace_size", "flc_unpack_shift_reduce_sparse",
@@ -336,6 +337,10 @@ def _bind(lib):
         lib.flc_unpack_reduce_slev_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
         lib.flc_unpack_reduce_slev_workspace_size.restype = sz
         lib.flc_unpack_reduce_slev.argtypes = [P(FlcCodecParams), vp, i64, vp, i64, i64, vp, f32, vp, vp, sz, vp]
+    if hasattr(lib, "flc_unpack_reduce_factored"):  # (absent from A/B builds of older revisions)
+        lib.flc_unpack_reduce_factored_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_unpack_reduce_factored_workspace_size.restype = sz
+        lib.flc_unpack_reduce_factored.argtypes = [P(FlcCodecParams), vp, i64, vp, i64, i64, vp, f32, vp, vp, sz, vp]
     lib.flc_combine_workspace_size.argtypes = [vp, i64, i32]
     lib.flc_combine_workspace_size.restype = sz
     lib.flc_combine_partials.argtypes = [vp, vp, i64, f32, i32, vp, sz, vp]
@@ -386,7 +391,7 @@ def _bind(lib):
                         "flc_payload_seeded_bytes", "flc_pack_seeded_workspace_size", "flc_unpack_seeded_workspace_size",
                         "flc_unpack_reduce_seeded_workspace_size",
                         "flc_payload_slev_bytes", "flc_payload_slev_used", "flc_pack_slev_workspace_size",
-                        "flc_unpack_reduce_slev_workspace_size",
+                        "flc_unpack_reduce_slev_workspace_size", "flc_unpack_reduce_factored_workspace_size",
                         "flc_combine_blocks_workspace_size", "flc_device_randk_counts_workspace_size",
                         "flc_norm2_torch_cpu_workspace_size"):
             getattr(lib, name).restype = i32

@@ -126,6 +126,9 @@ _BITS_ENTRY = {
 _SEEDED_ENTRY = {name: b.replace("_bits", "_seeded") for name, b in _BITS_ENTRY.items()}
 # ... and their sparse level counterparts (the nonzero Q8 codes as per-chunk lists, FMT_SLEV)
 _SLEV_ENTRY = {name: b.replace("_bits", "_slev") for name, b in _BITS_ENTRY.items()}
+# ... and the Rank-K fold from the factor blocks (the byte-format message, folded by one GEMM kernel)
+_FACTORED_ENTRY = {"flc_unpack_reduce_workspace_size": "flc_unpack_reduce_factored_workspace_size",
+                   "flc_unpack_reduce": "flc_unpack_reduce_factored"}
 
 
 def _gpu_device(x):
@@ -449,15 +452,27 @@ class Compressor:
             return prm
         return self.codec_params(torch.device("cpu"))[0]
 
-    def _wire_entry(self, name, bits, prm=None, seeded=False, sparse_levels=False):
+    def _wire_entry(self, name, bits, prm=None, seeded=False, sparse_levels=False, factored=False):
         """The C entry ``name`` of the byte formats or, with ``bits``, its bit-packed counterpart
         (FMT_LBITS / FMT_NAT9, include/flcodec.h "Bit-packed messages").  A codec without a bit-packed
         form is refused here, before any size is computed or anything is launched.  ``seeded``: the
         seeded counterpart (FMT_SEEDED, "Seeded RandK messages"), under the same contract: only RandK
         with ``device_rng`` set has it (the server redraws the index set from the client's key).
         ``sparse_levels``: the sparse level counterpart (FMT_SLEV, "Sparse level messages"), same
-        contract: standard dithering / qsgd / terngrad with s <= 127 only."""
+        contract: standard dithering / qsgd / terngrad with s <= 127 only.
+        ``factored``: the server fold of Rank-K messages from their factor blocks
+        (flc_unpack_reduce_factored, "Rank-K fold from the factor payloads"): the fold entries only,
+        the message itself is the byte format's; Rank-K only."""
         lib = _lib.load()
+        if factored:
+            other = "bits" if bits else "seeded" if seeded else "sparse_levels" if sparse_levels else None
+            if other:
+                raise ValueError(f"{name}: factored=True with {other}=True (a message has one form)")
+            if not hasattr(lib, "flc_unpack_reduce_factored"):
+                raise NotImplementedError("this library build has no flc_unpack_reduce_factored")
+            if self.compressorType != CompressorType.RANK_K_COMPRESSOR:
+                raise NotImplementedError(f"{name}: only Rank-K messages carry factor blocks to fold")
+            return getattr(lib, _FACTORED_ENTRY[name])
         if sparse_levels:
             if bits or seeded:
                 raise ValueError(f"{name}: sparse_levels=True with {'bits' if bits else 'seeded'}=True "

@@ -756,15 +756,26 @@ class PayloadReducer:
     a list of tensors of unequal used lengths or a strided matrix of capacity rows, folded by
     flc_unpack_reduce_slev in work proportional to their nonzeros.  The result agrees with the Q8
     fold up to the sign of zero (every nonzero sum has its bits; a zero sum is +0).  The weights
-    must be finite (ValueError): the dense fold turns 0 * inf into NaN, this one never sees the zero."""
+    must be finite (ValueError): the dense fold turns 0 * inf into NaN, this one never sees the zero.
+    ``factored=True`` (Rank-K only): the payloads are the messages of compressPayload(x) as they are,
+    folded from their factor blocks by flc_unpack_reduce_factored — one matrix-instruction GEMM over
+    the message bodies, no dense rows and no workspace.  The weight goes into the factor, so the result
+    is not flc_unpack_reduce's bits: both are within (n K' + 4) 2^-24 sum_i |w_i| |U'_i| |(SV)_i| / |sum(w)|
+    of the exact fold of the factors.  It is the same bits from call to call and for a strided matrix
+    and a list of payloads.  Any other codec, or a keyword of another form beside it (ValueError), is
+    refused when the reducer is made."""
 
-    def __init__(self, compressor: Compressor, device=None, bits=False, seeded=False, sparse_levels=False):
+    def __init__(self, compressor: Compressor, device=None, bits=False, seeded=False, sparse_levels=False,
+                 factored=False):
         _lib.require_gpu()
         self.comp = compressor
         self.device = _device(device)
         self.bits = bool(bits)
         self.seeded = bool(seeded)
         self.sparse_levels = bool(sparse_levels)
+        self.factored = bool(factored)
+        if self.factored:                                       # the refusals, before any message is seen
+            compressor._wire_entry("flc_unpack_reduce", self.bits, None, self.seeded, self.sparse_levels, True)
 
     def __call__(self, payloads, d=None, out=None, weights=None, divisor=None):
         """payloads: [N, ld] uint8 device tensor (rows 16-byte aligned, ld % 16 == 0) or a list of
@@ -773,7 +784,7 @@ class PayloadReducer:
         dev = self.device
         d = self.comp._dim(d)
         prm, keep = self.comp.codec_params(dev)
-        fold = self.comp._wire_entry("flc_unpack_reduce", self.bits, prm, self.seeded, self.sparse_levels)
+        fold = self.comp._wire_entry("flc_unpack_reduce", self.bits, prm, self.seeded, self.sparse_levels, self.factored)
         if self.sparse_levels and weights is not None:
             weights = [float(w) for w in weights]
             if not all(math.isfinite(w) for w in weights):
@@ -796,15 +807,16 @@ class PayloadReducer:
             out = torch.empty(d, dtype=torch.float32, device=dev)
         w_ptr, total = _fold_weights(weights, n, dev, keep, divisor)
         ws_bytes = self.comp._wire_entry("flc_unpack_reduce_workspace_size", self.bits, prm, self.seeded,
-                                         self.sparse_levels)(ctypes.byref(prm), n, d)
+                                         self.sparse_levels, self.factored)(ctypes.byref(prm), n, d)
         ws = _lib.WORKSPACE.get(dev, ws_bytes)
         with torch.cuda.device(dev):
             rc = fold(ctypes.byref(prm), ctypes.c_void_p(base), ldb, ctypes.c_void_p(ptrs), n, d,
                       ctypes.c_void_p(w_ptr), ctypes.c_float(total), ctypes.c_void_p(out.data_ptr()),
                       ctypes.c_void_p(ws.data_ptr()), ws.numel(), _lib.stream_ptr(dev))
-        _lib.check(rc, "flc_unpack_reduce_slev" if self.sparse_levels else
-                   ("flc_unpack_reduce_seeded" if self.seeded else
-                    ("flc_unpack_reduce_bits" if self.bits else "flc_unpack_reduce")))
+        _lib.check(rc, "flc_unpack_reduce_factored" if self.factored else
+                   ("flc_unpack_reduce_slev" if self.sparse_levels else
+                    ("flc_unpack_reduce_seeded" if self.seeded else
+                     ("flc_unpack_reduce_bits" if self.bits else "flc_unpack_reduce"))))
         return out
 
 

@@ -872,6 +872,30 @@ extern "C" int flc_unpack_reduce_slev(const flc_codec_params* prm, const void* d
                                   w_total, d_out, (hipStream_t)stream);
 }
 
+// ---- Rank-K fold from the factor payloads (rank_k_fold.hip) -----------------------------------------
+extern "C" size_t flc_unpack_reduce_factored_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    (void)prm; (void)n; (void)d;
+    return 0;                                       // the messages are read in place, the tiles live in registers
+}
+
+extern "C" int flc_unpack_reduce_factored(const flc_codec_params* prm, const void* d_payloads, int64_t ld_bytes,
+                                          const void* const* d_payload_ptrs, int64_t n, int64_t d, const float* d_w,
+                                          float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream) {
+    const char* me = "flc_unpack_reduce_factored";
+    (void)d_ws; (void)ws_bytes;
+    if (!prm || !known(prm->codec)) { set_error("%s: unknown codec", me); return FLC_ERR_UNSUPPORTED; }
+    if (prm->codec != FLC_RANK_K) {
+        set_error("%s: codec %d has no factor payloads (Rank-K only)", me, prm->codec);
+        return FLC_ERR_UNSUPPORTED;
+    }
+    if (n < 0 || d < 0 || (d > 0 && !d_out)) { set_error("%s: bad n/d/out", me); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) return too_many(me, n, "payloads", FLC_ERR_UNSUPPORTED);
+    if (n > 0 && d > 0 && !d_payloads && !d_payload_ptrs) { set_error("%s: no payloads", me); return FLC_ERR_ARG; }
+    if (d_payloads && ld_bytes < payload_bytes(prm, d)) { set_error("%s: ld_bytes < payload size", me); return FLC_ERR_ARG; }
+    return rk_fold_run(prm, (const char*)d_payloads, ld_bytes, (const char* const*)d_payload_ptrs, n, d, d_w, w_total,
+                       d_out, (hipStream_t)stream);
+}
+
 // ---- shifted steps on the wire (wire_shift.hip) ----------------------------------------------------
 extern "C" size_t flc_pack_shift_workspace_size(const flc_codec_params* prm, int64_t d) {
     if (!prm || !known(prm->codec) || prm->codec == FLC_RANK_K || d < 0) return 0;

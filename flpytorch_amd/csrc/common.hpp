@@ -213,6 +213,11 @@ int rk_unpack1(const flc_codec_params* prm, const float* body, int64_t d, float*
 int rk_unpack_reduce(const flc_codec_params* prm, const char* base, int64_t ld, const char* const* ptrs, int64_t n,
                      int64_t d, const float* w, float wt, float* out, bool reduce, void* wsp, size_t ws_bytes,
                      hipStream_t st);
+// the Rank-K fold from the factor payloads in place (rank_k_fold.hip, flc_unpack_reduce_factored):
+// rk_dims is the body's geometry (A, B, K' and the float offset of the S V'^T block); no workspace
+void rk_dims(const flc_codec_params* prm, int64_t d, int64_t* A, int64_t* B, int64_t* K, int64_t* uoff);
+int rk_fold_run(const flc_codec_params* prm, const char* base, int64_t ld, const char* const* ptrs, int64_t n, int64_t d,
+                const float* w, float wt, float* out, hipStream_t st);
 int payload_format(const flc_codec_params* prm);
 int payload_validate(const flc_codec_params* prm, const uint8_t* p, int64_t nbytes, int64_t d);
 size_t pack_workspace(const flc_codec_params* prm, int64_t d);

@@ -214,6 +214,11 @@ int rk_run(const flc_codec_params* prm, RowSrc rows, int64_t n, int64_t d, bool 
 // ---- wire format (wire.hip FMT_RANKK): the payload body is one row's factor block ----------------
 int64_t rk_payload_floats(const flc_codec_params* prm, int64_t d) { return rk_block(rk_shape(d, prm->k)); }
 int64_t rk_rank(const flc_codec_params* prm, int64_t d) { return rk_shape(d, prm->k).K; }
+// the factor block's geometry for a reader of the body in place (rank_k_fold.hip)
+void rk_dims(const flc_codec_params* prm, int64_t d, int64_t* A, int64_t* B, int64_t* K, int64_t* uoff) {
+    const RkShape sh = rk_shape(d, prm->k);
+    *A = sh.A; *B = sh.B; *K = sh.K; *uoff = rk_uoff(sh);
+}
 
 __global__ void k_rk_gather_blocks(const char* __restrict__ base, int64_t ld, const char* const* __restrict__ ptrs,
                                    int64_t n, int64_t per, float* __restrict__ blk) {

@@ -759,6 +759,34 @@ int flc_unpack_reduce_slev(const flc_codec_params* prm, const void* d_payloads, 
                            float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Rank-K fold from the factor payloads (additive to ABI 1.04: detect by symbol).  The messages are
+ * flc_pack's RANKK payloads (format 6), unchanged.  Their fold is one matrix product,
+ *     out (B x A column-major = the row-major A x B result)
+ *         = [U'_0 | U'_1 | ...] (B x nK')  [w_0 (SV)_0 ; w_1 (SV)_1 ; ...] (nK' x A)  / w_total,
+ * whose operands are the message bodies in place.  flc_unpack_reduce_factored runs it as one fp32
+ * matrix-instruction kernel (k_rk_fold): about 4 n K' (A + B) + 4 D bytes and 2 D n K' flops, where
+ * flc_unpack_reduce reconstructs n dense rows (about 8 n D + 4 D bytes and an n D-float workspace).
+ * No rocBLAS call, no workspace (the size query returns 0; d_ws may be null).
+ *
+ * Value: element (a, b) is ((sum over i = 0..n-1, k = 0..K'-1 of (w_i (SV)_i[k][a]) U'_i[b][k])) /
+ * w_total, rows in client order and k ascending, fp32; without weights no multiply by w_i happens.
+ * The order is fixed, so the result has the same bits from run to run and for strided rows and a
+ * pointer array.  It is NOT flc_unpack_reduce's bits: that fold rounds each row's product first and
+ * weights it afterwards.  Both are within (n K' + 4) 2^-24 sum_i |w_i| |U'_i| |(SV)_i| / |w_total| of
+ * the exact fold of the same factors.
+ * Arguments as flc_unpack_reduce's: 16-byte aligned payloads, strided rows (ld_bytes >=
+ * flc_payload_bytes, a multiple of 16) or a device pointer array; n == 0 zero-fills d_out, d == 0
+ * touches nothing, a refused call writes nothing.  Every index comes from the codec and d, none from
+ * a message: nothing outside flc_payload_bytes of a message is read whatever its bytes are, and
+ * flc_payload_validate (host) is the check of its header.  Every codec but Rank-K:
+ * FLC_ERR_UNSUPPORTED before any launch, and the size query returns 0.
+ * -------------------------------------------------------------------------------------- */
+size_t flc_unpack_reduce_factored_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_unpack_reduce_factored(const flc_codec_params* prm, const void* d_payloads, int64_t ld_bytes,
+                               const void* const* d_payload_ptrs, int64_t n, int64_t d, const float* d_w,
+                               float w_total, float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * Shifted steps on the wire (additive to ABI 1.04: detect by symbol): the shift codecs' client
  * step e = C(a - b) that EMITS its message, and the server fold of n such messages with the
  * shifted round's semantics.
