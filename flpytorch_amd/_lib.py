@@ -64,6 +64,8 @@ EXPORTS = [
     "flc_pack_shift_workspace_size", "flc_pack_shift",
     "flc_unpack_shift_reduce_workspace_size", "flc_unpack_shift_reduce",
     "flc_unpack_shift_reduce_sparse_workspace_size", "flc_unpack_shift_reduce_sparse",
+    "flc_pack_shift_bits_workspace_size", "flc_pack_shift_bits",
+    "flc_unpack_shift_reduce_bits_workspace_size", "flc_unpack_shift_reduce_bits",
     "flc_combine_workspace_size", "flc_combine_partials",
     "flc_combine_blocks_workspace_size", "flc_combine_blocks",
     "flc_mt_choice", "flc_mt_rand", "flc_mt_randint31",
@@ -298,6 +300,13 @@ def _bind(lib):
         lib.flc_unpack_shift_reduce_sparse_workspace_size.restype = sz
         lib.flc_unpack_shift_reduce_sparse.argtypes = [P(FlcCodecParams), P(FlcPayloadRows), P(FlcRowMap), i64, i64, vp, f32,
                                                        vp, vp, sz, vp]
+    if hasattr(lib, "flc_pack_shift_bits"):         # (absent from A/B builds of older revisions)
+        lib.flc_pack_shift_bits_workspace_size.argtypes = [P(FlcCodecParams), i64]
+        lib.flc_pack_shift_bits_workspace_size.restype = sz
+        lib.flc_pack_shift_bits.argtypes = list(lib.flc_pack_shift.argtypes)
+        lib.flc_unpack_shift_reduce_bits_workspace_size.argtypes = [P(FlcCodecParams), i64, i64]
+        lib.flc_unpack_shift_reduce_bits_workspace_size.restype = sz
+        lib.flc_unpack_shift_reduce_bits.argtypes = list(lib.flc_unpack_shift_reduce.argtypes)
     if hasattr(lib, "flc_pack_bits"):               # (absent from A/B builds of older revisions)
         lib.flc_payload_bits_format.argtypes = [P(FlcCodecParams)]
         lib.flc_payload_bits_bytes.argtypes = [P(FlcCodecParams), i64]
@@ -385,6 +394,7 @@ def _bind(lib):
                         "flc_frecon_reduce_workspace_size", "flc_payload_bytes", "flc_pack_workspace_size",
                         "flc_pack_shift_workspace_size", "flc_unpack_shift_reduce_workspace_size",
                         "flc_unpack_shift_reduce_sparse_workspace_size",
+                        "flc_pack_shift_bits_workspace_size", "flc_unpack_shift_reduce_bits_workspace_size",
                         "flc_unpack_reduce_workspace_size", "flc_combine_workspace_size",
                         "flc_payload_bits_bytes", "flc_pack_bits_workspace_size",
                         "flc_unpack_reduce_bits_workspace_size",

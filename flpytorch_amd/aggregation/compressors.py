@@ -633,22 +633,35 @@ class Compressor:
         return msg, hout
 
     def compressShiftPayload(self, a, b, *, scale=1.0, base=None, out=None, alpha=None, shift=None, shift_out=None,
-                             message=False, payload_out=None):
+                             message=False, payload_out=None, bits=False):
         """``compressShift`` that also emits the message this client sends (flc_pack_shift): the payload
         of ``compressVector(a - b)`` — byte for byte ``compressPayload(a - b)`` under the same pattern,
         so ``decompressPayload(payload)`` is the compressed difference — written in the pass that
         forms ``base + C(a - b) * scale`` and ``shift + alpha * C(a - b)``.  Both of those are optional
         here (``message`` defaults to False; MARINA's client needs the payload only).  ``payload_out``:
         a 16-byte aligned uint8 device tensor of ``payloadBytes()`` bytes that overlaps no operand.
-        Returns ``(payload, msg, shift_out)``; statistics advance like ``compressShift``."""
+        Returns ``(payload, msg, shift_out)``; statistics advance like ``compressShift``.
+        ``bits``: the message in its bit-packed form (flc_pack_shift_bits, ``payloadBytes(bits=True)``
+        bytes, byte for byte ``compressPayload(a - b, bits=True)``), packed in registers by the same
+        pass; ``msg`` and ``shift_out`` keep their bits.  A codec without a bit-packed form is refused
+        with NotImplementedError before any operand is looked at; there is no fallback to the bytes."""
         if not hasattr(_lib.load(), "flc_pack_shift"):
             raise NotImplementedError("this library build has no flc_pack_shift")
+        if bits:
+            self._shift_bits_entry("flc_pack_shift_bits")
         msg, hout, payload = self._shift("compressShiftPayload", a, b, scale, base, out, alpha, shift, shift_out,
-                                         message or out is not None, None, True, payload_out)
+                                         message or out is not None, None, True, payload_out, bool(bits))
         return payload, msg, hout
 
+    def _shift_bits_entry(self, name):
+        """The refusals of the bit-packed shifted steps, host only: a library build without ``name``,
+        or a codec without a bit-packed form (``_wire_entry``) — NotImplementedError either way."""
+        if not hasattr(_lib.load(), name):
+            raise NotImplementedError(f"this library build has no {name}")
+        self._wire_entry("flc_payload_bytes", True)
+
     def _shift(self, who, a, b, scale, base, out, alpha, shift, shift_out, message, pnorm_out, pack=False,
-               payload_out=None):
+               payload_out=None, bits=False):
         for name, v in (("a", a), ("b", b), ("base", base), ("shift", shift), ("out", out),
                         ("shift_out", shift_out)):
             if v is not None and (v.dtype != torch.float32 or not v.is_cuda):
@@ -691,7 +704,7 @@ class Compressor:
         vp = ctypes.c_void_p
         payload = None
         if pack:
-            nbytes = int(lib.flc_payload_bytes(ctypes.byref(prm), d))
+            nbytes = int(self._wire_entry("flc_payload_bytes", bits, prm)(ctypes.byref(prm), d))
             if payload_out is None:
                 payload = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             elif (payload_out.numel() < nbytes or payload_out.dtype != torch.uint8 or not payload_out.is_cuda
@@ -701,7 +714,7 @@ class Compressor:
             else:
                 payload = payload_out
         # the two entries differ in one argument: the payload to write, or the norm to report
-        entry = "flc_pack_shift" if pack else "flc_encode_shift"
+        entry = ("flc_pack_shift_bits" if bits else "flc_pack_shift") if pack else "flc_encode_shift"
         ws = _lib.WORKSPACE.get(dev, getattr(lib, entry + "_workspace_size")(ctypes.byref(prm), d))
 
         def ptr(v):
@@ -717,17 +730,20 @@ class Compressor:
         return (msg.view(a.shape) if msg is not None else None,
                 hout.view(shift.shape) if hout is not None else None, payload)
 
-    def decompressShiftPayload(self, payload, d=None, *, scale=1.0, base=None, out=None):
+    def decompressShiftPayload(self, payload, d=None, *, scale=1.0, base=None, out=None, bits=False):
         """The one-row server step of a shifted message: ``base + decompressPayload(payload) * scale``
         (``decompressPayload(payload) * scale`` without a base), fp32 op for op — the n = 1 fold of
         flc_unpack_shift_reduce with divisor 1.  ``out`` may be ``base`` (EF21's mirror in place).  A
-        host payload (off the network) crosses to the device first, as in ``decompressPayload``."""
+        host payload (off the network) crosses to the device first, as in ``decompressPayload``.
+        ``bits``: the payload is the bit-packed message (flc_unpack_shift_reduce_bits), the same bits."""
         from .fused import ShiftPayloadReducer
+        if bits:
+            self._shift_bits_entry("flc_unpack_shift_reduce_bits")
         dev = _gpu_device(payload)
         d = self._dim(d)
         if payload.dtype != torch.uint8:
             raise TypeError(f"decompressShiftPayload: payload must be uint8 (got {payload.dtype})")
-        nbytes = self.payloadBytes(d)
+        nbytes = self.payloadBytes(d, bits=bits)
         if payload.numel() < nbytes:
             raise ValueError(f"decompressShiftPayload: {payload.numel()} bytes, the payload of d={d} is {nbytes}")
         payload = payload.reshape(-1)[:nbytes].to(device=dev)
@@ -738,7 +754,7 @@ class Compressor:
                 raise ValueError(f"decompressShiftPayload: {name} must be a contiguous fp32 device tensor of {d} elements")
         res = torch.empty(d, dtype=torch.float32, device=dev) if out is None else out.view(-1)
         # the fold of one row with divisor 1 is the row: (m) / 1 == m, -0 included
-        ShiftPayloadReducer(self, device=dev)([payload], d, scale=scale, base=None if base is None else base.view(-1),
+        ShiftPayloadReducer(self, device=dev, bits=bits)([payload], d, scale=scale, base=None if base is None else base.view(-1),
                                               out=res, divisor=1.0)
         return res if out is None else out
 

@@ -841,23 +841,41 @@ class ShiftPayloadReducer:
     the rows the payloads were packed from, bit for bit.  ``clients=ids`` (with ``sparse=True``): the
     mirror is an [N_total, D] state matrix and payload i updates row ``ids[i]``; rows not named are
     neither read nor written.  Any other codec, operand shape or a scale that is not finite and > 0
-    raises ``NotImplementedError`` with the library's reason: there is no silent fallback."""
+    raises ``NotImplementedError`` with the library's reason: there is no silent fallback.
 
-    def __init__(self, compressor: Compressor, device=None):
+    ``bits=True`` (here or on the call): the payloads are the bit-packed messages of
+    ``compressShiftPayload(bits=True)``, folded by flc_unpack_shift_reduce_bits — a wave per half tile of
+    1024 elements for all N rows (k_unpack_bits_shift_accum), the next row's base in flight under the
+    current row's arithmetic — to the bits of the byte payloads' fold, ``out`` and every ``msg_out``
+    row.  A codec without a bit-packed form raises ``NotImplementedError`` when the reducer is made;
+    ``sparse`` / ``clients`` do not go with it (``ValueError``)."""
+
+    def __init__(self, compressor: Compressor, device=None, bits=False):
+        self.bits = bool(bits)
+        if self.bits:                                           # the refusals, host only
+            compressor._shift_bits_entry("flc_unpack_shift_reduce_bits")
         _lib.require_gpu()
         self.comp = compressor
         self.device = _device(device)
 
     def __call__(self, payloads, d=None, *, scale=1.0, base=None, msg_out=None, out=None, weights=None, divisor=None,
-                 sparse=False, clients=None):
+                 sparse=False, clients=None, bits=None):
         """payloads: [N, ld] uint8 device tensor (rows 16-byte aligned, ld % 16 == 0) or a list of N
         16-byte aligned uint8 device tensors.  ``base``: None, [N, D], or ONE [D] vector for every row
         (MARINA's g_prev).  ``msg_out``: None or [N, D]; it may be ``base`` (EF21's server mirror in
         place).  ``weights`` / ``divisor`` as in ``PayloadReducer``.  ``sparse`` / ``clients``: the
         one-pass fold of RandK / TopK payloads (the class docstring); with ``clients`` a per-row
-        ``base`` / ``msg_out`` is [N_total, D].  Returns ``out``."""
+        ``base`` / ``msg_out`` is [N_total, D].  ``bits``: the payloads are bit-packed (None: as the
+        reducer was made).  Returns ``out``."""
         lib = _lib.load()
-        entry = "flc_unpack_shift_reduce_sparse" if sparse else "flc_unpack_shift_reduce"
+        bits = self.bits if bits is None else bool(bits)
+        if bits and (sparse or clients is not None):
+            raise ValueError("ShiftPayloadReducer: bits=True goes with neither sparse=True nor clients=... "
+                             "(the bit-packed fold takes the dense level and natural messages, every row)")
+        entry = ("flc_unpack_shift_reduce_bits" if bits else
+                 "flc_unpack_shift_reduce_sparse" if sparse else "flc_unpack_shift_reduce")
+        if bits:
+            self.comp._shift_bits_entry(entry)
         if not hasattr(lib, entry):
             raise NotImplementedError(f"this library build has no {entry}")
         if clients is not None and not sparse:
@@ -876,7 +894,7 @@ class ShiftPayloadReducer:
         else:
             payloads = list(payloads)
             n = len(payloads)
-            nbytes = int(lib.flc_payload_bytes(ctypes.byref(prm), d))
+            nbytes = int(self.comp._wire_entry("flc_payload_bytes", bits, prm)(ctypes.byref(prm), d))
             for p in payloads:
                 if not torch.is_tensor(p) or p.dtype != torch.uint8 or not p.is_cuda:
                     raise TypeError("ShiftPayloadReducer: payloads must be uint8 device tensors")

@@ -50,29 +50,31 @@ def freconStep(compressor, grad_cur, h, grad_prev, alpha, in_place=False):
 
 
 # -- the same steps emitting the message the client sends (flc_pack_shift) -------------------------
-def dianaStepWire(compressor, grad_cur, h, alpha, in_place=False):
+def dianaStepWire(compressor, grad_cur, h, alpha, in_place=False, bits=False):
     """``dianaStep`` on the wire: returns ``(payload, h_new)`` — the payload decodes to ``m_i``
-    (``decompressShiftPayload(payload)``), written in the pass that updates the shift."""
+    (``decompressShiftPayload(payload)``), written in the pass that updates the shift.  ``bits`` (here
+    and in the two steps below): the bit-packed message (flc_pack_shift_bits), decoded with the same
+    keyword."""
     payload, _, h_new = compressor.compressShiftPayload(grad_cur, h, alpha=alpha, shift=h,
-                                                        shift_out=h if in_place else None)
+                                                        shift_out=h if in_place else None, bits=bits)
     return payload, h_new
 
 
-def ef21StepWire(compressor, grad_cur, g_prev, in_place=False):
+def ef21StepWire(compressor, grad_cur, g_prev, in_place=False, bits=False):
     """``ef21Step`` on the wire: returns ``(payload, g_next)``; the server mirror applies
     ``decompressShiftPayload(payload, scale=mult, base=g_prev)`` with the same ``mult``."""
     mult = 1.0
     if not compressor.isContractionCompressor():
         mult = 1.0 / (1.0 + compressor.getW())
     payload, msg, _ = compressor.compressShiftPayload(grad_cur, g_prev, scale=mult, base=g_prev,
-                                                      out=g_prev if in_place else None, message=True)
+                                                      out=g_prev if in_place else None, message=True, bits=bits)
     return payload, msg
 
 
-def marinaStepWire(compressor, grad_cur, grad_prev):
+def marinaStepWire(compressor, grad_cur, grad_prev, bits=False):
     """MARINA's client on the wire: the payload of ``C(grad_cur - grad_prev)`` and nothing else (the
     server adds it to its ``g_prev``: ``decompressShiftPayload(payload, base=g_prev)``)."""
-    payload, _, _ = compressor.compressShiftPayload(grad_cur, grad_prev)
+    payload, _, _ = compressor.compressShiftPayload(grad_cur, grad_prev, bits=bits)
     return payload
 
 

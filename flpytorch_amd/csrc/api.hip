@@ -1010,6 +1010,71 @@ extern "C" int flc_unpack_shift_reduce_sparse(const flc_codec_params* prm, const
                                    (hipStream_t)stream);
 }
 
+// ---- bit-packed shifted steps (wire_shift_bits.hip) -------------------------------------------------
+extern "C" size_t flc_pack_shift_bits_workspace_size(const flc_codec_params* prm, int64_t d) {
+    if (!prm || !known(prm->codec) || d < 0) return 0;
+    return bits_pack_workspace(prm, d);
+}
+
+extern "C" int flc_pack_shift_bits(const flc_codec_params* prm, const flc_pattern* pat, const float* d_a, const float* d_b,
+                                   int64_t d, float msg_scale, const float* d_base, float* d_msg, float shift_alpha,
+                                   const float* d_shift_in, float* d_shift_out, void* d_payload, void* d_ws,
+                                   size_t ws_bytes, void* stream) {
+    const char* me = "flc_pack_shift_bits";
+    if (int rc = bits_codec(prm, me)) return rc;
+    if (int rc = bad_params(prm, me)) return rc;
+    if (d < 0) { set_error("%s: d < 0", me); return FLC_ERR_ARG; }
+    if (!d_payload) { set_error("%s: need a payload", me); return FLC_ERR_ARG; }
+    if (int rc = shift_row_check(me, d_a, d_b, d, d_base, d_msg, d_shift_in, d_shift_out, /*need_output=*/false)) return rc;
+    ShiftArgs sh{d_b, msg_scale, d_base, d_msg, shift_alpha, d_shift_out ? d_shift_in : nullptr, d_shift_out};
+    return bits_pack_shift_run(prm, pat, d_a, d, sh, (char*)d_payload, d_ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" size_t flc_unpack_shift_reduce_bits_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d) {
+    (void)prm; (void)n; (void)d;
+    return 0;                                       // the fold keeps everything in registers
+}
+
+extern "C" int flc_unpack_shift_reduce_bits(const flc_codec_params* prm, const flc_payload_rows* rows, int64_t n, int64_t d,
+                                            const float* d_w, float w_total, float* d_out, void* d_ws, size_t ws_bytes,
+                                            void* stream) {
+    const char* me = "flc_unpack_shift_reduce_bits";
+    (void)d_ws; (void)ws_bytes;
+    if (int rc = bits_codec(prm, me)) return rc;
+    if (n < 0 || d < 0) { set_error("%s: n=%lld d=%lld", me, (long long)n, (long long)d); return FLC_ERR_ARG; }
+    if (n > FLC_MAX_ROWS) return too_many(me, n, "payloads", FLC_ERR_UNSUPPORTED);
+    if (d == 0) return FLC_OK;
+    if (!d_out) { set_error("%s: need out", me); return FLC_ERR_ARG; }
+    flc_payload_rows pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.msg_scale = 1.f;
+    if (n > 0) {
+        if (!rows || (!rows->d_payloads && !rows->d_payload_ptrs)) { set_error("%s: no payloads", me); return FLC_ERR_ARG; }
+        pr = *rows;
+        if (pr.d_payloads) {
+            pr.d_payload_ptrs = nullptr;
+            if ((uintptr_t)pr.d_payloads & 15u) { set_error("%s: payload rows must be 16-byte aligned", me); return FLC_ERR_ARG; }
+            if (pr.ld_bytes < bits_payload_bytes(prm, d) || (pr.ld_bytes & 15)) {
+                set_error("%s: ld_bytes=%lld, at least the bit-packed payload's %lld bytes and a multiple of 16", me,
+                          (long long)pr.ld_bytes, (long long)bits_payload_bytes(prm, d));
+                return FLC_ERR_ARG;
+            }
+        }
+        if (!pr.d_base) pr.ldbase = 0;
+        if (!pr.d_msg) pr.ldmsg = 0;
+        if (int rc = outputs_overlap(me, {{"d_msg", "ldmsg", pr.d_msg, pr.ldmsg}}, pr.d_base, pr.ldbase, n, d)) return rc;
+        // the fold loads base row i + 1 before it stores msg row i: the msg rows are the base rows in
+        // place (same pointer and leading dimension) or lie apart from them
+        if (pr.d_msg && pr.d_base && pr.ldbase != 0 && !(pr.d_msg == pr.d_base && pr.ldmsg == pr.ldbase)) {
+            uintptr_t m0, m1, b0, b1;
+            row_span(pr.d_msg, pr.ldmsg, n, d, &m0, &m1);
+            row_span(pr.d_base, pr.ldbase, n, d, &b0, &b1);
+            if (m0 < b1 && b0 < m1) { set_error("%s: d_msg overlaps d_base without being d_base in place", me); return FLC_ERR_ARG; }
+        }
+    }
+    return bits_unpack_shift_reduce_run(prm, pr, n, d, d_w, w_total, d_out, (hipStream_t)stream);
+}
+
 namespace flc {
 // the torch-order mode restates p = 2 of the dithering codecs; p = inf: a maximum, exact in any order
 static bool dithering(int codec) { return codec == FLC_STD_DITHERING || codec == FLC_NAT_DITHERING; }

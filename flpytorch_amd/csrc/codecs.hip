@@ -1374,6 +1374,10 @@ int ew_run(const flc_codec_params* prm, const flc_pattern* pat, RowSrc src, bool
     UniformSrc us{compat ? pat->d_uniforms : nullptr, (pat && pat->uniforms_ld) ? pat->uniforms_ld : d};
     auto go = [&](auto op, const float* levels, int s) -> int {
         if (sr) return launch_shift_accum(*sr, n, d, op, levels, s, w, wt, out, st, map);
+        if (sh && ca && ca->bits) {                  // flc_pack_shift_bits (wire_shift_bits.hip)
+            if constexpr (BitsOp<decltype(op)>::value) return launch_shift_code_bits(src.base, d, op, levels, s, *sh, *ca, st);
+            else { set_error("ew_run: codec %d has no bit-packed form", codec); return FLC_ERR_UNSUPPORTED; }
+        }
         if (sh && ca) return launch_shift_code(src.base, d, op, levels, s, *sh, *ca, st);
         if (sh) return launch_shift(src.base, d, op, levels, s, *sh, st);
         if (ca && ca->bits) {                        // flc_pack_bits: the bit-packed form (wire_bits.hip)

@@ -283,6 +283,14 @@ int bits_pack_run(const flc_codec_params* prm, const flc_pattern* pat, const flo
 int bits_unpack_run(const flc_codec_params* prm, const char* payload, int64_t d, float* out, hipStream_t st);
 int bits_unpack_reduce_run(const flc_codec_params* prm, const char* base, int64_t ld, const char* const* ptrs, int64_t n,
                            int64_t d, const float* w, float wt, float* out, hipStream_t st);
+// the bit-packed shifted steps (flc_pack_shift_bits: wire_bits.hip's host over wire_shift_bits.hip's
+// k_ew_shift_code_bits; flc_unpack_shift_reduce_bits: wire_shift_bits.hip); bits_decode_check: the
+// decoders' codec check under the entry's name
+int bits_decode_check(const flc_codec_params* prm, const char* me);
+int bits_pack_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const float* a, int64_t d, const ShiftArgs& sh,
+                        char* payload, void* ws, size_t ws_bytes, hipStream_t st);
+int bits_unpack_shift_reduce_run(const flc_codec_params* prm, const flc_payload_rows& pr, int64_t n, int64_t d,
+                                 const float* w, float wt, float* out, hipStream_t st);
 // the seeded RandK message (wire_seeded.hip, FMT_SEEDED): flc_pack_seeded & co.; randk.hip's count
 // pass with the keys given by (seed, client0 + row) or read from the n messages' draw blocks
 int randk_counts_keyed(uint64_t seed, int64_t client0, int64_t n, int64_t d, int64_t K, uint32_t* cnt, uint64_t* ckey,

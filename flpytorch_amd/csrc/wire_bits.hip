@@ -171,22 +171,6 @@ template int launch_code_bits(const float*, int64_t, NaturalOp<true>, const floa
 template int launch_code_bits(const float*, int64_t, NaturalOp<false>, const float*, int, const CodeArgs&, hipStream_t);
 
 // ---- decode ----------------------------------------------------------------------------------------
-// a lane's 32 values of a tile to the dense row: eight float4, or the elements below d
-__device__ inline void bt_store(float* __restrict__ out, int64_t j0, int64_t d, const float* e) {
-    const bool al = ((uintptr_t)out & 15u) == 0;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int64_t j = j0 + 256 * t;
-        if (al && j + 3 < d) {
-            *reinterpret_cast<float4*>(out + j) = make_float4(e[4 * t], e[4 * t + 1], e[4 * t + 2], e[4 * t + 3]);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (j + q < d) out[j + q] = e[4 * t + q];
-        }
-    }
-}
-
 // One payload to a dense row: a wave per tile (the fold's ownership, no accumulation).  The format,
 // b and s come from the codec, never from the message (flc_payload_validate_bits reports a header
 // that lies), and the body is read within the bytes flc_payload_bits_bytes sized.
@@ -289,35 +273,43 @@ size_t bits_pack_workspace(const flc_codec_params* prm, int64_t d) {
     return b;
 }
 
-int bits_pack_run(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, char* payload, void* ws,
-                  size_t ws_bytes, hipStream_t st) {
-    if (int rc = bits_refuse(prm, "flc_pack_bits")) return rc;
+// flc_pack_bits (sh null: the row x) and flc_pack_shift_bits (the row x - sh->b, with the epilogues of
+// *sh): everything refused before the header is written
+static int bits_pack_go(const char* me, const flc_codec_params* prm, const flc_pattern* pat, const float* x,
+                        const ShiftArgs* sh, int64_t d, char* payload, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (int rc = bits_refuse(prm, me)) return rc;
     const bool dither = prm->codec == FLC_STD_DITHERING;
     if (dither) if (int rc = check_dither(prm)) return rc;
-    if (ws_bytes < bits_pack_workspace(prm, d)) { set_error("flc_pack_bits: workspace too small"); return FLC_ERR_WORKSPACE; }
-    if ((uintptr_t)payload & 15u) { set_error("flc_pack_bits: payload must be 16-byte aligned"); return FLC_ERR_ARG; }
+    if (ws_bytes < bits_pack_workspace(prm, d)) { set_error("%s: workspace too small", me); return FLC_ERR_WORKSPACE; }
+    if ((uintptr_t)payload & 15u) { set_error("%s: payload must be 16-byte aligned", me); return FLC_ERR_ARG; }
     BitsWs w = carve_bits(ws, prm, d, nullptr);
     hipLaunchKernelGGL(k_bits_header, dim3(1), dim3(64), 0, st, payload, (uint32_t)bits_format(prm), (uint32_t)d);
     FLC_CHECK_LAUNCH("k_bits_header");
     if (d == 0) return FLC_OK;
-    // the norm pass, then ONE pass from x to the packed words (codecs.hip ew_run -> k_ew_code_bits)
+    // the norm pass (over x - b for a shifted step), then ONE pass to the packed words (codecs.hip
+    // ew_run -> k_ew_code_bits, or wire_shift_bits.hip's k_ew_shift_code_bits)
     CodeArgs ca{0, payload, prm->d_levels, prm->s, dither ? w.pnorm : nullptr, bits_width(prm)};
     RowSrc src{x, d, nullptr};
-    return ew_run(prm, pat, src, ((uintptr_t)x & 15u) == 0, 1, d, nullptr, dither ? w.pnorm : nullptr, /*dense=*/true,
-                  nullptr, nullptr, 1.f, w.inner, w.inner_bytes, st, nullptr, &ca);
+    const bool vec = (((uintptr_t)x | (uintptr_t)(sh ? sh->b : nullptr)) & 15u) == 0;
+    return ew_run(prm, pat, src, vec, 1, d, nullptr, dither ? w.pnorm : nullptr, /*dense=*/true, nullptr, nullptr, 1.f,
+                  w.inner, w.inner_bytes, st, sh, &ca);
 }
 
-static int bits_decode_check(const flc_codec_params* prm, const char* me) {
+int bits_pack_run(const flc_codec_params* prm, const flc_pattern* pat, const float* x, int64_t d, char* payload, void* ws,
+                  size_t ws_bytes, hipStream_t st) {
+    return bits_pack_go("flc_pack_bits", prm, pat, x, nullptr, d, payload, ws, ws_bytes, st);
+}
+
+int bits_pack_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const float* a, int64_t d, const ShiftArgs& sh,
+                        char* payload, void* ws, size_t ws_bytes, hipStream_t st) {
+    return bits_pack_go("flc_pack_shift_bits", prm, pat, a, &sh, d, payload, ws, ws_bytes, st);
+}
+
+int bits_decode_check(const flc_codec_params* prm, const char* me) {
     if (int rc = bits_refuse(prm, me)) return rc;
     if (prm->codec == FLC_STD_DITHERING && !prm->d_levels) { set_error("%s: dithering needs the level table", me); return FLC_ERR_ARG; }
     return FLC_OK;
 }
-
-#define FLC_BITS_SWITCH(b, CASE)                                                                   \
-    switch (b) {                                                                                   \
-        case 2: CASE(2) break; case 3: CASE(3) break; case 4: CASE(4) break; case 5: CASE(5) break; \
-        case 6: CASE(6) break; case 7: CASE(7) break; default: CASE(9) break;                      \
-    }
 
 int bits_unpack_run(const flc_codec_params* prm, const char* payload, int64_t d, float* out, hipStream_t st) {
     if (int rc = bits_decode_check(prm, "flc_unpack_bits")) return rc;

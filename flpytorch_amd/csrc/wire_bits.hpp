@@ -16,4 +16,17 @@ template <bool COMPAT> struct BitsOp<NaturalOp<COMPAT>> : std::true_type {};
 template <class Op>
 int launch_code_bits(const float* x, int64_t d, Op op, const float* levels, int s, const CodeArgs& ca, hipStream_t st);
 
+// the same pass over a - b with the shift epilogues (flc_pack_shift_bits), instantiated in
+// wire_shift_bits.hip
+template <class Op>
+int launch_shift_code_bits(const float* a, int64_t d, Op op, const float* levels, int s, const ShiftArgs& sh,
+                           const CodeArgs& ca, hipStream_t st);
+
+// one statement per width of the bit-packed forms: CASE(2) .. CASE(7), CASE(9)
+#define FLC_BITS_SWITCH(b, CASE)                                                                   \
+    switch (b) {                                                                                   \
+        case 2: CASE(2) break; case 3: CASE(3) break; case 4: CASE(4) break; case 5: CASE(5) break; \
+        case 6: CASE(6) break; case 7: CASE(7) break; default: CASE(9) break;                      \
+    }
+
 }  // namespace flc

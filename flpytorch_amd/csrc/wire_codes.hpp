@@ -134,25 +134,68 @@ __device__ inline void bt_each(F&& f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
 }
 
-// A lane's 32 values from its B words.  NAT9: the code is the value's top nine bits.  Level codes:
-// `lv` is |levels[min(lane, s)]|, so an element's magnitude is lane idx's register (one cross-lane
-// read, no LDS table, no barrier) and an index past s reads the top level; then the sign and the
-// norm exactly as lev_decode: (levels[idx] * sign) * norm, code 0 the exact +0.  Every lane of the
-// wave must be active.
+// A code's value.  NAT9: the code is the value's top nine bits.  Level codes: `lv` is
+// |levels[min(lane, s)]|, so an element's magnitude is lane idx's register (one cross-lane read, no
+// LDS table, no barrier) and an index past s reads the top level; then the sign and the norm exactly
+// as lev_decode: (levels[idx] * sign) * norm, code 0 the exact +0.  Every lane of the wave must be
+// active.
+template <int B>
+__device__ inline float bt_value(uint32_t c, float lv, float norm) {
+    if constexpr (B == 9) {
+        return __uint_as_float(c << 23);
+    } else {
+        const uint32_t idx = c & ((1u << (B - 1)) - 1u);
+        const uint32_t mag = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << 2), (int)__float_as_uint(lv));
+        const float v = __uint_as_float(mag | ((c >> (B - 1)) << 31)) * norm;
+        return c == 0u ? 0.f : v;
+    }
+}
+
+// A lane's 32 values from its B words.
 template <int B>
 __device__ inline void bt_decode(const uint32_t (&w)[B], float lv, float norm, float* e) {
     bt_each([&](auto ic) {
         constexpr int I = decltype(ic)::value;
-        const uint32_t c = bt_get<B, I>(w);
-        if constexpr (B == 9) {
-            e[I] = __uint_as_float(c << 23);
-        } else {
-            const uint32_t idx = c & ((1u << (B - 1)) - 1u);
-            const uint32_t mag = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << 2), (int)__float_as_uint(lv));
-            const float v = __uint_as_float(mag | ((c >> (B - 1)) << 31)) * norm;
-            e[I] = c == 0u ? 0.f : v;
-        }
+        e[I] = bt_value<B>(bt_get<B, I>(w), lv, norm);
     }, std::make_integer_sequence<int, 32>{});
 }
+
+// Half a lane's tile: codes 16 H .. 16 H + 15 (steps t = 4 H .. 4 H + 3) lie in words K0 .. K0 + NW - 1
+// of the lane (for odd B the middle word belongs to both halves).
+template <int B, int H>
+struct BtHalf {
+    static constexpr int K0 = (16 * B * H) >> 5, NW = ((16 * B * (H + 1) + 31) >> 5) - K0;
+};
+
+template <int B, int H>
+__device__ inline void bt_decode_half(const uint32_t (&w)[BtHalf<B, H>::NW], float lv, float norm, float* e) {
+    bt_each([&](auto ic) {
+        constexpr int I = decltype(ic)::value;
+        constexpr int P = B * (16 * H + I), k = (P >> 5) - BtHalf<B, H>::K0, sh = P & 31;
+        uint32_t c = w[k] >> sh;
+        if constexpr (sh + B > 32) c |= w[k + 1] << (32 - sh);
+        e[I] = bt_value<B>(c & ((1u << B) - 1u), lv, norm);
+    }, std::make_integer_sequence<int, 16>{});
+}
+
+// a lane's 32 values of a tile to the dense row: eight float4, or the elements below d
+__device__ inline void bt_store(float* __restrict__ out, int64_t j0, int64_t d, const float* e) {
+    const bool al = ((uintptr_t)out & 15u) == 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int64_t j = j0 + 256 * t;
+        if (al && j + 3 < d) {
+            *reinterpret_cast<float4*>(out + j) = make_float4(e[4 * t], e[4 * t + 1], e[4 * t + 2], e[4 * t + 3]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (j + q < d) out[j + q] = e[4 * t + q];
+        }
+    }
+}
+
+// the base operand of the shifted-wire folds (wire_shift.hip, wire_shift_bits.hip): none, a row per
+// payload, or ONE [d] vector for every row (ldbase == 0)
+enum { UB_NONE = 0, UB_ROWS = 1, UB_SHARED = 2 };
 
 }  // namespace flc

@@ -89,8 +89,8 @@ int pack_shift_run(const flc_codec_params* prm, const flc_pattern* pat, const fl
 // of base included: every element of a row is read and written by one thread, the base load before
 // the store).  A shared base (MARINA's g_prev) is loaded once, outside the row loop.  VEC: base / msg
 // rows as float4s (16-byte aligned, leading dimensions multiples of 4); else element loads and stores,
-// the same bits.  The format and s come from the codec, never from the message.
-enum { UB_NONE = 0, UB_ROWS = 1, UB_SHARED = 2 };
+// the same bits.  The format and s come from the codec, never from the message.  (base_mode: UB_*,
+// wire_codes.hpp)
 
 template <int FMT, bool W, int PF, bool VEC>
 __global__ __launch_bounds__(256) void k_unpack_shift_accum(const char* __restrict__ pbase, int64_t ld,

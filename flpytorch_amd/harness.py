@@ -297,9 +297,10 @@ class Simulation:
         self.wire = wire
         # wire_bits=True (with wire): the messages go in the bit-packed form (compressPayload(bits=True):
         # natural at 9 bits, qsgd / terngrad with s <= 63 at 1 + bit_length(s)), validated with the
-        # bit-packed check on receipt; same iterates and history, fewer payload_bytes
-        if wire_bits and not wire:
-            raise ValueError("wire_bits goes with wire=True or wire='socket'")
+        # bit-packed check on receipt; same iterates and history, fewer payload_bytes.  With shift_wire
+        # the shifted steps' messages go that way (compressShiftPayload / decompressShiftPayload(bits=True))
+        if wire_bits and not (wire or shift_wire):
+            raise ValueError("wire_bits goes with wire=True or wire='socket' (or shift_wire)")
         self.wire_bits = bool(wire_bits)
         if self.wire_bits:
             try:
@@ -464,6 +465,7 @@ class Simulation:
         # the product's codec runs on the MI355X whatever device the client state lives on (like
         # _on_gpu); another implementation of the protocol (a test's double) takes the tensors as they are
         on_gpu = isinstance(comp, ag.Compressor)
+        bits = {"bits": True} if self.wire_bits else {}                          # (a double need not know the keyword)
 
         def dev(t):
             return t.cuda() if on_gpu and t.device.type != "cuda" else t
@@ -473,25 +475,25 @@ class Simulation:
             return self.transfer(comp, payload, d) if self.link is not None else payload
         if self.algorithm == "diana":                                            # algorithms.py:1383-1392
             h = dev(cs["hi"])
-            payload, _, h_new = comp.compressShiftPayload(dev(g), h, alpha=self.H["alpha"], shift=h)
+            payload, _, h_new = comp.compressShiftPayload(dev(g), h, alpha=self.H["alpha"], shift=h, **bits)
             cs["hi"] = h_new.to(home)
-            out = comp.decompressShiftPayload(ship(payload), d)
+            out = comp.decompressShiftPayload(ship(payload), d, **bits)
         elif self.algorithm == "marina":                                         # algorithms.py:512-540
             if cs["ck"] == 1:
                 cs["stats"]["send_scalars_to_master"] += d
                 return g
             _, g_old = self.model.value_and_gradient(self.H["x_prev"], cs["client_id"])
-            payload, _, _ = comp.compressShiftPayload(dev(g), dev(g_old))
-            out = comp.decompressShiftPayload(ship(payload), d, base=dev(self.H["g_prev"].to(home)))
+            payload, _, _ = comp.compressShiftPayload(dev(g), dev(g_old), **bits)
+            out = comp.decompressShiftPayload(ship(payload), d, base=dev(self.H["g_prev"].to(home)), **bits)
         else:                                                                    # EF21, algorithms.py:1494-1518
             if cs["g_prev"] is None:
                 cs["g_prev"] = g                                                 # (first step: not counted)
                 return g
             mult = 1.0 if comp.isContractionCompressor() else 1.0 / (1.0 + comp.getW())
             g_prev = dev(cs["g_prev"])
-            payload, g_next, _ = comp.compressShiftPayload(dev(g), g_prev, scale=mult, base=g_prev, message=True)
+            payload, g_next, _ = comp.compressShiftPayload(dev(g), g_prev, scale=mult, base=g_prev, message=True, **bits)
             cs["g_prev"] = g_next.to(home)                                       # the client's own estimator
-            out = comp.decompressShiftPayload(ship(payload), d, scale=mult, base=g_prev)   # the server's mirror
+            out = comp.decompressShiftPayload(ship(payload), d, scale=mult, base=g_prev, **bits)   # the server's mirror
         cs["stats"]["send_scalars_to_master"] += comp.last_need_to_send_advance
         return out.to(home)
 

@@ -905,6 +905,51 @@ int flc_unpack_shift_reduce_sparse(const flc_codec_params* prm, const flc_payloa
                                    float* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ----------------------------------------------------------------------------------------
+ * Bit-packed shifted steps (additive: flc_version() stays 104, detect the entries by their symbols):
+ * flc_pack_shift and flc_unpack_shift_reduce with the message in its bit-packed form ("Bit-packed
+ * messages" above: LBITS at b = 1 + bit_length(s) bits for std dithering / qsgd / terngrad with
+ * s <= 63, NAT9 for natural).  Arguments, operand rules (aliases included) and the order and rounding
+ * of every operation are those of the byte entries; only the payload differs.
+ *
+ * flc_pack_shift_bits — one client row.  d_payload (16-byte aligned, flc_payload_bits_bytes) receives,
+ * byte for byte, what flc_pack_bits writes for the fp32 row x = a - b under the same prm / pat: header
+ * {format word, d, the norm of a - b, bad}, then the tiles.  d_msg and d_shift_out get flc_pack_shift's
+ * bits.  One pass after the norm pass (k_ew_shift_code_bits): a, b [, base, shift_in] are read once,
+ * the codes are packed in registers and leave as b coalesced words per tile with msg / shift_out; no
+ * byte-format message and no dense C(a - b) row is written.  d == 0 writes the header alone.
+ * Workspace: flc_pack_bits'.
+ *
+ * flc_unpack_shift_reduce_bits — the server, over flc_payload_rows exactly as flc_unpack_shift_reduce
+ * takes it (ld_bytes >= flc_payload_bits_bytes, a multiple of 16).  d_out and every d_msg row equal
+ * flc_unpack_shift_reduce's over the byte payloads of the same rows, bit for bit, so n x
+ * flc_pack_shift_bits followed by this fold closes the identity stated above with
+ * flc_encode_shift_reduce.  One pass (k_unpack_bits_shift_accum): a wave folds half a tile (1024
+ * elements) for all n rows in client order with the next row's base loads in flight; an in-place
+ * EF21 mirror moves (8 + b / 8) n d + 4 d bytes, a shared base or the plain fold (b / 8) n d + 4 d.
+ * The format, b and s come from prm, never from a message; no address beyond flc_payload_bits_bytes
+ * of a message or beyond d of a row is formed whatever the bytes are.  Workspace: none (the query
+ * returns 0; d_ws may be NULL).
+ *
+ * Checked before any launch; a refused call writes nothing.  FLC_ERR_UNSUPPORTED first, for every
+ * codec without a bit-packed form (flc_payload_bits_format == 0; the client's size query then
+ * returns 0) and for n > FLC_MAX_ROWS.  FLC_ERR_ARG as the byte entries', and on the server also
+ * d_msg rows that overlap the d_base rows without being them in place (same pointer and leading
+ * dimension): the fold reads base row i + 1 before it stores msg row i.  FLC_ERR_WORKSPACE: the
+ * client's ws_bytes below its size query.  Server: d == 0 returns FLC_OK without touching the device;
+ * n == 0 with d > 0 zero-fills d_out.
+ * -------------------------------------------------------------------------------------- */
+size_t flc_pack_shift_bits_workspace_size(const flc_codec_params* prm, int64_t d);
+int flc_pack_shift_bits(const flc_codec_params* prm, const flc_pattern* pat,
+                        const float* d_a, const float* d_b, int64_t d,
+                        float msg_scale, const float* d_base, float* d_msg,
+                        float shift_alpha, const float* d_shift_in, float* d_shift_out,
+                        void* d_payload, void* d_ws, size_t ws_bytes, void* stream);
+size_t flc_unpack_shift_reduce_bits_workspace_size(const flc_codec_params* prm, int64_t n, int64_t d);
+int flc_unpack_shift_reduce_bits(const flc_codec_params* prm, const flc_payload_rows* rows,
+                                 int64_t n, int64_t d, const float* d_w, float w_total,
+                                 float* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ----------------------------------------------------------------------------------------
  * Multi-GPU combine on a caller-owned RCCL communicator (rccl_comm: an ncclComm_t, passed as
  * void* so no RCCL type crosses the boundary).  Each rank's d_partial holds the client-order
  * partial sum of its client block (flc_encode_reduce / flc_unpack_reduce with w_total = 1.0);

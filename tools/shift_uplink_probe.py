@@ -71,6 +71,18 @@ compared as int32.  Byte models: sparse 4 N D + 12 N K + 4 D (mirror in place; 8
 base) against about 28 N D; the summary carries the two kernels' own times.  Writes
 <out-dir>/<spec>_<shape>.jsonl (default profiles/r17/sparse_wire).
 
+--wire --bits (specs with a bit-packed form, default natural,terngrad,qsgd:7,qsgd:63; device draws): the
+bit-packed shifted steps against the byte-format ones, payloads packed once outside the clock,
+  ef21     ShiftPayloadReducer(P, base = msg_out = M, scale = mult)   the server mirror in place, N payloads
+  marina   ShiftPayloadReducer(P, base = g_prev)                      one shared base, nothing stored
+  diana    compressShiftPayload(g, h, alpha, shift = shift_out = h)   the client pack, one row in place
+each as `bits` (flc_unpack_shift_reduce_bits / flc_pack_shift_bits) and `bytes` (flc_unpack_shift_reduce /
+flc_pack_shift) on its own copy of the in-place operand, interleaved in one process on one allocation;
+after every repeat the outputs and the in-place operands are compared as int32.  Byte models: mirror in
+place (8 + c) N D + 4 D, shared base c N D + 8 D, client (norm 8 +) 16 + c per element, with c the code
+bytes per element of the message (b / 8 against 1 or 2).  Writes <out-dir>/<spec>_<shape>.jsonl (default
+profiles/r21/shift_wire_bits).
+
 --frecon (elementwise specs, default qsgd:127,natural; device draws): the FRECON round with its server tail,
   one_call     FreconUplinkReducer(G, H, P, alpha, server=...)                flc_frecon_reduce
   composition  ShiftUplinkReducer twice (in-place DIANA over (G, H), the plain fold over (G, P)) and the
@@ -660,6 +672,99 @@ def main_wire_sparse(a):
         del P
 
 
+def main_wire_bits(a):
+    import torch
+
+    from flpytorch_amd import _lib
+    from flpytorch_amd import aggregation as ag
+    _lib.require_gpu()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n, d = a.n, a.d
+    os.makedirs(a.out_dir, exist_ok=True)
+    gen = torch.Generator(device=dev).manual_seed(1000)
+
+    def filled(rows):
+        t = torch.empty((rows, d), dtype=torch.float32, device=dev)
+        for i in range(0, rows, 64):
+            t[i:i + 64].normal_(generator=gen)
+        return t
+    G, M0, gprev = filled(n), filled(n), filled(1)[0]
+    M = {v: torch.empty_like(M0) for v in ("bits", "bytes")}
+    outs = {v: torch.empty(d, dtype=torch.float32, device=dev) for v in ("bits", "bytes")}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for spec in a.specs.split(","):
+        comp = ag.initCompressor(spec, d)
+        pb = {"bits": comp.payloadBytes(d, bits=True), "bytes": comp.payloadBytes(d)}
+        code = {v: (pb[v] - 16) / d for v in pb}       # code bytes per element
+        norm = 0 if spec.startswith("natural") else 8  # the norm pass reads a and b once more
+        alpha = 1.0 / (1.0 + comp.getW())
+        mult = 1.0 if comp.isContractionCompressor() else 1.0 / (1.0 + comp.getW())
+        P = {v: torch.empty((n, pb[v]), dtype=torch.uint8, device=dev) for v in pb}    # packed once, outside the clock
+        for i in range(n):
+            for v in pb:
+                comp.device_rng = (SEED, i)
+                comp.compressShiftPayload(G[i], M0[i], payload_out=P[v][i], bits=v == "bits")
+        comp.device_rng = (SEED, 0)
+        red = {v: ag.ShiftPayloadReducer(comp, device=dev, bits=v == "bits") for v in pb}
+        for shape in ("ef21", "marina", "diana"):
+            for v in pb:
+                M[v].copy_(M0)
+            if shape == "ef21":                        # the server mirror in place, each leg on its own copy
+                runs = {v: (lambda v=v: red[v](P[v], d, scale=mult, base=M[v], msg_out=M[v], out=outs[v])) for v in pb}
+                model = {v: int((8 + code[v]) * n * d + 4 * d) for v in pb}
+            elif shape == "marina":                    # one shared base, nothing stored
+                runs = {v: (lambda v=v: red[v](P[v], d, base=gprev, out=outs[v])) for v in pb}
+                model = {v: int(code[v] * n * d + 8 * d) for v in pb}
+            else:                                      # the client pack of one row, DIANA in place
+                pl = {v: torch.empty(pb[v], dtype=torch.uint8, device=dev) for v in pb}
+                runs = {v: (lambda v=v: comp.compressShiftPayload(G[0], M[v][0], alpha=alpha, shift=M[v][0], shift_out=M[v][0],
+                                                                  payload_out=pl[v], bits=v == "bits")) for v in pb}
+                model = {v: int((norm + 8 + 4 + code[v]) * d) for v in pb}
+
+            def agree():
+                return (torch.equal(outs["bits"].view(torch.int32), outs["bytes"].view(torch.int32))
+                        and torch.equal(M["bits"].view(torch.int32), M["bytes"].view(torch.int32)))
+            for f in runs.values():                    # warm: code objects, workspaces
+                f()
+            torch.cuda.synchronize()
+            if not agree():
+                raise SystemExit(f"{spec} {shape}: the bit-packed and the byte-format step differ after the warm-up call")
+            ms = {v: [] for v in runs}
+            path = os.path.join(a.out_dir, spec.replace(":", "_") + f"_{shape}.jsonl")
+            with open(path, "w") as fh:
+                def emit(rec):
+                    line = json.dumps(rec)
+                    fh.write(line + "\n")
+                    fh.flush()
+                    print(line, flush=True)
+                extra = {"spec": spec, "shape": shape, "n": 1 if shape == "diana" else n, "d": d, "payload_bytes": pb}
+                for r in range(a.repeats):
+                    for v, f in runs.items():
+                        e0.record()
+                        for _ in range(a.steps):
+                            f()
+                        e1.record()
+                        e1.synchronize()
+                        t = e0.elapsed_time(e1) / a.steps
+                        ms[v].append(t)
+                        emit(dict(extra, repeat=r, variant=v, ms_per_call=round(t, 4)))
+                    if not agree():
+                        raise SystemExit(f"{spec} {shape}: the bit-packed and the byte-format step differ after repeat {r}")
+                med = {v: statistics.median(ms[v]) for v in runs}
+                verdict = ("faster beyond the spread" if max(ms["bits"]) < min(ms["bytes"]) else
+                           "slower beyond the spread" if min(ms["bits"]) > max(ms["bytes"]) else "within the spread")
+                emit(dict(extra, summary=True, repeats=a.repeats, steps=a.steps,
+                          median_ms={v: round(med[v], 4) for v in runs}, min_ms={v: round(min(ms[v]), 4) for v in runs},
+                          max_ms={v: round(max(ms[v]), 4) for v in runs}, model_bytes=model,
+                          TBps_of_model_at_median={v: round(model[v] / med[v] / 1e9, 3) for v in runs},
+                          bytes_over_bits=round(med["bytes"] / med["bits"], 3),
+                          byte_model_bytes_over_bits=round(model["bytes"] / model["bits"], 3),
+                          bits_against_bytes=verdict, bits_equal_every_repeat=True))
+            print("wrote", path, flush=True)
+        del P
+
+
 def main_frecon(a):
     import torch
 
@@ -917,6 +1022,7 @@ def main():
     ap.add_argument("--topk", action="store_true", help="TopK specs: flc_topk_shift_reduce against the general entry")
     ap.add_argument("--one-read", action="store_true", help="QSGD specs: flc_dither_shift_reduce against the general entry")
     ap.add_argument("--wire", action="store_true", help="flc_pack_shift / flc_unpack_shift_reduce against their compositions")
+    ap.add_argument("--bits", action="store_true", help="with --wire: the bit-packed shifted steps against the byte-format ones")
     ap.add_argument("--frecon", action="store_true", help="flc_frecon_reduce against two fused rounds plus the tail in torch")
     ap.add_argument("--shapes", default="diana,ef21", help="--topk / --one-read: the in-place rounds to time")
     ap.add_argument("--sampled", action="store_true", help="the _sampled entries against gather + contiguous entry + scatter")
@@ -937,6 +1043,13 @@ def main():
             a.out_dir = os.path.join(ROOT, "profiles", "r17", "sparse_wire")
         if a.specs == ap.get_default("specs"):
             a.specs = "topk:1%,randk:1%"
+    if a.bits and (not a.wire or a.sparse):
+        ap.error("--bits goes with --wire (and not with --sparse)")
+    if a.bits:
+        if a.out_dir == ap.get_default("out_dir"):
+            a.out_dir = os.path.join(ROOT, "profiles", "r21", "shift_wire_bits")
+        if a.specs == ap.get_default("specs"):
+            a.specs = "natural,terngrad,qsgd:7,qsgd:63"
     if a.wire and a.out_dir == ap.get_default("out_dir"):
         a.out_dir = os.path.join(ROOT, "profiles", "r13", "shift_wire")
     if a.wire and a.specs == ap.get_default("specs"):
@@ -951,6 +1064,8 @@ def main():
         return main_sampled(a)
     if a.wire and a.sparse:
         return main_wire_sparse(a)
+    if a.wire and a.bits:
+        return main_wire_bits(a)
     if a.sparse:
         return main_sparse(a)
     if a.topk:
